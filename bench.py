@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: local analyses / second of the LETKF hot path (BASELINE.json).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 Workload at N = 1 is BASELINE config 2: LETKF, G = 1e5 grid points, k = 40 members,
 observations at every 2nd grid point (P = 5e4), Gaspari-Cohn radius 10 (19-20 local obs),
@@ -37,6 +37,7 @@ G_PER_GPU = 100000
 PEAK_FP32_TFLOPS = 157.3     # MI355X FP32 vector = FP32 MFMA peak (MI355X_MICROARCH.md)
 PEAK_F16_TFLOPS = 2516.8      # dense F16 / BF16 MFMA: 16 x the F32 rate (same guide)
 PEAK_HBM_GBS = 8000.0
+DUMP_BYTES = 64 << 20        # --dump-outputs: at most this much in all
 
 
 def algorithmic_flops(k, p, m):
@@ -192,6 +193,23 @@ def make_case(G, k, stride, device, seed=42):
     d = (y - mean).contiguous()
     grid_x = torch.arange(G, device=device, dtype=torch.float64)
     return X, grid_x, obs_x, Yb, d
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one ``path/<name>.npy`` per array, as the timed path returned it (float32 / float64).  Arrays past their
+    share of DUMP_BYTES keep a fixed, seeded sample of their last axis (grid points), whose indices go to ``<name>_index.npy``."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), "%s: %s" % (name, a.dtype)
+        if a.nbytes > share:
+            n = a.shape[-1]
+            n_keep = n * (share // 2) // a.nbytes          # (half the share: the index array fits beside it)
+            idx = np.sort(np.random.RandomState(0).choice(n, n_keep, replace=False))
+            np.save(os.path.join(path, name + "_index.npy"), idx.astype(np.float64))
+            a = np.ascontiguousarray(a[..., idx])
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def make_case_2d(ny, nx, k, stride, device, seed=42, m=1):
@@ -450,6 +468,8 @@ def dryrun(args, rank, world):
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     ranks = dist.get_world_size()
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"analysis": out.numpy()})
         print(json.dumps({"metric": "local analyses/sec (LETKF, 40-member)", "value": G * args.steps / float(t.item()),
                           "unit": "analyses/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                           "ms_per_step": 1e3 * float(t.item()) / args.steps, "higher_is_better": True, "scaling": "weak",
@@ -475,6 +495,9 @@ def main():
                          "is collected; 1 = serial steps")
     ap.add_argument("--method", default="auto", choices=["auto", "eig", "matfun"],
                     help="analysis route: auto = eigensolver-free matfun kernel (default), eig = fused Jacobi")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the analysis ensemble of the last timed step to DIR/analysis.npy "
+                         "(float32; a seeded sample of grid points beyond %d MB)" % (DUMP_BYTES >> 20))
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -580,21 +603,18 @@ def main():
     gc.freeze()
     # warm-up LAST, straight into the timed loop: the collection above leaves the GPU idle for ~0.1 s and the clocks
     # take a few milliseconds of work to come back (20 timed steps right after it ran 25 % slower than steady state)
-    # Untimed conditioning of clocks and caches; then EXACTLY --warmup steps straight into the timed region.  A timed region of
-    # fewer than 200 steps lasts a few milliseconds (20 steps: 1.5 ms), less than the host's scheduling noise: such a region is
-    # timed `repeats` times back to back (each bracketed by barrier + synchronize as the contract asks) and the MEDIAN
-    # region is reported -- `steps` stays what was asked, `repeats` says how many regions were measured.
+    # Untimed conditioning of clocks and caches; then EXACTLY --warmup steps straight into the timed region, which is ONE region
+    # of exactly --steps steps bracketed by barrier + synchronize.  A region of fewer than 200 steps lasts a few milliseconds
+    # (20 steps: 1.5 ms), not much more than the host's scheduling noise: the caller sizes --steps from ms_per_step.
     run(max(50, args.warmup), depth)
-    repeats = 1 if args.steps >= 200 else max(25, min(200, 4000 // max(args.steps, 1)))
     warm = args.warmup
     run(warm, depth)
     runner.kernel_timings.clear()
     co_l0, co_s0 = _cabi_stats()
-    regions = []
-    for _ in range(repeats):
-        el_i, out = timed(args.steps, depth)
-        regions.append(el_i)
-    elapsed = float(np.median(regions))
+    elapsed, out = timed(args.steps, depth)
+    if args.dump_outputs and rank == 0:
+        # the last timed step's analysis, read before later steps reuse its pipeline slot (copy_results=False)
+        dump_outputs(args.dump_outputs, {"analysis": out.detach().cpu().numpy()})
     loop_kernel_ms = runner.kernel_ms()      # the dominant kernel's LAUNCHES inside the timed loop (every 4th step opens one)
     spl = runner.kernel_steps_per_launch() if loop_kernel_ms else 1.0      # launch coalescing: steps whose tiles one launch holds
     co_l1, co_s1 = _cabi_stats()
@@ -644,7 +664,7 @@ def main():
         run2(max(50, args.warmup))
         r2.kernel_timings.clear()
         reg = []
-        for _ in range(max(5, repeats // 4)):
+        for _ in range(5):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             o2 = run2(args.steps)
@@ -923,12 +943,6 @@ def main():
         line = {
             "metric": "local analyses/sec (LETKF, 40-member)", "value": value, "unit": "analyses/s",
             "n_gpus": world, "steps": args.steps, "warmup": warm,
-            "repeats": repeats,
-            "repeats_note": ("the timed region of --steps steps was measured %d times back to back (each bracketed by barrier + "
-                             "synchronize); value / ms_per_step are the median region's, spread (min .. max) %.4f .. %.4f ms per step; every region fills "
-                             "and drains the pipeline of steps in flight (1.5-2 step latencies, 0.15-0.2 ms, per region: a 20-step region "
-                             "is 12-15 %% slower per step than the default 2000-step region, profiles/r03_final_bench_steps20.json)"
-                             % (repeats, 1e3 * min(regions) / args.steps, 1e3 * max(regions) / args.steps)) if repeats > 1 else None,
             "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "dtype_detail": ("inputs, outputs, accumulation and every vector operation float32; the matrix products run as "
