@@ -41,6 +41,7 @@ extern "C" {
 #define MIA_ERR_WORKSPACE (-4)   /* workspace too small */
 #define MIA_ERR_ALIGN (-5)       /* pointer not aligned as documented */
 #define MIA_ERR_COMM (-6)        /* RCCL / communicator failure: see mia_comm_last_error() */
+#define MIA_ERR_ARG (-7)         /* invalid argument value (e.g. a negative or non-finite period) */
 
 /* per-grid-point flag bits written to `flags_opt` */
 #define MIA_FLAG_OVERFLOW 1 /* more local observations than p_max: point NOT analysed */
@@ -160,6 +161,21 @@ int mia_letkf_localize_taper_f64(int taper, const double* grid_xyz, int64_t g0, 
 int mia_letkf_index_build_f64(const double* obs_xyz, int64_t P, int n_coord,
                               const int32_t* coord_group /* host */, const double* gc_c /* host */, int n_r,
                               void* ws, size_t ws_bytes /* mia_letkf_localize_workspace_bytes */, void* stream);
+
+/* Cyclic coordinates (PeriodicMetric, no reference counterpart): the same lists / index where coordinate c has period
+ * period[c] > 0 -- coordinates taken modulo period[c], displacement the minimum image d - L round(d / L), radius groups, taper,
+ * eps and sqrt as above; 0 = open (all zero: the entries above).  The period belongs to the cell grid: it is stored in the index
+ * header, and every kernel that scans the index reads it there (cyclic axis: [0, L) in max(1, floor(L / (2 c))) cells, no margin).
+ * period is host memory, [n_coord], finite and >= 0, else MIA_ERR_ARG before any device work.  The fused per-point analysis
+ * (mia_letkf_analysis_matfun_fused_f32) takes open indexes only. */
+int mia_letkf_localize_taper_periodic_f64(int taper, const double* grid_xyz, int64_t g0, int64_t g1,
+                                          const double* obs_xyz, int64_t P, int n_coord,
+                                          const int32_t* coord_group /* host */, const double* period /* host, [n_coord] */,
+                                          const double* gc_c /* host */, int n_r, double gc_eps, int p_cap, int32_t* nbr_cnt, int32_t* nbr_idx, double* nbr_w,
+                                          int32_t* stats, void* ws, size_t ws_bytes, void* stream);
+int mia_letkf_index_build_periodic_f64(const double* obs_xyz, int64_t P, int n_coord,
+                                       const int32_t* coord_group /* host */, const double* period /* host, [n_coord] */,
+                                       const double* gc_c /* host */, int n_r, void* ws, size_t ws_bytes, void* stream);
 
 /* Same lists from caller-evaluated distances (an arbitrary Python dist_func evaluated on
  * the host in batch): dist [n_r][g1-g0][p_cap] f64, cand_idx [g1-g0][p_cap] (-1 = pad).
@@ -302,6 +318,12 @@ int mia_letkf_localize_tiles_f64(int taper, const double* grid_xyz, int64_t g0, 
                                  const int32_t* coord_group /* host */, const double* gc_c /* host */, int n_r,
                                  double gc_eps, int p_max, int extra_blocks, void* tile_lists, size_t tile_lists_bytes,
                                  int32_t* stats, void* ws, size_t ws_bytes, void* stream);
+/* the same on cyclic coordinates (see mia_letkf_localize_taper_periodic_f64) */
+int mia_letkf_localize_tiles_periodic_f64(int taper, const double* grid_xyz, int64_t g0, int64_t g1,
+                                          const double* obs_xyz, int64_t P, int n_coord,
+                                          const int32_t* coord_group /* host */, const double* period /* host, [n_coord] */,
+                                          const double* gc_c /* host */, int n_r, double gc_eps, int p_max, int extra_blocks, void* tile_lists, size_t tile_lists_bytes,
+                                          int32_t* stats, void* ws, size_t ws_bytes, void* stream);
 int mia_letkf_split_record_bytes(int k, size_t* bytes);
 int mia_letkf_pack_split_f32(const float* Yb, const float* d, int k, int64_t P, void* split_rec /* (P + 1) records */,
                              void* stream);
@@ -581,8 +603,20 @@ typedef struct mia_step_args {
   void* stream; void* comm_stream; void* prep_stream; int32_t step_flags; int32_t* host8; void* after_stream; void* on_stream;
   void** done_event; void* time_start_event; void* time_stop_event;
   void* caller_stream; void** in_event;
+  /* cyclic coordinates (PeriodicMetric): period[c] > 0 = coordinate c is taken modulo period[c], the distance is the minimum image;
+   * 0 = open (every entry 0: the step as without this field).  Finite and >= 0, else MIA_ERR_ARG.  Part of the workspace's
+   * geometry: a change of period rebuilds the cell grid and the lists. */
+  double period[MIA_MAX_COORD];
 } mia_step_args_t;
 int mia_letkf_step_submit_args(const mia_step_args_t* a, void** job_out);
+/* mia_letkf_sharded_step_streams_f32 on cyclic coordinates: period (host, [n_coord], see mia_letkf_localize_taper_periodic_f64)
+ * follows coord_group; every index the step builds -- bucket index, scan index, the redo of declined points -- takes it. */
+int mia_letkf_sharded_step_periodic_f32(const float* X, int64_t G, int m, int k, const float* Yb, const float* d, int64_t P,
+                                        const double* grid_xyz, const double* obs_xyz, int n_coord, const int32_t* coord_group,
+                                        const double* period, const double* gc_c, int n_r, double gc_eps, float inf_factor,
+                                        float gamma, int method, int p_max_assumed, mia_comm_t* comm, int n_chunks, int phase,
+                                        float* Xa, int32_t* flags, int32_t* counters, void* ws, size_t ws_bytes, void* stream,
+                                        void* comm_stream, void* prep_stream, int step_flags);
 /* One step taken at once on the caller's thread through the same block (MIA_STEP_NO_JOIN is ignored): drain of the launch threads,
  * the step call, the counters' read-back (after_stream / on_stream / done_event as in mia_letkf_step_readback) and, when out8 is
  * given, the host's wait for it and the eight counters -- the whole of a cycled filter's step in one call (a Python caller's

@@ -11,6 +11,7 @@ __version__ = "0.1.0"
 _LAZY = {
     "LetkfEngine": "engine", "NeighbourLists": "engine",
     "GaspariCohn": "localization", "EuclideanMetric": "localization", "AbsoluteDistance": "localization",
+    "PeriodicMetric": "localization",
     "ETKFModule": "core", "KETKFModule": "core",
     "LETKF": "interface", "ETKF": "interface", "LKETKF": "interface", "KETKF": "interface",
     "GaspariCohnInf": "localization",

@@ -57,6 +57,13 @@ _PROTOS = {
     "mia_letkf_weights_retry_f32": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f32, f32,
                                      vp, i64, i64, vp, vp, vp], i32),
     "mia_letkf_index_build_f64": ([vp, i64, i32, C.POINTER(C.c_int32), C.POINTER(f64), i32, vp, sz, vp], i32),
+    # cyclic coordinates (PeriodicMetric): the period, host [n_coord], follows coord_group / gc_c / n_r
+    "mia_letkf_index_build_periodic_f64": ([vp, i64, i32, C.POINTER(C.c_int32), C.POINTER(f64), C.POINTER(f64), i32, vp, sz, vp],
+                                           i32),
+    "mia_letkf_localize_taper_periodic_f64": ([i32, vp, i64, i64, vp, i64, i32, C.POINTER(C.c_int32), C.POINTER(f64),
+                                               C.POINTER(f64), i32, f64, i32, vp, vp, vp, vp, vp, sz, vp], i32),
+    "mia_letkf_localize_tiles_periodic_f64": ([i32, vp, i64, i64, vp, i64, i32, C.POINTER(C.c_int32), C.POINTER(f64),
+                                               C.POINTER(f64), i32, f64, i32, i32, vp, sz, vp, vp, sz, vp], i32),
     "mia_letkf_analysis_matfun_fused_f32": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, i32, C.POINTER(C.c_int32),
                                              C.POINTER(f64), i32, f64, vp, sz, i32, f32, f32, vp, i64, i64, vp, vp, vp,
                                              vp], i32),
@@ -139,6 +146,9 @@ _PROTOS = {
     "mia_letkf_sharded_step_streams_f32": ([vp, i64, i32, i32, vp, vp, i64, vp, vp, i32, C.POINTER(C.c_int32),
                                             C.POINTER(f64), i32, f64, f32, f32, i32, i32, vp, i32, i32, vp, vp, vp, vp,
                                             sz, vp, vp, vp, i32], i32),
+    "mia_letkf_sharded_step_periodic_f32": ([vp, i64, i32, i32, vp, vp, i64, vp, vp, i32, C.POINTER(C.c_int32), C.POINTER(f64),
+                                             C.POINTER(f64), i32, f64, f32, f32, i32, i32, vp, i32, i32, vp, vp, vp, vp,
+                                             sz, vp, vp, vp, i32], i32),
 }
 EXPORTED_SYMBOLS = tuple(_PROTOS)
 # callbacks of mia_comm_create_custom
@@ -189,7 +199,7 @@ class StepArgs(C.Structure):
                 ("comm_stream", C.c_void_p), ("prep_stream", C.c_void_p), ("step_flags", C.c_int32), ("host8", C.c_void_p),
                 ("after_stream", C.c_void_p), ("on_stream", C.c_void_p), ("done_event", C.POINTER(C.c_void_p)),
                 ("time_start_event", C.c_void_p), ("time_stop_event", C.c_void_p), ("caller_stream", C.c_void_p),
-                ("in_event", C.POINTER(C.c_void_p))]
+                ("in_event", C.POINTER(C.c_void_p)), ("period", C.c_double * 3)]
 
 
 class TimingEvent:

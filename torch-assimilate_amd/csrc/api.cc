@@ -12,6 +12,7 @@ extern "C" const char* mia_status_string(int status) {
     case MIA_ERR_WORKSPACE: return "workspace too small (use the *_workspace_bytes query)";
     case MIA_ERR_ALIGN: return "workspace pointer must be 256-byte aligned";
     case MIA_ERR_COMM: return "RCCL / communicator failure (mia_comm_last_error has the detail)";
+    case MIA_ERR_ARG: return "invalid argument value (e.g. a negative or non-finite period)";
     default: return status > 0 ? "HIP runtime error (value is the hipError_t)" : "unknown status";
   }
 }

@@ -41,7 +41,8 @@ namespace mia {
 // the same shape, two wavefronts per SIMD); the loop launders the lane-derived indices at its top, so that work stays inside
 // the row: 100 registers, four wavefronts per SIMD, 0.0196 instead of 0.0211 ms per row and 1e5 points.
 //
-// LOC = 0: lists from memory (localize_tiles_kernel ran before).  LOC = 1, 2, 3 (the number of coordinates): the wavefront
+// LOC = 0: lists from memory (localize_tiles_kernel ran before).  LOC = 1, 2, 3 (the number of coordinates; + 4 on an index with
+// cyclic coordinates, tile_localize's PERIODIC instantiation): the wavefront
 // LOCALISES ITS TILE ITSELF over the step's bucket index (tile_localize, mia_tile_localize.h -- the same code and therefore the same
 // union, ranks and sqrt(rho) as the list kernel's) before anything else; its scratch shares the LDS of the record image, which is
 // filled afterwards.  No tile list is written or read, one launch and one memory round trip less per step.
@@ -119,7 +120,7 @@ __device__ __forceinline__ void tile2_body(Tile2Params P, const Tile2Loc* loc, c
     for (int t = 0; t < UT; ++t) dreg[t] = t2_ld<f4w>(P.tD + (tile * UT + t) * 64, (unsigned)lane * 16u);
   } else {
     // the tile's lists, formed here: union members / slot table / sqrt(rho) in LDS scratch -> this lane's slots and D fragments
-    const TileLocOut lo = tile_localize<true, LOC, MIA_TAPER_GC>(loc->scan, P.g0, P.ng, UT, tile, smem, lane);
+    const TileLocOut lo = tile_localize<true, (LOC > 3 ? LOC - 4 : LOC), MIA_TAPER_GC, (LOC > 3)>(loc->scan, P.g0, P.ng, UT, tile, smem, lane);
     const TileLocLds LL(smem);
     hdU = lo.overflow ? -1 : lo.U;
     // (two rounds of independent LDS reads, one wait each: slot -> member, then the member's key / weights -- an unused slot reads

@@ -1,4 +1,5 @@
-// Fused localisation + LETKF analysis: letkf_tile2_kernel's body (letkf_tile2_kernel.h) with LOC = number of coordinates -- every
+// Fused localisation + LETKF analysis: letkf_tile2_kernel's body (letkf_tile2_kernel.h) with LOC = number of coordinates (+ 4 on an
+// index with cyclic coordinates: NC below is that LOC; such steps are launched on their own, never coalesced) -- every
 // wavefront first localises its own tile of sixteen grid points over the step's bucket index (tile_localize, the list kernel's
 // code: same union, same ranks, same sqrt(rho), so the analysis is bit for bit the one from lists in memory), then analyses it.
 // Reference: GaspariCohn.localize_obs (pytassim/localization/gaspari_cohn.py:97-136) + wrapper_localization
@@ -75,7 +76,7 @@ static int tile2f_launch_m(const Tile2FParams& pf, hipStream_t stream) {
   if (Tile2fCollector* c = t_collect) {
     // collected, not launched: the same instantiation and ensemble size as what the collector holds, room left, a grid that fits
     const int64_t nt = (pf.t.ng + 15) >> 4;
-    const bool fits = !MROWS && c->n < kT2fBatchMax && nt < ((int64_t)1 << 24) &&      // (one state row: the instantiations that exist)
+    const bool fits = !MROWS && NC <= 3 && c->n < kT2fBatchMax && nt < ((int64_t)1 << 24) &&      // (one state row: the instantiations that exist)
                       (c->n == 0 || (c->ut == UT && c->kt == KT && c->nc == NC && c->mrows == MROWS && c->k == pf.t.k));
     if (fits) {
       c->ut = UT; c->kt = KT; c->nc = NC; c->mrows = MROWS; c->k = pf.t.k;
@@ -115,10 +116,13 @@ static int tile2f_launch_n(const Tile2FParams& pf, hipStream_t stream) {        
 
 template <int UT, int KT>
 static int tile2f_launch_k(const Tile2FParams& pf, hipStream_t stream) {
-  switch (pf.loc.scan.nc) {
+  switch (pf.loc.scan.nc + (pf.loc.periodic ? 4 : 0)) {
     case 1: return tile2f_launch_n<UT, KT, 1>(pf, stream);
     case 2: return tile2f_launch_n<UT, KT, 2>(pf, stream);
     case 3: return tile2f_launch_n<UT, KT, 3>(pf, stream);
+    case 5: return tile2f_launch_n<UT, KT, 5>(pf, stream);
+    case 6: return tile2f_launch_n<UT, KT, 6>(pf, stream);
+    case 7: return tile2f_launch_n<UT, KT, 7>(pf, stream);
   }
   return MIA_ERR_UNSUPPORTED;
 }

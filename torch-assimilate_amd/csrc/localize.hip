@@ -41,6 +41,8 @@ struct IndexParams {
   PackJob pack;          // ... the others (if any) pack observation records (pack.rec != nullptr)
   ZeroJob zero;          // small caller buffers cleared by the first kernel (saves their fill launches)
   int scatter_xyz;       // the cell sort is skipped (see index_build_impl): the scatter lays the coordinates out itself
+  double period[MIA_MAX_COORD];  // > 0: cyclic coordinate (IndexHeader::period); all zero: every coordinate open
+  int periodic;                  // some period is > 0: the binning kernels' PER instantiations (they reduce the coordinates)
   long long bucket_total;   // entries of the bucket arrays
   int* bidx; double* bxyz;
   unsigned nb_main;         // index_bucket_kernel: workgroups nb_main, nb_main + 1, ... pack split records (independent passenger)
@@ -72,6 +74,16 @@ __device__ inline void index_dims(const IndexParams& p) {
     __hip_atomic_store(&p.hdr->kmax[c], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(&p.hdr->kmin_inv[c], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     h[c] = p.cutoff[c] > 0.0 ? p.cutoff[c] : 1.0;
+    if (p.period[c] > 0.0) {       // cyclic: [0, L) in floor(L / cutoff) cells (at least one), no margin, no bounding box
+      const double L = p.period[c];
+      double nn = floor(L / h[c]);
+      nn = nn < 1.0 ? 1.0 : (nn > 1048576.0 ? 1048576.0 : nn);
+      if (nn > 1.0 && L / nn < h[c]) nn -= 1.0;        // (every edge at least the cutoff, also after rounding)
+      p.hdr->mn[c] = 0.0;
+      ext[c] = L;
+      n[c] = (long long)nn;
+      continue;
+    }
     // (one cell of margin on either side: observations that drift a little between two builds stay inside a box that the
     //  bucket index of the step driver keeps from one step to the next)
     mn -= h[c]; mx += h[c];
@@ -87,7 +99,16 @@ __device__ inline void index_dims(const IndexParams& p) {
     for (int c = 1; c < p.nc; ++c) if (n[c] > n[big]) big = c;
     n[big] = (n[big] + 1) / 2;
   }
+  for (int c = 0; c < MIA_MAX_COORD; ++c) {
+    p.hdr->period[c] = c < p.nc && p.period[c] > 0.0 ? p.period[c] : 0.0;
+    p.hdr->inv_period[c] = c < p.nc && p.period[c] > 0.0 ? 1.0 / p.period[c] : 0.0;
+  }
   for (int c = 0; c < p.nc; ++c) {
+    if (p.period[c] > 0.0) {       // (edge L / n >= cutoff: the halving above only made the cells larger)
+      p.hdr->invh[c] = double(n[c]) / p.period[c];
+      p.hdr->n[c] = int(n[c]);
+      continue;
+    }
     double hc = ext[c] / double(n[c]);
     if (hc < h[c]) hc = h[c]; else hc *= (1.0 + 1e-12);
     p.hdr->invh[c] = 1.0 / hc;
@@ -146,10 +167,21 @@ __global__ __launch_bounds__(256) void index_bbox_dims_kernel(IndexParams p) {
   }
 }
 
-__device__ inline int obs_cell(const IndexHeader* h, const double* x, int nc) {
+// an observation's coordinate as the index stores it: reduced to [0, L) on a cyclic coordinate (PER: the index has some)
+template <bool PER>
+__device__ inline double obs_coord(const IndexParams& p, const double* x, int c) {
+  if constexpr (PER) return p.period[c] > 0.0 ? wrap_coord(x[c], p.period[c]) : x[c];
+  return x[c];
+}
+
+template <bool PER>
+__device__ inline int obs_cell(const IndexParams& p, const IndexHeader* h, const double* x, int nc) {
   int id = 0;
   for (int c = 0; c < nc; ++c) {
-    int cc = cell_coord(x[c], h->mn[c], h->invh[c], h->n[c]);
+    int cc;
+    if constexpr (PER) cc = p.period[c] > 0.0 ? cell_coord_cyc(wrap_coord(x[c], p.period[c]), h->invh[c], h->n[c])
+                                              : cell_coord(x[c], h->mn[c], h->invh[c], h->n[c]);
+    else cc = cell_coord(x[c], h->mn[c], h->invh[c], h->n[c]);
     cc = cc < 0 ? 0 : (cc > h->n[c] - 1 ? h->n[c] - 1 : cc);
     id = id * h->n[c] + cc;
   }
@@ -199,16 +231,18 @@ __global__ __launch_bounds__(64) void index_clear_kernel(uint32_t* p, size_t n) 
 
 // cell of every observation + per-cell counts.  256-thread workgroups of 15 VGPRs: they fit beside the analysis
 // kernel's waves (see index_scan_kernel).
+template <bool PER>
 __global__ __launch_bounds__(64) void index_count_kernel(IndexParams p) {
   MIA_PREP_PRIORITY();
   const int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   if (j < p.P) {
-    const int c = obs_cell(p.hdr, p.obs + j * p.nc, p.nc);
+    const int c = obs_cell<PER>(p, p.hdr, p.obs + j * p.nc, p.nc);
     p.cell_of[j] = c;
     p.rank_of[j] = atomicAdd(&p.cursor[c], 1);      // (the count IS the observation's place inside its cell: no second atomic)
   }
 }
 
+template <bool PER>
 __global__ void index_scatter_kernel(IndexParams p) {
   MIA_PREP_PRIORITY();
   int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
@@ -217,7 +251,7 @@ __global__ void index_scatter_kernel(IndexParams p) {
   int pos = p.start[c] + p.rank_of[j];
   p.sorted[pos] = int(j);
   if (p.scatter_xyz)
-    for (int q = 0; q < p.nc; ++q) p.sxyz[(int64_t)pos * p.nc + q] = p.obs[j * p.nc + q];
+    for (int q = 0; q < p.nc; ++q) p.sxyz[(int64_t)pos * p.nc + q] = obs_coord<PER>(p, p.obs + j * p.nc, q);
 }
 
 // Lists built on an index whose cells were NOT sorted (lazy sort of the step driver) hold the right observations in
@@ -265,6 +299,7 @@ __global__ __launch_bounds__(64) void sort_flagged_lists_kernel(SortListsParams 
 // coordinates out in that order.  One WAVE per cell (grid-stride over the cells): a cell of up to 64
 // observations is ranked in registers (ids are distinct: rank = number of smaller ids) with one load and one
 // store per lane; the thread-per-cell insertion sort this replaces spent 16 us in dependent global round trips.
+template <bool PER>
 __global__ __launch_bounds__(256) void index_sortcell_kernel(IndexParams p) {
   MIA_PREP_PRIORITY();
   const int lane = threadIdx.x & 63;
@@ -279,7 +314,7 @@ __global__ __launch_bounds__(256) void index_sortcell_kernel(IndexParams p) {
       for (int l = 0; l < n; ++l) rank += __shfl(v, l, 64) < v ? 1 : 0;
       if (lane < n) {
         p.sorted[lo + rank] = v;
-        for (int q = 0; q < p.nc; ++q) p.sxyz[(int64_t)(lo + rank) * p.nc + q] = p.obs[(int64_t)v * p.nc + q];
+        for (int q = 0; q < p.nc; ++q) p.sxyz[(int64_t)(lo + rank) * p.nc + q] = obs_coord<PER>(p, p.obs + (int64_t)v * p.nc, q);
       }
     } else {
       // larger cells (dense networks: hundreds of observations per cell): the same rank sort out of place -- ids copied to
@@ -295,7 +330,7 @@ __global__ __launch_bounds__(256) void index_sortcell_kernel(IndexParams p) {
         int rank = 0;
         for (int l = 0; l < n; ++l) rank += tmp[l] < v ? 1 : 0;
         p.sorted[lo + rank] = v;
-        for (int q = 0; q < p.nc; ++q) p.sxyz[(int64_t)(lo + rank) * p.nc + q] = p.obs[(int64_t)v * p.nc + q];
+        for (int q = 0; q < p.nc; ++q) p.sxyz[(int64_t)(lo + rank) * p.nc + q] = obs_coord<PER>(p, p.obs + (int64_t)v * p.nc, q);
       }
     }
   }
@@ -329,6 +364,8 @@ struct LocalizeParams {
 // (~30 candidates x ~50 float64 operations) runs with all lanes busy.
 // (106 VGPRs.  Capping it at 80, so that ONE retiring wave of a co-running analysis kernel -- 7 x 72 registers per
 //  SIMD -- makes room, cost 24 spilled registers and gained nothing: 68 us beside the analysis kernel either way)
+// PER: the index has cyclic coordinates (cyc_window_seg / cyc_disp); the open instantiation is the kernel as it was.
+template <bool PER>
 __global__ __launch_bounds__(64) void localize_kernel(LocalizeParams p) {
   MIA_PREP_PRIORITY();
   MIA_LOCALIZE_PASSENGER(p);
@@ -343,7 +380,8 @@ __global__ __launch_bounds__(64) void localize_kernel(LocalizeParams p) {
     for (int c = 0; c < MIA_MAX_COORD; ++c) { gx[c] = 0.0; cg[c] = 0; }
     for (int c = 0; c < nc; ++c) {
       gx[c] = q.grid[(p.g0 + pt) * nc + c];
-      cg[c] = cell_coord(gx[c], h->mn[c], h->invh[c], h->n[c]);
+      if constexpr (PER) point_cell(h, c, gx[c], &gx[c], &cg[c]);
+      else cg[c] = cell_coord(gx[c], h->mn[c], h->invh[c], h->n[c]);
     }
     int* my_idx = p.idx + pt * p.p_cap;
     double* my_w = p.w + pt * p.p_cap;
@@ -352,7 +390,13 @@ __global__ __launch_bounds__(64) void localize_kernel(LocalizeParams p) {
     int lo_l = cg[last] - 1, hi_l = cg[last] + 1;
     lo_l = lo_l < 0 ? 0 : lo_l;
     hi_l = hi_l > h->n[last] - 1 ? h->n[last] - 1 : hi_l;
-    for (int o = 0; o < n_outer; ++o) {
+    for (int o = 0; o < n_outer * (PER ? 2 : 1); ++o) {
+      int beg, end;
+      CycSeg sg;
+      if constexpr (PER) {
+        if (!cyc_window_seg(h, nc, cg, o >> 1, o & 1, sg)) continue;
+        beg = q.start[sg.c_lo]; end = q.start[sg.c_hi + 1];
+      } else {
       int base_cell = 0;
       bool ok = lo_l <= hi_l;
       if (nc >= 2) {
@@ -368,7 +412,8 @@ __global__ __launch_bounds__(64) void localize_kernel(LocalizeParams p) {
         base_cell *= h->n[last];
       }
       if (!ok) continue;
-      const int beg = q.start[base_cell + lo_l], end = q.start[base_cell + hi_l + 1];
+      beg = q.start[base_cell + lo_l]; end = q.start[base_cell + hi_l + 1];
+      }
       // four candidates per trip: their (independent) loads are issued together, so the ~1.5 us memory
       // latency is paid once per four candidates instead of once per candidate
       for (int pos0 = beg; pos0 < end; pos0 += 4) {
@@ -380,7 +425,9 @@ __global__ __launch_bounds__(64) void localize_kernel(LocalizeParams p) {
           oj[u] = q.sorted[pos];
           double d2[MIA_MAX_RADII] = {0.0, 0.0, 0.0};
           for (int c = 0; c < nc; ++c) {
-            const double dx = q.sxyz[(int64_t)pos * nc + c] - gx[c];
+            double dx;
+            if constexpr (PER) dx = cyc_disp(q.sxyz[(int64_t)pos * nc + c], gx[c], sg.s[c], (sg.pw >> c) & 1u, h->period[c], h->inv_period[c]);
+            else dx = q.sxyz[(int64_t)pos * nc + c] - gx[c];
             d2[q.group[c]] += dx * dx;
           }
           double wgt = 1.0;
@@ -414,6 +461,7 @@ __global__ __launch_bounds__(64) void localize_kernel(LocalizeParams p) {
 // times as many wavefronts, each a quarter as long and half the registers: alone on the GPU the thread-per-point kernel
 // runs at 1.5 waves per SIMD (1563 waves for 1e5 points) and is all latency; beside the analysis kernel of an earlier step
 // (pipelined steps) its long-lived 106-register waves each kept a 168-register analysis wave out of its SIMD.
+template <bool PER>
 __global__ __launch_bounds__(64) void localize_quad_kernel(LocalizeParams p) {
   MIA_PREP_PRIORITY();
   MIA_LOCALIZE_PASSENGER(p);
@@ -430,7 +478,8 @@ __global__ __launch_bounds__(64) void localize_quad_kernel(LocalizeParams p) {
     for (int c = 0; c < MIA_MAX_COORD; ++c) { gx[c] = 0.0; cg[c] = 0; }
     for (int c = 0; c < nc; ++c) {
       gx[c] = q.grid[(p.g0 + pt) * nc + c];
-      cg[c] = cell_coord(gx[c], h->mn[c], h->invh[c], h->n[c]);
+      if constexpr (PER) point_cell(h, c, gx[c], &gx[c], &cg[c]);
+      else cg[c] = cell_coord(gx[c], h->mn[c], h->invh[c], h->n[c]);
     }
     int* my_idx = p.idx + pt * p.p_cap;
     double* my_w = p.w + pt * p.p_cap;
@@ -439,7 +488,13 @@ __global__ __launch_bounds__(64) void localize_quad_kernel(LocalizeParams p) {
     int lo_l = cg[last] - 1, hi_l = cg[last] + 1;
     lo_l = lo_l < 0 ? 0 : lo_l;
     hi_l = hi_l > h->n[last] - 1 ? h->n[last] - 1 : hi_l;
-    for (int o = 0; o < n_outer; ++o) {
+    for (int o = 0; o < n_outer * (PER ? 2 : 1); ++o) {
+      int beg, end;
+      CycSeg sg;
+      if constexpr (PER) {
+        if (!cyc_window_seg(h, nc, cg, o >> 1, o & 1, sg)) continue;
+        beg = q.start[sg.c_lo]; end = q.start[sg.c_hi + 1];
+      } else {
       int base_cell = 0;
       bool ok = lo_l <= hi_l;
       if (nc >= 2) {
@@ -455,7 +510,8 @@ __global__ __launch_bounds__(64) void localize_quad_kernel(LocalizeParams p) {
         base_cell *= h->n[last];
       }
       if (!ok) continue;
-      const int beg = q.start[base_cell + lo_l], end = q.start[base_cell + hi_l + 1];
+      beg = q.start[base_cell + lo_l]; end = q.start[base_cell + hi_l + 1];
+      }
       // two candidates per lane and trip (positions pos0 + sub and pos0 + 4 + sub: their loads are requested together,
       // half as many dependent memory round trips per point); the survivors of the first four positions are placed
       // before those of the second four, i.e. still in position order
@@ -470,7 +526,9 @@ __global__ __launch_bounds__(64) void localize_quad_kernel(LocalizeParams p) {
           oj[u] = q.sorted[pos];
           double d2[MIA_MAX_RADII] = {0.0, 0.0, 0.0};
           for (int c = 0; c < nc; ++c) {
-            const double dx = q.sxyz[(int64_t)pos * nc + c] - gx[c];
+            double dx;
+            if constexpr (PER) dx = cyc_disp(q.sxyz[(int64_t)pos * nc + c], gx[c], sg.s[c], (sg.pw >> c) & 1u, h->period[c], h->inv_period[c]);
+            else dx = q.sxyz[(int64_t)pos * nc + c] - gx[c];
             d2[q.group[c]] += dx * dx;
           }
           wgt[u] = 1.0;
@@ -504,6 +562,7 @@ __global__ __launch_bounds__(64) void localize_quad_kernel(LocalizeParams p) {
 // list of several hundred candidates serially in every lane (p ~ 1000: 13 ms for 2e4 points, 20x the analysis itself);
 // here 64 candidates are evaluated per trip and compacted with a ballot (scan_neighbours, the routine the fused
 // analysis route uses).  Same order (cell order, ascending index inside a cell), same weights: identical lists.
+template <bool PER>
 __global__ __launch_bounds__(64) void localize_wave_kernel(LocalizeParams p) {
   MIA_PREP_PRIORITY();
   MIA_LOCALIZE_PASSENGER(p);
@@ -512,7 +571,9 @@ __global__ __launch_bounds__(64) void localize_wave_kernel(LocalizeParams p) {
   if (pt >= p.ng) return;
   int* my_idx = p.idx + pt * p.p_cap;
   double* my_w = p.w + pt * p.p_cap;
-  const int count = scan_neighbours<double>(p.scan, p.g0 + pt, lane, p.p_cap, my_idx, my_w);
+  int count;
+  if constexpr (PER) count = scan_neighbours_cyc<double>(p.scan, p.g0 + pt, lane, p.p_cap, my_idx, my_w);
+  else count = scan_neighbours<double>(p.scan, p.g0 + pt, lane, p.p_cap, my_idx, my_w);
   for (int s_ = (count < p.p_cap ? count : p.p_cap) + lane; s_ < p.p_cap; s_ += 64) { my_idx[s_] = -1; my_w[s_] = 0.0; }
   if (lane == 0) {
     p.cnt[pt] = count;
@@ -585,15 +646,27 @@ static int taper_launch(const T* r, int64_t n, T* w, hipStream_t stream) {
   return MIA_OK;
 }
 
+int check_period(const double* period, int n_coord, bool* cyclic) {
+  *cyclic = false;
+  if (!period) return MIA_OK;
+  for (int c = 0; c < n_coord; ++c) {
+    if (!(period[c] >= 0.0) || !(period[c] < __builtin_inf())) return MIA_ERR_ARG;      // (NaN, negative, infinite)
+    *cyclic = *cyclic || period[c] > 0.0;
+  }
+  return MIA_OK;
+}
+
 // builds the cell index of the observations in ws (all kernels enqueued on stream)
 int index_build_impl(const double* obs_xyz, int64_t P, int n_coord, const int32_t* coord_group,
                      const double* gc_c, int n_r, void* ws, size_t ws_bytes, hipStream_t stream, const PackJob* pack,
-                     const ZeroJob* zero, bool header_clean, bool sort_cells) {
+                     const ZeroJob* zero, bool header_clean, bool sort_cells, const double* period) {
   if (P < 0 || n_coord < 1 || n_coord > MIA_MAX_COORD || n_r < 1 || n_r > MIA_MAX_RADII) return MIA_ERR_SIZE;
   if (P > 2000000000LL) return MIA_ERR_UNSUPPORTED;
   if (!coord_group || !gc_c) return MIA_ERR_NULL;
   for (int c = 0; c < n_coord; ++c) if (coord_group[c] < 0 || coord_group[c] >= n_r) return MIA_ERR_SIZE;
   for (int r = 0; r < n_r; ++r) if (!(gc_c[r] > 0.0)) return MIA_ERR_SIZE;
+  bool cyclic = false;
+  if (check_period(period, n_coord, &cyclic) != MIA_OK) return MIA_ERR_ARG;
   if (P == 0) return MIA_OK;
   if (!obs_xyz || !ws) return MIA_ERR_NULL;
   if (((uintptr_t)ws) & 255) return MIA_ERR_ALIGN;
@@ -605,6 +678,8 @@ int index_build_impl(const double* obs_xyz, int64_t P, int n_coord, const int32_
   ip.hdr = L.hdr; ip.start = L.start; ip.cursor = L.cursor; ip.sorted = L.sorted; ip.cell_of = L.cell_of; ip.rank_of = L.rank_of;
   ip.sxyz = L.sxyz;
   ip.bucket_total = (long long)L.bucket_total; ip.bidx = L.bidx; ip.bxyz = L.bxyz;
+  for (int c = 0; c < MIA_MAX_COORD; ++c) ip.period[c] = (cyclic && c < n_coord) ? period[c] : 0.0;
+  ip.periodic = cyclic ? 1 : 0;
   // SINGLE-WAVE workgroups throughout the chain: when steps are pipelined these kernels run beside the previous step's
   // analysis kernel, which fills every SIMD's register file (7 waves x 72 VGPRs at C2).  A lone wave takes the slot of
   // the next analysis wave that retires; a 4-wave workgroup needs one to retire on each SIMD of one CU at the same
@@ -636,16 +711,19 @@ int index_build_impl(const double* obs_xyz, int64_t P, int n_coord, const int32_
   const size_t pack_lds = nb_pack ? (size_t)64 * (ip.pack.kp + 1) * sizeof(float) : 0;      // (kp <= 132: 34 KB)
   index_bbox_dims_kernel<<<dim3(ip.nb_bbox + nb_pack), dim3(kPrepThreads), pack_lds, stream>>>(ip);
   MIA_LAUNCH_CHECK();
-  index_count_kernel<<<dim3(nbP), dim3(kPrepThreads), 0, stream>>>(ip);
+  if (cyclic) index_count_kernel<true><<<dim3(nbP), dim3(kPrepThreads), 0, stream>>>(ip);
+  else index_count_kernel<false><<<dim3(nbP), dim3(kPrepThreads), 0, stream>>>(ip);
   MIA_LAUNCH_CHECK();
   index_scan_kernel<<<dim3(1), dim3(64), 0, stream>>>(ip);
   MIA_LAUNCH_CHECK();
   ip.scatter_xyz = sort_cells ? 0 : 1;
-  index_scatter_kernel<<<dim3(nbP), dim3(kPrepThreads), 0, stream>>>(ip);
+  if (cyclic) index_scatter_kernel<true><<<dim3(nbP), dim3(kPrepThreads), 0, stream>>>(ip);
+  else index_scatter_kernel<false><<<dim3(nbP), dim3(kPrepThreads), 0, stream>>>(ip);
   MIA_LAUNCH_CHECK();
   if (!sort_cells) return MIA_OK;      // (lazy sort: the scatter has laid the coordinates out; see sort_flagged_lists_kernel)
   const size_t sort_blocks = L.cap < 8192 ? (L.cap ? L.cap : 1) : 8192;      // one wave (cell) per workgroup
-  index_sortcell_kernel<<<dim3((unsigned)sort_blocks), dim3(kPrepThreads), 0, stream>>>(ip);
+  if (cyclic) index_sortcell_kernel<true><<<dim3((unsigned)sort_blocks), dim3(kPrepThreads), 0, stream>>>(ip);
+  else index_sortcell_kernel<false><<<dim3((unsigned)sort_blocks), dim3(kPrepThreads), 0, stream>>>(ip);
   MIA_LAUNCH_CHECK();
   return MIA_OK;
 }
@@ -658,6 +736,7 @@ int index_build_impl(const double* obs_xyz, int64_t P, int n_coord, const int32_
 // radii against the ones the grid was derived for): kIndexErrBox sends the step back through the bounding-box kernel,
 // kIndexErrFull (a cell with more observations than a bucket holds) to the scan-based index.  The per-cell counts are zero on
 // entry: the tile-list kernel's last workgroup puts them back (localize_tiles_kernel).
+template <bool PER>
 __global__ __launch_bounds__(64) void index_bucket_kernel(IndexParams p) {
   MIA_PREP_PRIORITY();
   MIA_PREP_PRIORITY();
@@ -679,13 +758,24 @@ __global__ __launch_bounds__(64) void index_bucket_kernel(IndexParams p) {
     const bool grid_ok = h->magic == kIndexMagic;
     bool ok = grid_ok && h->bucket_cap > 0;
     for (int c = 0; c < p.nc; ++c) ok = ok && h->cutoff[c] == p.cutoff[c];
+    // (a grid made for another period counts as a changed box.  An open step does not look: a cyclic grid that holds all its
+    //  observations is a valid open one -- no open kernel reads the period -- and a cyclic step after it finds period 0 and rebuilds)
+    if constexpr (PER)
+      for (int c = 0; c < p.nc; ++c) ok = ok && h->period[c] == p.period[c];
     const int cap = h->bucket_cap;
     int id = 0;
     bool skip = false;
     double x[MIA_MAX_COORD] = {0.0, 0.0, 0.0};
     for (int c = 0; c < p.nc; ++c) {
       x[c] = p.obs[j * p.nc + c];
-      const double f = floor((x[c] - h->mn[c]) * h->invh[c]);
+      double f;
+      if (PER && p.period[c] > 0.0) {
+        x[c] = wrap_coord(x[c], p.period[c]);
+        f = floor(x[c] * h->invh[c]);
+        f = f > double(h->n[c] - 1) ? double(h->n[c] - 1) : f;
+      } else {
+        f = floor((x[c] - h->mn[c]) * h->invh[c]);
+      }
       if (!(x[c] == x[c])) { skip = true; continue; }         // NaN coordinate: no cell (its weight is 0 everywhere)
       if (!(f >= 0.0 && f < double(h->n[c]))) { ok = false; continue; }
       id = id * h->n[c] + int(f);
@@ -708,13 +798,17 @@ __global__ __launch_bounds__(64) void index_bucket_kernel(IndexParams p) {
 
 int index_bucket_build_impl(const double* obs_xyz, int64_t P, int n_coord, const int32_t* coord_group, const double* gc_c, int n_r,
                             void* ws, size_t ws_bytes, hipStream_t stream, const ZeroJob* zero, bool fresh_box,
-                            const SplitPackJob* spack, int* counts) {
+                            const SplitPackJob* spack, int* counts, const double* period) {
   if (P <= 0 || n_coord < 1 || n_coord > MIA_MAX_COORD || n_r < 1 || n_r > MIA_MAX_RADII) return MIA_ERR_SIZE;
   if (P > 500000000LL) return MIA_ERR_UNSUPPORTED;
   if (!coord_group || !gc_c || !obs_xyz || !ws) return MIA_ERR_NULL;
+  bool cyclic = false;
+  if (check_period(period, n_coord, &cyclic) != MIA_OK) return MIA_ERR_ARG;
   const IndexLayout L = index_layout(ws, P, n_coord);
   if (ws_bytes < L.bytes) return MIA_ERR_WORKSPACE;
   IndexParams ip;
+  for (int c = 0; c < MIA_MAX_COORD; ++c) ip.period[c] = (cyclic && c < n_coord) ? period[c] : 0.0;
+  ip.periodic = cyclic ? 1 : 0;
   ip.obs = obs_xyz; ip.P = P; ip.nc = n_coord; ip.cell_cap = (int)L.cap;
   for (int c = 0; c < MIA_MAX_COORD; ++c) ip.cutoff[c] = c < n_coord ? 2.0 * gc_c[coord_group[c]] : 1.0;
   ip.hdr = L.hdr; ip.start = L.start; ip.cursor = L.cursor; ip.sorted = L.sorted; ip.cell_of = L.cell_of; ip.rank_of = L.rank_of;
@@ -746,9 +840,13 @@ int index_bucket_build_impl(const double* obs_xyz, int64_t P, int n_coord, const
     nb = (unsigned)((P + 1 + 63) / 64);      // (record P is the all-zero record)
     lds = split_pack_lean_lds(spack->k);
     if (lds > kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
-    if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)index_bucket_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (lds > 48 * 1024) {
+      MIA_HIP_TRY(hipFuncSetAttribute((const void*)index_bucket_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      MIA_HIP_TRY(hipFuncSetAttribute((const void*)index_bucket_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
   }
-  index_bucket_kernel<<<dim3(nb), dim3(kPrepThreads), lds, stream>>>(ip);
+  if (cyclic) index_bucket_kernel<true><<<dim3(nb), dim3(kPrepThreads), lds, stream>>>(ip);
+  else index_bucket_kernel<false><<<dim3(nb), dim3(kPrepThreads), lds, stream>>>(ip);
   MIA_LAUNCH_CHECK();
   return MIA_OK;
 }
@@ -779,12 +877,14 @@ int localize_impl(const double* grid_xyz, int64_t g0, int64_t g1, const double* 
                   const int32_t* coord_group, const double* gc_c, int n_r, double gc_eps, int p_cap,
                   int32_t* nbr_cnt, int32_t* nbr_idx, double* nbr_w, int32_t* stats, void* ws, size_t ws_bytes,
                   hipStream_t stream, const PackJob* pack, bool stats_zeroed, const ZeroJob* zero, int taper,
-                  bool header_clean, bool sort_cells) {
+                  bool header_clean, bool sort_cells, const double* period) {
   if (g1 < g0 || g0 < 0 || P < 0) return MIA_ERR_SIZE;
   if (n_coord < 1 || n_coord > MIA_MAX_COORD || n_r < 1 || n_r > MIA_MAX_RADII || p_cap < 1) return MIA_ERR_SIZE;
   if (!coord_group || !gc_c || !stats) return MIA_ERR_NULL;
   for (int c = 0; c < n_coord; ++c) if (coord_group[c] < 0 || coord_group[c] >= n_r) return MIA_ERR_SIZE;
   for (int r = 0; r < n_r; ++r) if (!(gc_c[r] > 0.0)) return MIA_ERR_SIZE;
+  bool cyclic = false;
+  if (check_period(period, n_coord, &cyclic) != MIA_OK) return MIA_ERR_ARG;
   const int64_t ng = g1 - g0;
   if (!stats_zeroed) MIA_HIP_TRY(hipMemsetAsync(stats, 0, 2 * sizeof(int32_t), stream));
   if (ng == 0) return MIA_OK;
@@ -799,17 +899,18 @@ int localize_impl(const double* grid_xyz, int64_t g0, int64_t g1, const double* 
 #define MIA_PACK_IN_LOCALIZE 1
 #endif
   int rc = index_build_impl(obs_xyz, P, n_coord, coord_group, gc_c, n_r, ws, ws_bytes, stream, MIA_PACK_IN_LOCALIZE ? nullptr : pack,
-                            zero, header_clean, sort_cells);
+                            zero, header_clean, sort_cells, period);
   if (rc != MIA_OK) return rc;
   return localize_lists_impl(grid_xyz, g0, g1, P, n_coord, coord_group, gc_c, n_r, gc_eps, p_cap, nbr_cnt, nbr_idx, nbr_w, stats, ws,
-                             stream, MIA_PACK_IN_LOCALIZE ? pack : nullptr, taper);
+                             stream, MIA_PACK_IN_LOCALIZE ? pack : nullptr, taper, cyclic);
 }
 
 // neighbour lists of grid points [g0, g1) over an index that already exists in `ws` (second half of localize_impl; the
 // step driver's tile route calls it alone when declined points need per-point lists); P > 0
 int localize_lists_impl(const double* grid_xyz, int64_t g0, int64_t g1, int64_t P, int n_coord, const int32_t* coord_group,
                         const double* gc_c, int n_r, double gc_eps, int p_cap, int32_t* nbr_cnt, int32_t* nbr_idx,
-                        double* nbr_w, int32_t* stats, void* ws, hipStream_t stream, const PackJob* pack, int taper) {
+                        double* nbr_w, int32_t* stats, void* ws, hipStream_t stream, const PackJob* pack, int taper,
+                        bool periodic) {
   const int64_t ng = g1 - g0;
   if (ng <= 0 || P <= 0) return MIA_OK;
   int rc;
@@ -832,7 +933,8 @@ int localize_lists_impl(const double* grid_xyz, int64_t g0, int64_t g1, int64_t 
   if (p_cap >= 64 && ng <= 2147483647LL && !MIA_EXP_FLAG("MIA_LOCALIZE_THREAD")) {   // long lists: one wavefront per grid point
     if (ng + nb_pack > 2147483647LL) return MIA_ERR_UNSUPPORTED;
     lp.nb_main = (unsigned)ng;
-    localize_wave_kernel<<<dim3((unsigned)ng + nb_pack), dim3(64), pack_lds, stream>>>(lp);
+    if (periodic) localize_wave_kernel<true><<<dim3((unsigned)ng + nb_pack), dim3(64), pack_lds, stream>>>(lp);
+    else localize_wave_kernel<false><<<dim3((unsigned)ng + nb_pack), dim3(64), pack_lds, stream>>>(lp);
     MIA_LAUNCH_CHECK();
     return MIA_OK;
   }
@@ -843,14 +945,16 @@ int localize_lists_impl(const double* grid_xyz, int64_t g0, int64_t g1, int64_t 
     const int64_t nbq = (ng + 15) / 16;
     if (nbq + nb_pack > 2147483647LL) return MIA_ERR_UNSUPPORTED;
     lp.nb_main = (unsigned)nbq;
-    localize_quad_kernel<<<dim3((unsigned)nbq + nb_pack), dim3(64), pack_lds, stream>>>(lp);
+    if (periodic) localize_quad_kernel<true><<<dim3((unsigned)nbq + nb_pack), dim3(64), pack_lds, stream>>>(lp);
+    else localize_quad_kernel<false><<<dim3((unsigned)nbq + nb_pack), dim3(64), pack_lds, stream>>>(lp);
     MIA_LAUNCH_CHECK();
     return MIA_OK;
   }
   const int64_t nb = (ng + 63) / 64;
   if (nb + nb_pack > 2147483647LL) return MIA_ERR_UNSUPPORTED;
   lp.nb_main = (unsigned)nb;
-  localize_kernel<<<dim3((unsigned)nb + nb_pack), dim3(64), pack_lds, stream>>>(lp);
+  if (periodic) localize_kernel<true><<<dim3((unsigned)nb + nb_pack), dim3(64), pack_lds, stream>>>(lp);
+  else localize_kernel<false><<<dim3((unsigned)nb + nb_pack), dim3(64), pack_lds, stream>>>(lp);
   MIA_LAUNCH_CHECK();
   return MIA_OK;
 }
@@ -902,6 +1006,18 @@ extern "C" int mia_letkf_index_build_f64(const double* obs_xyz, int64_t P, int n
   return index_build_impl(obs_xyz, P, n_coord, coord_group, gc_c, n_r, ws, ws_bytes, (hipStream_t)stream);
 }
 
+extern "C" int mia_letkf_index_build_periodic_f64(const double* obs_xyz, int64_t P, int n_coord, const int32_t* coord_group,
+                                                  const double* period, const double* gc_c, int n_r, void* ws, size_t ws_bytes,
+                                                  void* stream) {
+  (void)hipGetLastError();
+  if (!period) return MIA_ERR_NULL;
+  if (n_coord < 1 || n_coord > MIA_MAX_COORD) return MIA_ERR_SIZE;
+  bool cyclic = false;
+  if (check_period(period, n_coord, &cyclic) != MIA_OK) return MIA_ERR_ARG;
+  return index_build_impl(obs_xyz, P, n_coord, coord_group, gc_c, n_r, ws, ws_bytes, (hipStream_t)stream, nullptr, nullptr, false,
+                          true, period);
+}
+
 extern "C" int mia_letkf_localize_f64(const double* grid_xyz, int64_t g0, int64_t g1,
                                       const double* obs_xyz, int64_t P, int n_coord,
                                       const int32_t* coord_group, const double* gc_c, int n_r,
@@ -923,6 +1039,23 @@ extern "C" int mia_letkf_localize_taper_f64(int taper, const double* grid_xyz, i
   if (taper != MIA_TAPER_GC && taper != MIA_TAPER_GC_INF) return MIA_ERR_SIZE;
   return mia::localize_impl(grid_xyz, g0, g1, obs_xyz, P, n_coord, coord_group, gc_c, n_r, gc_eps, p_cap, nbr_cnt,
                             nbr_idx, nbr_w, stats, ws, ws_bytes, (hipStream_t)stream, nullptr, false, nullptr, taper);
+}
+
+extern "C" int mia_letkf_localize_taper_periodic_f64(int taper, const double* grid_xyz, int64_t g0, int64_t g1,
+                                                     const double* obs_xyz, int64_t P, int n_coord,
+                                                     const int32_t* coord_group, const double* period, const double* gc_c, int n_r,
+                                                     double gc_eps, int p_cap, int32_t* nbr_cnt, int32_t* nbr_idx,
+                                                     double* nbr_w, int32_t* stats, void* ws, size_t ws_bytes,
+                                                     void* stream) {
+  (void)hipGetLastError();
+  if (taper != MIA_TAPER_GC && taper != MIA_TAPER_GC_INF) return MIA_ERR_SIZE;
+  if (!period) return MIA_ERR_NULL;
+  if (n_coord < 1 || n_coord > MIA_MAX_COORD) return MIA_ERR_SIZE;
+  bool cyclic = false;
+  if (check_period(period, n_coord, &cyclic) != MIA_OK) return MIA_ERR_ARG;
+  return mia::localize_impl(grid_xyz, g0, g1, obs_xyz, P, n_coord, coord_group, gc_c, n_r, gc_eps, p_cap, nbr_cnt,
+                            nbr_idx, nbr_w, stats, ws, ws_bytes, (hipStream_t)stream, nullptr, false, nullptr, taper, false, true,
+                            period);
 }
 
 extern "C" int mia_letkf_localize_from_dist_f64(const double* dist, const int32_t* cand_idx,

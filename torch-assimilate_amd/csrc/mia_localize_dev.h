@@ -22,7 +22,12 @@ struct IndexHeader {        // lives at the start of the workspace, written on d
   unsigned magic;                   // kIndexMagic: mn / invh / n / ncell describe a cell grid
   unsigned err;                     // bucket build: kIndexErrBox / kIndexErrFull (cleared by the tile-list kernel's last workgroup)
   unsigned done_tiles;              // tile-list workgroups finished (the last one cleans the per-cell counts and err)
+  // cyclic coordinates (PeriodicMetric): period[c] > 0 = coordinate c is taken modulo period[c] and its cell grid is [0, period)
+  // cut into n[c] equal cells (mn = 0, no margin); 0 = open.  Part of the cell grid: a bucket build for another period rebuilds it
+  double period[MIA_MAX_COORD];
+  double inv_period[MIA_MAX_COORD];
 };
+static_assert(sizeof(IndexHeader) <= 256, "the index layout reserves 256 bytes for the header");
 constexpr unsigned kIndexMagic = 0x6d696131u;
 constexpr unsigned kIndexErrBox = 1u;      // an observation lies outside the stored box, or the radii changed: the box must be rebuilt
 constexpr unsigned kIndexErrFull = 2u;     // a cell holds more observations than a bucket has entries: scan-based index instead
@@ -31,6 +36,23 @@ __device__ inline int cell_coord(double x, double mn, double invh, int n) {
   double f = floor((x - mn) * invh);
   f = f < -2.0 ? -2.0 : f;
   f = f > double(n) + 1.0 ? double(n) + 1.0 : f;
+  return (f == f) ? int(f) : -2;  // NaN coordinate -> no cell
+}
+
+// ---- cyclic coordinates.  A coordinate of period L is reduced to [0, L) where it is read (grid point) or binned (observation).  The
+// displacement of a candidate o from a point g is then (o + s) - g with s in {-L, 0, +L} the shift of the candidate's image: one
+// shift per cell range of the window where the window decides it (three or more cells along the axis), or per pair, the minimum
+// image, where it does not (fewer than three cells; a tile whose box straddles the seam or wraps onto itself).  For a pair inside
+// the support both give the same s, so every route -- per-point lists, tile lists, the fused kernel -- forms the same bits.
+__device__ inline double wrap_coord(double x, double L) {
+  double r = __builtin_fma(-L, floor(x / L), x);       // (an explicit fma: the same bits whatever a kernel's contraction setting)
+  r = r < 0.0 ? r + L : r;
+  return r >= L ? r - L : r;                           // (rounding may give exactly L: that is 0)
+}
+__device__ inline double min_image_shift(double o, double g, double L, double inv_L) { return -L * rint((o - g) * inv_L); }
+__device__ inline int cell_coord_cyc(double xr, double invh, int n) {
+  double f = floor(xr * invh);
+  f = f > double(n - 1) ? double(n - 1) : f;
   return (f == f) ? int(f) : -2;  // NaN coordinate -> no cell
 }
 
@@ -91,6 +113,7 @@ struct Tile2Loc {
   // step's error word says so) -- every tile guarding its atomic with a load of the running maximum was a dependent round trip to
   // ONE address of all resident wavefronts at once, 6 us of the kernel's 43 at config 2 (tools/tile2f_stamps.py)
   int longest_bound;
+  int periodic;          // the bucket index has cyclic coordinates: the PERIODIC instantiation of tile_localize
 };
 constexpr int kStepSampledLongest = 64;      // status bit in counters[3] / [7] (include/mia_letkf.h: MIA_STEP_STATUS_SAMPLED)
 constexpr int kStepNonfinite = 128;          // ... MIA_STEP_STATUS_NONFINITE: some point of the fused kernel's launch carries MIA_FLAG_NONFINITE
@@ -99,6 +122,68 @@ constexpr int kStepNonfinite = 128;          // ... MIA_STEP_STATUS_NONFINITE: s
 // contiguous range), evaluates distance and taper in float64 and compacts the observations whose weight
 // exceeds eps with a wave ballot, in cell order, ascending index inside a cell.  The first `cap` survivors
 // are written as (index, sqrt(weight)); the return value is the true count (may exceed cap).
+// One segment of the cell window of a grid point on a cyclic index (cells cg of its reduced coordinates): row o of the 3^(nc-1)
+// rows of outer cells, part 0 / 1 of its last-coordinate range (a range across the seam is two).  False where the segment is
+// empty; else the cell range [c_lo, c_hi], the image shift of its candidates per coordinate, and the coordinates whose shift is
+// taken per pair (pw, bit c: fewer than three cells along c -- the window would visit a cell twice, so every cell once instead).
+struct CycSeg { int c_lo, c_hi; double s[MIA_MAX_COORD]; unsigned pw; };
+__device__ inline bool cyc_window_seg(const IndexHeader* h, int nc, const int* cg, int o, int part, CycSeg& sg) {
+  int base = 0;
+  sg.pw = 0u;
+  for (int c = 0; c < MIA_MAX_COORD; ++c) sg.s[c] = 0.0;
+  for (int a = 0; a + 1 < nc; ++a) {
+    const int i = nc == 2 ? o : (a == 0 ? o / 3 : o % 3);
+    const int n = h->n[a];
+    const double L = h->period[a];
+    int c = cg[a] + i - 1;
+    if (L > 0.0) {
+      if (cg[a] < 0) return false;                    // (NaN coordinate)
+      if (n < 3) {
+        if (i >= n) return false;
+        c = cg[a] + i >= n ? cg[a] + i - n : cg[a] + i;
+        sg.pw |= 1u << a;
+      } else if (c < 0) { c += n; sg.s[a] = -L; }
+      else if (c >= n) { c -= n; sg.s[a] = L; }
+    } else if (c < 0 || c >= n) {
+      return false;
+    }
+    base = base * n + c;
+  }
+  const int l = nc - 1, n = h->n[l];
+  const double L = h->period[l];
+  int lo = cg[l] - 1, hi = cg[l] + 1;
+  if (L > 0.0) {
+    if (cg[l] < 0) return false;
+    if (n < 3) {
+      if (part) return false;
+      lo = 0; hi = n - 1; sg.pw |= 1u << l;
+    } else if (lo < 0) {
+      if (part == 0) { lo = hi = n - 1; sg.s[l] = -L; } else lo = 0;
+    } else if (hi >= n) {
+      if (part == 0) hi = n - 1; else { lo = hi = 0; sg.s[l] = L; }
+    } else if (part) {
+      return false;
+    }
+  } else {
+    if (part) return false;
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > n - 1 ? n - 1 : hi;
+    if (lo > hi) return false;
+  }
+  sg.c_lo = base * n + lo; sg.c_hi = base * n + hi;
+  return true;
+}
+// displacement o - g of a candidate on a cyclic index: o's image shifted by s, or by the minimum-image shift where pw
+__device__ inline double cyc_disp(double o, double g, double s, bool pw, double L, double inv_L) {
+  return (o + (pw ? min_image_shift(o, g, L, inv_L) : s)) - g;
+}
+// a grid point's coordinate c as the kernels read it: reduced on a cyclic axis, and its cell
+__device__ inline void point_cell(const IndexHeader* h, int c, double x, double* xr, int* cell) {
+  const double L = h->period[c];
+  if (L > 0.0) { *xr = wrap_coord(x, L); *cell = cell_coord_cyc(*xr, h->invh[c], h->n[c]); }
+  else { *xr = x; *cell = cell_coord(x, h->mn[c], h->invh[c], h->n[c]); }
+}
+
 template <typename WT>
 __device__ inline int scan_neighbours(const ScanParams& p, int64_t g, int lane, int cap, int* oidx, WT* ow) {
   const IndexHeader* h = p.hdr;
@@ -160,6 +245,51 @@ __device__ inline int scan_neighbours(const ScanParams& p, int64_t g, int lane, 
   return count;
 }
 
+// The same on an index with cyclic coordinates (cyc_window_seg: up to two cell ranges per row; cyc_disp: the candidate's image).
+template <typename WT>
+__device__ inline int scan_neighbours_cyc(const ScanParams& p, int64_t g, int lane, int cap, int* oidx, WT* ow) {
+  const IndexHeader* h = p.hdr;
+  double gx[MIA_MAX_COORD];
+  int cg[MIA_MAX_COORD];
+  for (int c = 0; c < MIA_MAX_COORD; ++c) { gx[c] = 0.0; cg[c] = 0; }
+  for (int c = 0; c < p.nc; ++c) {
+    gx[c] = p.grid[g * p.nc + c];
+    point_cell(h, c, gx[c], &gx[c], &cg[c]);
+  }
+  int count = 0;
+  const int nc = p.nc;
+  const int n_outer = nc == 1 ? 1 : (nc == 2 ? 3 : 9);
+  for (int o = 0; o < 2 * n_outer; ++o) {
+    CycSeg sg;
+    if (!cyc_window_seg(h, nc, cg, o >> 1, o & 1, sg)) continue;
+    const int beg = p.start[sg.c_lo], end = p.start[sg.c_hi + 1];
+    for (int b = beg; b < end; b += 64) {
+      const int pos = b + lane;
+      bool use = false;
+      int j = -1;
+      double wgt = 0.0;
+      if (pos < end) {
+        j = p.sorted[pos];
+        double d2[MIA_MAX_RADII] = {0.0, 0.0, 0.0};
+        for (int c = 0; c < nc; ++c) {
+          const double dx = cyc_disp(p.sxyz[(int64_t)pos * nc + c], gx[c], sg.s[c], (sg.pw >> c) & 1u, h->period[c], h->inv_period[c]);
+          d2[p.group[c]] += dx * dx;
+        }
+        wgt = 1.0;
+        for (int r = 0; r < p.n_r; ++r) wgt *= taper_d2(p.taper, d2[r], p.inv_c[r], p.cc[r]);
+        use = wgt > p.eps;
+      }
+      const unsigned long long mask = __ballot(use);
+      if (use) {
+        const int slot = count + __popcll(mask & ((1ull << lane) - 1ull));
+        if (slot < cap) { oidx[slot] = j; ow[slot] = WT(wgt * rsqrt_f64(wgt)); }
+      }
+      count += __popcll(mask);
+    }
+  }
+  return count;
+}
+
 // layout of the index workspace (built by mia_letkf_index_build_f64)
 struct IndexLayout {
   IndexHeader* hdr; int* start; int* cursor; int* sorted; int* cell_of; int* rank_of; double* sxyz; size_t bytes; size_t cap;
@@ -200,10 +330,13 @@ static inline IndexLayout index_layout(void* ws, int64_t P, int nc) {
 struct PackJob;
 // up to three small int32 buffers cleared by the first index kernel (only honoured when P > 0: the kernel runs)
 struct ZeroJob { int32_t* ptr[3]; int64_t n[3]; };
+// period: [n_coord] on the host, entry c > 0 = coordinate c is cyclic (nullptr: all open)
 int index_build_impl(const double* obs_xyz, int64_t P, int n_coord, const int32_t* coord_group,
                      const double* gc_c, int n_r, void* ws, size_t ws_bytes, hipStream_t stream,
                      const PackJob* pack = nullptr, const ZeroJob* zero = nullptr, bool header_clean = false,
-                     bool sort_cells = true);
+                     bool sort_cells = true, const double* period = nullptr);
+// a period argument: nullptr or n_coord finite entries >= 0 (MIA_ERR_ARG otherwise); true when some entry is > 0
+int check_period(const double* period, int n_coord, bool* cyclic);
 // neighbour lists of grid points [g0, g1) (mia_letkf_localize_f64 without the argument checks of the C entry);
 // pack: float32 record packing job executed inside the first index kernel; stats_zeroed: stats are cleared by
 // the caller or listed in `zero`
@@ -211,10 +344,11 @@ int localize_impl(const double* grid_xyz, int64_t g0, int64_t g1, const double* 
                   const int32_t* coord_group, const double* gc_c, int n_r, double gc_eps, int p_cap,
                   int32_t* nbr_cnt, int32_t* nbr_idx, double* nbr_w, int32_t* stats, void* ws, size_t ws_bytes,
                   hipStream_t stream, const PackJob* pack, bool stats_zeroed, const ZeroJob* zero,
-                  int taper = MIA_TAPER_GC, bool header_clean = false, bool sort_cells = true);
+                  int taper = MIA_TAPER_GC, bool header_clean = false, bool sort_cells = true, const double* period = nullptr);
 int localize_lists_impl(const double* grid_xyz, int64_t g0, int64_t g1, int64_t P, int n_coord, const int32_t* coord_group,
                         const double* gc_c, int n_r, double gc_eps, int p_cap, int32_t* nbr_cnt, int32_t* nbr_idx,
-                        double* nbr_w, int32_t* stats, void* ws, hipStream_t stream, const PackJob* pack, int taper);
+                        double* nbr_w, int32_t* stats, void* ws, hipStream_t stream, const PackJob* pack, int taper,
+                        bool periodic = false);
 // lists of the points flagged MIA_FLAG_RETRY into the order a sorted index gives (see sort_flagged_lists_kernel)
 int sort_flagged_lists(const int32_t* flags, const int32_t* nbr_cnt, int32_t* nbr_idx, double* nbr_w, int64_t ng, int p_cap,
                        void* ws, int64_t P, int n_coord, hipStream_t stream);
@@ -225,6 +359,6 @@ int make_scan_params(ScanParams* sp, const double* grid_xyz, int64_t P, int n_co
 struct SplitPackJob;
 int index_bucket_build_impl(const double* obs_xyz, int64_t P, int n_coord, const int32_t* coord_group, const double* gc_c, int n_r,
                             void* ws, size_t ws_bytes, hipStream_t stream, const ZeroJob* zero, bool fresh_box,
-                            const SplitPackJob* spack = nullptr, int* counts = nullptr);
+                            const SplitPackJob* spack = nullptr, int* counts = nullptr, const double* period = nullptr);
 
 }  // namespace mia

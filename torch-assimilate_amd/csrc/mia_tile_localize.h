@@ -104,7 +104,14 @@ struct TileLocOut {
 // completion counter: 6250 atomics on one address cost 75 us.)
 // NC = number of coordinates, TAPER = MIA_TAPER_*: compile-time, so that the distance loops unroll and the taper is one
 // straight-line polynomial (the generic form spent more scalar instructions on its loops than vector ones on the weights).
-template <bool BUCKET, int NC, int TAPER>
+// PERIODIC: the index may have cyclic coordinates (IndexHeader::period; the open instantiation never reads it).  On a cyclic
+// coordinate the tile's box is taken on the circle -- cells relative to the tile's first point, then min / max, so that a tile at
+// the seam spans a few cells and not the ring -- and its cells are enumerated modulo n.  Where the tile's points all lie on one side
+// of the seam the box decides the image of every candidate: ONE shift per cell, added where the candidate's coordinates are
+// gathered, and the pair loop is the open one.  Where it cannot (a point beyond the seam, fewer than three cells, a box that
+// wraps onto itself: then the whole ring, every cell once) the tile is `pairwise`: candidates unshifted, the minimum image per
+// pair (cyc_disp) -- a few tiles of a ring.  Both form (o + s) - g as the per-point kernels do: the same bits.
+template <bool BUCKET, int NC, int TAPER, bool PERIODIC = false>
 __device__ __forceinline__ TileLocOut tile_localize(const ScanParams& q, int64_t g0, int64_t ng, int ut, int64_t tile,
                                                     unsigned char* tl_lds, int lane) {
   const TileLocLds lds_(tl_lds);
@@ -124,7 +131,8 @@ __device__ __forceinline__ TileLocOut tile_localize(const ScanParams& q, int64_t
       int cg = 0;
       if (c < nc) {
         gx = q.grid[pt * nc + c];
-        cg = cell_coord(gx, hd->mn[c], hd->invh[c], hd->n[c]);
+        if constexpr (PERIODIC) point_cell(hd, c, gx, &gx, &cg);
+        else cg = cell_coord(gx, hd->mn[c], hd->invh[c], hd->n[c]);
       }
       gxs[lane * MIA_MAX_COORD + c] = gx;
       cgs[lane * MIA_MAX_COORD + c] = cg;
@@ -136,16 +144,46 @@ __device__ __forceinline__ TileLocOut tile_localize(const ScanParams& q, int64_t
   MIA_TL_STAMP(1);
   // the tile's cell box: [min cell - 1, max cell + 1] per coordinate, clipped to the cell grid
   int lo[MIA_MAX_COORD], hi[MIA_MAX_COORD];
+  // (cyclic coordinates: the period and its inverse, and whether the tile is pairwise -- see above)
+  double perL[NC], perI[NC];
+  bool pairwise = false;
+  if constexpr (PERIODIC) {
+#pragma unroll
+    for (int c = 0; c < NC; ++c) { perL[c] = hd->period[c]; perI[c] = hd->inv_period[c]; }
+  }
   for (int c = 0; c < MIA_MAX_COORD; ++c) {
     // (lane cl holds point cl's cell -- points past the tile's end repeat its last one, see above -- and the sixteen lanes of a row
     //  reduce with four DPP steps each way; the loop over the points in LDS this replaces was a sixth of the kernel's instructions)
     int mn = cgs[cl * MIA_MAX_COORD + c], mx = mn;
+    bool cyc = false;
+    int cg0 = 0, ncyc = 1;
+    if constexpr (PERIODIC) {
+      if (c < nc && hd->period[c] > 0.0) {
+        // cells relative to the first point, in (-n/2, n/2]; a NaN point (cell -2) or a point beyond the seam marks the tile pairwise
+        cyc = true;
+        ncyc = hd->n[c];
+        cg0 = __builtin_amdgcn_readfirstlane(cgs[c]);
+        int rel = mn - cg0;
+        rel = rel < 0 ? rel + ncyc : rel;
+        rel = rel > ncyc / 2 ? rel - ncyc : rel;
+        const bool odd = mn < 0 || cg0 < 0 || cg0 + rel < 0 || cg0 + rel >= ncyc;
+        pairwise = pairwise || __ballot(odd) != 0ull;
+        mn = mx = rel;
+      }
+    }
 #define MIA_TL_ROW_STEP(ctrl) do { const int a_ = __builtin_amdgcn_update_dpp(0, mn, ctrl, 0xf, 0xf, false), b_ = __builtin_amdgcn_update_dpp(0, mx, ctrl, 0xf, 0xf, false); \
                                    mn = a_ < mn ? a_ : mn; mx = b_ > mx ? b_ : mx; } while (0)
     MIA_TL_ROW_STEP(0xB1); MIA_TL_ROW_STEP(0x4E); MIA_TL_ROW_STEP(0x124); MIA_TL_ROW_STEP(0x128);      // quad_perm x 2, row_ror:4, row_ror:8
 #undef MIA_TL_ROW_STEP
     lo[c] = mn - 1 < 0 ? 0 : mn - 1;
     hi[c] = mx + 1 > hd->n[c] - 1 ? hd->n[c] - 1 : mx + 1;
+    if constexpr (PERIODIC) {
+      if (cyc) {      // unwrapped cells [lo, hi], taken modulo n below; the whole ring where the box would wrap onto itself
+        lo[c] = cg0 + mn - 1;
+        hi[c] = cg0 + mx + 1;
+        if (ncyc < 3 || hi[c] - lo[c] + 1 > ncyc || cg0 < 0) { lo[c] = 0; hi[c] = ncyc - 1; pairwise = true; }
+      }
+    }
     if (c >= nc) { lo[c] = 0; hi[c] = 0; }
     lo[c] = __builtin_amdgcn_readfirstlane(lo[c]);       // (the same in every lane: scalar loop bounds below)
     hi[c] = __builtin_amdgcn_readfirstlane(hi[c]);
@@ -192,6 +230,13 @@ __device__ __forceinline__ TileLocOut tile_localize(const ScanParams& q, int64_t
 #pragma unroll
   for (int i = 0; i < 4; ++i) ptok[i] = 4 * pg + i < npts;
   int cntl[4] = {0, 0, 0, 0};          // local observations of point 4 pg + i met by THIS lane (one candidate column); summed at the end
+  // displacement of candidate coordinate ox from point i's: the minimum image per pair on the cyclic coordinates of a pairwise tile
+  auto disp = [&](double ox, int i, int c) -> double {
+    if constexpr (PERIODIC) {
+      if (pairwise) return cyc_disp(ox, gxr[i][c], 0.0, perL[c] > 0.0, perL[c], perI[c]);
+    }
+    return ox - gxr[i][c];
+  };
   auto weigh = [&](bool have, const Cand& cd) {
 #pragma clang fp contract(off)      // (the same bits in every kernel this is inlined into, see gc_taper_fast)
     const int oj = cd.oj;
@@ -211,14 +256,14 @@ __device__ __forceinline__ TileLocOut tile_localize(const ScanParams& q, int64_t
         double d2[MIA_MAX_RADII] = {0.0, 0.0, 0.0};
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-          const double dx = ox[c] - gxr[i][c];
+          const double dx = disp(ox[c], i, c);
 #pragma unroll
           for (int r = 0; r < (NC == 1 ? 1 : MIA_MAX_RADII); ++r)
             if (grp[c] == r) d2[r] = __builtin_fma(dx, dx, d2[r]);
         }
         float wf = 1.0f;
         if constexpr (NC == 1) {
-          wf = gc_taper_fast_1d(ox[0] - gxr[i][0], twoc0, icf[0], ccf[0]);
+          wf = gc_taper_fast_1d(disp(ox[0], i, 0), twoc0, icf[0], ccf[0]);
         } else {
 #pragma unroll
           for (int r = 0; r < MIA_MAX_RADII; ++r)
@@ -238,7 +283,7 @@ __device__ __forceinline__ TileLocOut tile_localize(const ScanParams& q, int64_t
             for (int r = 0; r < n_r; ++r) {
               double d2r = 0.0;
               for (int c = 0; c < NC; ++c)
-                if (grp[c] == r) { const double dx = ox[c] - gxr[i][c]; d2r = __builtin_fma(dx, dx, d2r); }
+                if (grp[c] == r) { const double dx = disp(ox[c], i, c); d2r = __builtin_fma(dx, dx, d2r); }
               wgt *= gc_taper_d2(d2r, q.inv_c[r], q.cc[r]);
             }
             const bool u64 = wgt > q.eps;
@@ -256,7 +301,7 @@ __device__ __forceinline__ TileLocOut tile_localize(const ScanParams& q, int64_t
         double d2[MIA_MAX_RADII] = {0.0, 0.0, 0.0};
 #pragma unroll
         for (int c = 0; c < NC; ++c) {
-          const double dx = ox[c] - gxr[i][c];
+          const double dx = disp(ox[c], i, c);
 #pragma unroll
           for (int r = 0; r < (NC == 1 ? 1 : MIA_MAX_RADII); ++r)
             if (grp[c] == r) d2[r] = __builtin_fma(dx, dx, d2[r]);
@@ -286,6 +331,15 @@ __device__ __forceinline__ TileLocOut tile_localize(const ScanParams& q, int64_t
     }
     ubase += __popc(memb);
   };
+  // (cyclic coordinates: unwrapped cell u of the box -> its cell modulo n, and the shift of its candidates' image -- none where pairwise)
+  auto wrap_cell = [&](int c, int u, double* sh) {
+    if constexpr (PERIODIC) {
+      const int n = hd->n[c];
+      if (u < 0) { u += n; if (!pairwise) *sh = -perL[c]; }
+      else if (u >= n) { u -= n; if (!pairwise) *sh = perL[c]; }
+    }
+    return u;
+  };
   if constexpr (BUCKET) {
     const int cap = hd->bucket_cap;
     const int nlast = empty ? 0 : hi[last] - lo[last] + 1;
@@ -293,12 +347,22 @@ __device__ __forceinline__ TileLocOut tile_localize(const ScanParams& q, int64_t
     box_overflow = box_overflow || ncb > 64;
     overflow = overflow || ncb > 64;
     int mycid = 0, mycnt = 0;
+    double mysh[NC];           // (PERIODIC: the image shift of this lane's cell)
+#pragma unroll
+    for (int c = 0; c < NC; ++c) mysh[c] = 0.0;
     if (!overflow && lane < (int)ncb) {
       const int row = NC == 1 ? 0 : lane / nlast, cc = lane - row * nlast;      // (one coordinate: one row of cells, no division)
+      if constexpr (PERIODIC) {
+        int id = 0;
+        if constexpr (NC == 2) id = wrap_cell(0, lo[0] + row, &mysh[0]);
+        else if constexpr (NC == 3) id = wrap_cell(0, lo[0] + row / n1, &mysh[0]) * hd->n[1] + wrap_cell(1, lo[1] + row % n1, &mysh[1]);
+        mycid = id * hd->n[last] + wrap_cell(last, lo[last] + cc, &mysh[NC - 1]);
+      } else {
       int base_cell = 0;
       if (nc == 2) base_cell = (lo[0] + row) * hd->n[1];
       else if (nc == 3) base_cell = ((lo[0] + row / n1) * hd->n[1] + (lo[1] + row % n1)) * hd->n[2];
       mycid = base_cell + lo[last] + cc;
+      }
       mycnt = q.start[mycid];
       mycnt = mycnt > cap ? cap : mycnt;
     }
@@ -329,7 +393,11 @@ __device__ __forceinline__ TileLocOut tile_localize(const ScanParams& q, int64_t
         int sel = 0;                                         // the cell of candidate qc: last cell whose prefix is <= qc
         for (int i = 1; i < ncbi; ++i) sel += pref[i] <= qc ? 1 : 0;
         const int cid = __shfl(mycid, sel, 64), pf = pref[sel];
-        const Cand cd = fetch((int64_t)cid * cap + (qc - pf));
+        Cand cd = fetch((int64_t)cid * cap + (qc - pf));
+        if constexpr (PERIODIC) {      // (the candidate's image: shifted once here, not per pair)
+#pragma unroll
+          for (int c = 0; c < NC; ++c) cd.ox[c] = cd.ox[c] + __shfl(mysh[c], sel, 64);
+        }
         coj[lane] = cd.oj;
 #pragma unroll
         for (int c = 0; c < NC; ++c) cox[lane * NC + c] = cd.ox[c];
@@ -350,6 +418,33 @@ __device__ __forceinline__ TileLocOut tile_localize(const ScanParams& q, int64_t
     for (int s_ = lane; s_ < kTlUmax; s_ += 64) uinv[s_] = -1;
   } else {
     for (int row = 0; row < (overflow ? 0 : (int)nrows); ++row) {
+      if constexpr (PERIODIC) {
+        // the row's cells of the last coordinate: one range, or two where it crosses the seam (a range never crosses both ends)
+        double sh[NC];
+#pragma unroll
+        for (int c = 0; c < NC; ++c) sh[c] = 0.0;
+        int id = 0;
+        if constexpr (NC == 2) id = wrap_cell(0, lo[0] + row, &sh[0]);
+        else if constexpr (NC == 3) id = wrap_cell(0, lo[0] + row / n1, &sh[0]) * hd->n[1] + wrap_cell(1, lo[1] + row % n1, &sh[1]);
+        const int nl = hd->n[last];
+        for (int part = 0; part < 2; ++part) {
+          int a = lo[last], b = hi[last];
+          if (a < 0) { if (part == 0) { a += nl; b = nl - 1; } else a = 0; }
+          else if (b >= nl) { if (part == 0) b = nl - 1; else { a = 0; b -= nl; } }
+          else if (part) break;
+          sh[NC - 1] = 0.0;
+          (void)wrap_cell(last, part == 0 ? lo[last] : hi[last], &sh[NC - 1]);
+          const int beg = __builtin_amdgcn_readfirstlane(q.start[id * nl + a]);
+          const int end = __builtin_amdgcn_readfirstlane(q.start[id * nl + b + 1]);
+          for (int pos0 = beg; pos0 < end; pos0 += 16) {
+            const bool have = pos0 + cl < end;
+            Cand cd = fetch(have ? pos0 + cl : end - 1);
+#pragma unroll
+            for (int c = 0; c < NC; ++c) cd.ox[c] = cd.ox[c] + sh[c];
+            weigh(have, cd);
+          }
+        }
+      } else {
       int base_cell = 0;
       if (nc == 2) base_cell = (lo[0] + row) * hd->n[1];
       else if (nc == 3) base_cell = ((lo[0] + row / n1) * hd->n[1] + (lo[1] + row % n1)) * hd->n[2];
@@ -358,6 +453,7 @@ __device__ __forceinline__ TileLocOut tile_localize(const ScanParams& q, int64_t
       for (int pos0 = beg; pos0 < end; pos0 += 16) {
         const bool have = pos0 + cl < end;
         weigh(have, fetch(have ? pos0 + cl : end - 1));
+      }
       }
     }
   }

@@ -700,6 +700,7 @@ struct GeomStamp {
   int64_t G, P;
   double eps, rc[MIA_MAX_RADII];
   int cg[MIA_MAX_COORD];
+  double per[MIA_MAX_COORD];      // periods of the cyclic coordinates (0: open)
 };
 static std::mutex g_stamp_mu;
 // ... and which of the index layout's two per-cell count arrays (cursor / start: the bucket index needs no starts) the workspace's
@@ -783,10 +784,13 @@ static int step_impl(const float* X, int64_t G, int m, int k, const float* Yb, c
                      mia_comm_t* comm, int n_chunks, int phase, float* Xa, int32_t* flags, int32_t* counters, void* ws,
                      size_t ws_bytes, void* stream, void* comm_stream, void* prep_stream, int step_flags, int stage,
                      hipEvent_t* pe_io, uint32_t* seq_io, hipEvent_t t_start, hipEvent_t t_stop, hipEvent_t* kdone_out,
-                     StepDecision* dec_io) {
+                     StepDecision* dec_io, const double* period) {
   const bool do1 = stage != 2, do2 = stage != 1;
   if (kdone_out) *kdone_out = nullptr;
   if (!X || !Xa || !flags || !counters || !ws || !grid_xyz || !coord_group || !gc_c) return MIA_ERR_NULL;
+  bool cyclic = false;      // (period: nullptr or [n_coord] on the host, > 0 = cyclic coordinate -- every index build of the step takes it)
+  if (n_coord >= 1 && n_coord <= MIA_MAX_COORD && mia::check_period(period, n_coord, &cyclic) != MIA_OK) return MIA_ERR_ARG;
+  if (!cyclic) period = nullptr;
   if (P > 0 && (!Yb || !d || !obs_xyz)) return MIA_ERR_NULL;
   if (method < 0 || method > 2 || (phase != 0 && phase != 1)) return MIA_ERR_SIZE;
   if ((uintptr_t)ws % 256) return MIA_ERR_ALIGN;
@@ -861,6 +865,7 @@ static int step_impl(const float* X, int64_t G, int m, int k, const float* Yb, c
   stamp_now.G = G; stamp_now.P = P; stamp_now.rank = rank; stamp_now.world = world; stamp_now.k = k; stamp_now.eps = gc_eps;
   for (int i = 0; i < n_r && i < MIA_MAX_RADII; ++i) stamp_now.rc[i] = gc_c[i];
   for (int i = 0; i < n_coord && i < MIA_MAX_COORD; ++i) stamp_now.cg[i] = coord_group[i];
+  for (int i = 0; i < n_coord && i < MIA_MAX_COORD; ++i) stamp_now.per[i] = period ? period[i] : 0.0;
   // (decided once per step -- where its preparation is enqueued; the analysis stage and a redo of declined points read the decision)
   StepDecision dec_local;
   StepDecision& D = dec_io ? *dec_io : dec_local;
@@ -908,6 +913,7 @@ static int step_impl(const float* X, int64_t G, int m, int k, const float* Yb, c
     tl_loc.scan.start = tl_counts;
     tl_loc.stats = ctr;
     tl_loc.longest_bound = pm_tl;
+    tl_loc.periodic = cyclic ? 1 : 0;
   }
   (void)hipGetLastError();
   if (exch || peer) {
@@ -954,16 +960,18 @@ static int step_impl(const float* X, int64_t G, int m, int k, const float* Yb, c
                                           zero_in_kernel ? &zj : nullptr,
                                           !(step_flags & MIA_STEP_WS_CLEAN) || (step_flags & MIA_STEP_FRESH_BOX) || cnt_must_clear,
                                           tl_rbf ? nullptr : &sj,
-                                          tl_counts);
+                                          tl_counts, period);
       else {
         const bool arrays_clean = count_arrays_clean_for_scan(ws);      // (a scan-based build counts in array 0)
         rc = mia::index_build_impl(obs_xyz, P, n_coord, coord_group, gc_c, n_r, base + L.loc, L.loc_bytes, ps, nullptr,
-                                   zero_in_kernel ? &zj : nullptr, (step_flags & MIA_STEP_WS_CLEAN) != 0 && arrays_clean, false);
+                                   zero_in_kernel ? &zj : nullptr, (step_flags & MIA_STEP_WS_CLEAN) != 0 && arrays_clean, false,
+                                   period);
       }
       if (rc != MIA_OK) return rc;
       if (!tl_fused) {
         rc = mia::tile_lists_launch(grid_xyz, b0, b1 - b0, P, n_coord, coord_group, gc_c, n_r, gc_eps, MIA_TAPER_GC, L.ut,
-                                    base + L.tl, ctr, base + L.loc, ps, (tl_bucket || tl_rbf) ? nullptr : &sj, tl_bucket, tl_counts);
+                                    base + L.tl, ctr, base + L.loc, ps, (tl_bucket || tl_rbf) ? nullptr : &sj, tl_bucket, tl_counts,
+                                    cyclic);
         if (rc != MIA_OK) return rc;
       }
     } else if (b1 > b0) {
@@ -974,7 +982,7 @@ static int step_impl(const float* X, int64_t G, int m, int k, const float* Yb, c
       rc = mia::localize_impl(grid_xyz, b0, b1, obs_xyz, P, n_coord, coord_group, gc_c, n_r, gc_eps, L.cap,
                               cnt, idx, w, ctr, base + L.loc, L.loc_bytes, ps, P > 0 ? &job : nullptr, true,
                               zero_in_kernel ? &zj : nullptr, MIA_TAPER_GC,
-                              (step_flags & MIA_STEP_WS_CLEAN) != 0 && count_arrays_clean_for_scan(ws), !lazy);
+                              (step_flags & MIA_STEP_WS_CLEAN) != 0 && count_arrays_clean_for_scan(ws), !lazy, period);
       if (rc != MIA_OK) return rc;
     }
     if (ps != s) {   // the analysis stream starts once the preparation stream has produced records and lists
@@ -1034,13 +1042,13 @@ static int step_impl(const float* X, int64_t G, int m, int k, const float* Yb, c
           if (tl_bucket) {      // (the buckets are no scan-based index: build one, unsorted like the lazy route's)
             (void)count_arrays_clean_for_scan(ws);      // (cleared whole below; the scan counts in array 0)
             rc = mia::index_build_impl(obs_xyz, P, n_coord, coord_group, gc_c, n_r, base + L.loc, L.loc_bytes, (hipStream_t)stream,
-                                       nullptr, nullptr, false, false);
+                                       nullptr, nullptr, false, false, period);
             if (rc != MIA_OK) return rc;
           }
         }
         rc = mia::localize_lists_impl(grid_xyz, c0, c1, P, n_coord, coord_group, gc_c, n_r, gc_eps, L.cap, const_cast<int32_t*>(ccnt),
                                       const_cast<int32_t*>(cidx), const_cast<double*>(cw), (int32_t*)(base + L.scratch),
-                                      base + L.loc, (hipStream_t)stream, nullptr, MIA_TAPER_GC);
+                                      base + L.loc, (hipStream_t)stream, nullptr, MIA_TAPER_GC, cyclic);
         if (rc != MIA_OK) return rc;
         rc = mia::sort_flagged_lists(cfl, ccnt, const_cast<int32_t*>(cidx), const_cast<double*>(cw), c1 - c0, (int)L.cap,
                                      base + L.loc, P, n_coord, (hipStream_t)stream);
@@ -1175,7 +1183,23 @@ extern "C" int mia_letkf_sharded_step_streams_f32(const float* X, int64_t G, int
   t_time_start = t_time_stop = nullptr;
   return step_impl(X, G, m, k, Yb, d, P, grid_xyz, obs_xyz, n_coord, coord_group, gc_c, n_r, gc_eps, inf_factor, gamma, method,
                    p_max_assumed, comm, n_chunks, phase, Xa, flags, counters, ws, ws_bytes, stream, comm_stream, prep_stream,
-                   step_flags, 0, &pe, &seq, t0, t1, nullptr, nullptr);
+                   step_flags, 0, &pe, &seq, t0, t1, nullptr, nullptr, nullptr);
+}
+
+extern "C" int mia_letkf_sharded_step_periodic_f32(const float* X, int64_t G, int m, int k, const float* Yb, const float* d, int64_t P,
+                                                   const double* grid_xyz, const double* obs_xyz, int n_coord, const int32_t* coord_group,
+                                                   const double* period, const double* gc_c, int n_r, double gc_eps, float inf_factor,
+                                                   float gamma, int method, int p_max_assumed, mia_comm_t* comm, int n_chunks, int phase,
+                                                   float* Xa, int32_t* flags, int32_t* counters, void* ws, size_t ws_bytes, void* stream,
+                                                   void* comm_stream, void* prep_stream, int step_flags) {
+  if (!period) return MIA_ERR_NULL;
+  hipEvent_t pe = nullptr;
+  uint32_t seq = 0;
+  const hipEvent_t t0 = t_time_start, t1 = t_time_stop;
+  t_time_start = t_time_stop = nullptr;
+  return step_impl(X, G, m, k, Yb, d, P, grid_xyz, obs_xyz, n_coord, coord_group, gc_c, n_r, gc_eps, inf_factor, gamma, method,
+                   p_max_assumed, comm, n_chunks, phase, Xa, flags, counters, ws, ws_bytes, stream, comm_stream, prep_stream,
+                   step_flags, 0, &pe, &seq, t0, t1, nullptr, nullptr, period);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1191,7 +1215,7 @@ extern "C" int mia_letkf_sharded_step_streams_f32(const float* X, int64_t G, int
 namespace {
 struct StepJob {
   const float* X; int64_t G; int m, k; const float* Yb; const float* d; int64_t P; const double* grid; const double* obs;
-  int n_coord; int32_t cg[MIA_MAX_COORD]; double rc_[MIA_MAX_RADII]; int n_r; double eps; float inf, gamma; int method, hint;
+  int n_coord; int32_t cg[MIA_MAX_COORD]; double rc_[MIA_MAX_RADII]; int n_r; double per[MIA_MAX_COORD] = {0.0, 0.0, 0.0}; double eps; float inf, gamma; int method, hint;
   mia_comm_t* comm; int n_chunks, phase; float* Xa; int32_t* flags; int32_t* counters; void* ws; size_t ws_bytes;
   void *stream, *comm_stream, *prep_stream; int step_flags;
   int32_t* host8; void *after, *on; void** done_event; void *t0, *t1;
@@ -1209,7 +1233,7 @@ struct StepJob {
     struct Scope { Scope(const int* o) { mia::option_override(o); } ~Scope() { mia::option_override(nullptr); } } scope(opts);
     return step_impl(X, G, m, k, Yb, d, P, grid, obs, n_coord, cg, rc_, n_r, eps, inf, gamma, method, hint, comm, n_chunks, phase,
                      Xa, flags, counters, ws, ws_bytes, stream, comm_stream, prep_stream, step_flags, stage, &pe, &seq,
-                     (hipEvent_t)t0, (hipEvent_t)t1, stage == 2 ? &kdone : nullptr, &dec);
+                     (hipEvent_t)t0, (hipEvent_t)t1, stage == 2 ? &kdone : nullptr, &dec, per);
   }
 };
 struct LaunchThreads {
@@ -1440,16 +1464,19 @@ LaunchThreads g_launcher;
 }  // namespace
 
 static thread_local long long t_submit_entry = 0;      // (diagnostics: when the argument-block submission was entered, mia_debug_step_trace)
-extern "C" int mia_letkf_step_submit(const float* X, int64_t G, int m, int k, const float* Yb, const float* d, int64_t P,
-                                     const double* grid_xyz, const double* obs_xyz, int n_coord, const int32_t* coord_group,
-                                     const double* gc_c, int n_r, double gc_eps, float inf_factor, float gamma, int method,
-                                     int p_max_assumed, mia_comm_t* comm, int n_chunks, int phase, float* Xa, int32_t* flags,
-                                     int32_t* counters, void* ws, size_t ws_bytes, void* stream, void* comm_stream,
-                                     void* prep_stream, int step_flags, int32_t* host8, void* after_stream, void* on_stream,
-                                     void** done_event, void* time_start_event, void* time_stop_event, void** job_out) {
+static int step_submit(const float* X, int64_t G, int m, int k, const float* Yb, const float* d, int64_t P,
+                       const double* grid_xyz, const double* obs_xyz, int n_coord, const int32_t* coord_group,
+                       const double* gc_c, int n_r, double gc_eps, float inf_factor, float gamma, int method,
+                       int p_max_assumed, mia_comm_t* comm, int n_chunks, int phase, float* Xa, int32_t* flags,
+                       int32_t* counters, void* ws, size_t ws_bytes, void* stream, void* comm_stream,
+                       void* prep_stream, int step_flags, int32_t* host8, void* after_stream, void* on_stream,
+                       void** done_event, void* time_start_event, void* time_stop_event, void** job_out, const double* period) {
   if (!job_out || !coord_group || !gc_c) return MIA_ERR_NULL;
   if (n_coord < 1 || n_coord > MIA_MAX_COORD || n_r < 1 || n_r > MIA_MAX_RADII) return MIA_ERR_SIZE;
+  bool cyclic = false;
+  if (mia::check_period(period, n_coord, &cyclic) != MIA_OK) return MIA_ERR_ARG;
   StepJob* j = new StepJob();
+  for (int c = 0; c < n_coord; ++c) j->per[c] = cyclic ? period[c] : 0.0;
   j->X = X; j->G = G; j->m = m; j->k = k; j->Yb = Yb; j->d = d; j->P = P; j->grid = grid_xyz; j->obs = obs_xyz;
   j->n_coord = n_coord; j->n_r = n_r; j->eps = gc_eps; j->inf = inf_factor; j->gamma = gamma; j->method = method;
   for (int c = 0; c < n_coord; ++c) j->cg[c] = coord_group[c];
@@ -1480,6 +1507,18 @@ extern "C" int mia_letkf_step_submit(const float* X, int64_t G, int m, int k, co
   return MIA_OK;
 }
 
+extern "C" int mia_letkf_step_submit(const float* X, int64_t G, int m, int k, const float* Yb, const float* d, int64_t P,
+                                     const double* grid_xyz, const double* obs_xyz, int n_coord, const int32_t* coord_group,
+                                     const double* gc_c, int n_r, double gc_eps, float inf_factor, float gamma, int method,
+                                     int p_max_assumed, mia_comm_t* comm, int n_chunks, int phase, float* Xa, int32_t* flags,
+                                     int32_t* counters, void* ws, size_t ws_bytes, void* stream, void* comm_stream,
+                                     void* prep_stream, int step_flags, int32_t* host8, void* after_stream, void* on_stream,
+                                     void** done_event, void* time_start_event, void* time_stop_event, void** job_out) {
+  return step_submit(X, G, m, k, Yb, d, P, grid_xyz, obs_xyz, n_coord, coord_group, gc_c, n_r, gc_eps, inf_factor, gamma, method,
+                     p_max_assumed, comm, n_chunks, phase, Xa, flags, counters, ws, ws_bytes, stream, comm_stream, prep_stream,
+                     step_flags, host8, after_stream, on_stream, done_event, time_start_event, time_stop_event, job_out, nullptr);
+}
+
 extern "C" int mia_letkf_step_submit_args(const mia_step_args_t* a, void** job_out) {
   if (!a) return MIA_ERR_NULL;
   t_submit_entry = LaunchThreads::now_ns();
@@ -1493,10 +1532,10 @@ extern "C" int mia_letkf_step_submit_args(const mia_step_args_t* a, void** job_o
       if (rc != MIA_OK) return rc;
     }
   }
-  return mia_letkf_step_submit(a->X, a->G, a->m, a->k, a->Yb, a->d, a->P, a->grid_xyz, a->obs_xyz, a->n_coord, a->coord_group, a->gc_c,
-                               a->n_r, a->gc_eps, a->inf_factor, a->gamma, a->method, a->p_max_assumed, a->comm, a->n_chunks, a->phase,
-                               a->Xa, a->flags, a->counters, a->ws, a->ws_bytes, a->stream, a->comm_stream, a->prep_stream, a->step_flags,
-                               a->host8, a->after_stream, a->on_stream, a->done_event, a->time_start_event, a->time_stop_event, job_out);
+  return step_submit(a->X, a->G, a->m, a->k, a->Yb, a->d, a->P, a->grid_xyz, a->obs_xyz, a->n_coord, a->coord_group, a->gc_c,
+                     a->n_r, a->gc_eps, a->inf_factor, a->gamma, a->method, a->p_max_assumed, a->comm, a->n_chunks, a->phase,
+                     a->Xa, a->flags, a->counters, a->ws, a->ws_bytes, a->stream, a->comm_stream, a->prep_stream, a->step_flags,
+                     a->host8, a->after_stream, a->on_stream, a->done_event, a->time_start_event, a->time_stop_event, job_out, a->period);
 }
 
 // One step taken at once on the caller's thread through the argument block: what mia_letkf_step_drain + the step call +
@@ -1515,7 +1554,7 @@ extern "C" int mia_letkf_step_run_args(const mia_step_args_t* a, int32_t* out8) 
   rc = step_impl(a->X, a->G, a->m, a->k, a->Yb, a->d, a->P, a->grid_xyz, a->obs_xyz, a->n_coord, a->coord_group, a->gc_c, a->n_r, a->gc_eps,
                  a->inf_factor, a->gamma, a->method, a->p_max_assumed, a->comm, a->n_chunks, a->phase, a->Xa, a->flags, a->counters, a->ws,
                  a->ws_bytes, a->stream, a->comm_stream, a->prep_stream, a->step_flags & ~MIA_STEP_NO_JOIN, 0, &pe, &seq,
-                 (hipEvent_t)a->time_start_event, (hipEvent_t)a->time_stop_event, nullptr, nullptr);
+                 (hipEvent_t)a->time_start_event, (hipEvent_t)a->time_stop_event, nullptr, nullptr, a->period);
   if (rc != MIA_OK) return rc;
   rc = mia_letkf_step_readback(a->counters, a->host8, a->after_stream, a->on_stream, a->done_event);
   if (rc != MIA_OK || !out8) return rc;

@@ -52,7 +52,7 @@ struct TileLocParams {
 };
 
 // The localisation itself: tile_localize<BUCKET, NC, TAPER> (mia_tile_localize.h), shared with the analysis kernel's fused variant.
-template <bool BUCKET, int NC, int TAPER>
+template <bool BUCKET, int NC, int TAPER, bool PERIODIC = false>
 __global__ __launch_bounds__(64) void localize_tiles_kernel(TileLocParams p) {
   MIA_PREP_PRIORITY();
   extern __shared__ __attribute__((aligned(16))) unsigned char tl_lds[];
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(64) void localize_tiles_kernel(TileLocParams p) {
   const int lane = threadIdx.x, cl = lane & 15, pg = lane >> 4;
   const int UMAX = 16 * p.ut;
   const int64_t tile = blockIdx.x;
-  const TileLocOut r = tile_localize<BUCKET, NC, TAPER>(p.scan, p.g0, p.ng, p.ut, tile, tl_lds, lane);
+  const TileLocOut r = tile_localize<BUCKET, NC, TAPER, PERIODIC>(p.scan, p.g0, p.ng, p.ut, tile, tl_lds, lane);
   const TileLocLds L(tl_lds);
   const bool overflow = r.overflow;
   for (int s = lane; s < UMAX; s += 64) {
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(64) void localize_tiles_kernel(TileLocParams p) {
 
 int tile_lists_launch(const double* grid_xyz, int64_t g0, int64_t ng, int64_t P, int n_coord, const int32_t* coord_group,
                       const double* gc_c, int n_r, double gc_eps, int taper, int ut, void* tile_lists, int32_t* stats,
-                      void* index_ws, hipStream_t stream, const SplitPackJob* pack, bool bucket, const int* counts) {
+                      void* index_ws, hipStream_t stream, const SplitPackJob* pack, bool bucket, const int* counts, bool periodic) {
   if (ng < 0 || P < 0 || ut < 1 || ut > 6) return MIA_ERR_SIZE;
   if (!tile_lists || !stats) return MIA_ERR_NULL;
   const TileListLayout L = tile_list_layout(ng, ut);
@@ -125,7 +125,8 @@ int tile_lists_launch(const double* grid_xyz, int64_t g0, int64_t ng, int64_t P,
   tp.nb_main = (unsigned)L.ntile;
   void (*kern)(TileLocParams) = nullptr;
 #define MIA_TL_PICK(B, T)                                                                                                  \
-  kern = n_coord == 1 ? localize_tiles_kernel<B, 1, T> : (n_coord == 2 ? localize_tiles_kernel<B, 2, T> : localize_tiles_kernel<B, 3, T>)
+  if (periodic) kern = n_coord == 1 ? localize_tiles_kernel<B, 1, T, true> : (n_coord == 2 ? localize_tiles_kernel<B, 2, T, true> : localize_tiles_kernel<B, 3, T, true>); \
+  else kern = n_coord == 1 ? localize_tiles_kernel<B, 1, T> : (n_coord == 2 ? localize_tiles_kernel<B, 2, T> : localize_tiles_kernel<B, 3, T>)
   if (bucket) { if (taper == MIA_TAPER_GC_INF) MIA_TL_PICK(true, MIA_TAPER_GC_INF); else MIA_TL_PICK(true, MIA_TAPER_GC); }
   else { if (taper == MIA_TAPER_GC_INF) MIA_TL_PICK(false, MIA_TAPER_GC_INF); else MIA_TL_PICK(false, MIA_TAPER_GC); }
 #undef MIA_TL_PICK
@@ -159,25 +160,46 @@ extern "C" int mia_letkf_tile_lists_bytes(int64_t n_points, int p_max, int extra
   return MIA_OK;
 }
 
-extern "C" int mia_letkf_localize_tiles_f64(int taper, const double* grid_xyz, int64_t g0, int64_t g1,
-                                            const double* obs_xyz, int64_t P, int n_coord, const int32_t* coord_group,
-                                            const double* gc_c, int n_r, double gc_eps, int p_max, int extra_blocks,
-                                            void* tile_lists, size_t tile_lists_bytes, int32_t* stats, void* ws, size_t ws_bytes,
-                                            void* stream_) {
+static int localize_tiles_entry(int taper, const double* grid_xyz, int64_t g0, int64_t g1, const double* obs_xyz, int64_t P,
+                                int n_coord, const int32_t* coord_group, const double* gc_c, int n_r, const double* period,
+                                double gc_eps, int p_max, int extra_blocks, void* tile_lists, size_t tile_lists_bytes, int32_t* stats,
+                                void* ws, size_t ws_bytes, void* stream_) {
   (void)hipGetLastError();
   hipStream_t stream = (hipStream_t)stream_;
   if (taper != MIA_TAPER_GC && taper != MIA_TAPER_GC_INF) return MIA_ERR_SIZE;
   if (g1 < g0 || g0 < 0 || P < 0 || p_max < 0 || extra_blocks < 0) return MIA_ERR_SIZE;
   if (n_coord < 1 || n_coord > MIA_MAX_COORD || n_r < 1 || n_r > MIA_MAX_RADII) return MIA_ERR_SIZE;
   if (!coord_group || !gc_c || !stats || !tile_lists) return MIA_ERR_NULL;
+  bool cyclic = false;
+  if (check_period(period, n_coord, &cyclic) != MIA_OK) return MIA_ERR_ARG;
   const int ut = tile_ut_for(p_max) + extra_blocks;
   if (ut > 6) return MIA_ERR_UNSUPPORTED;
   if (tile_lists_bytes < tile_list_layout(g1 - g0, ut).bytes) return MIA_ERR_WORKSPACE;
   MIA_HIP_TRY(hipMemsetAsync(stats, 0, 2 * sizeof(int32_t), stream));
   if (P > 0) {
-    int rc = index_build_impl(obs_xyz, P, n_coord, coord_group, gc_c, n_r, ws, ws_bytes, stream, nullptr, nullptr, false, false);
+    int rc = index_build_impl(obs_xyz, P, n_coord, coord_group, gc_c, n_r, ws, ws_bytes, stream, nullptr, nullptr, false, false,
+                              period);
     if (rc != MIA_OK) return rc;
   }
   return tile_lists_launch(grid_xyz, g0, g1 - g0, P, n_coord, coord_group, gc_c, n_r, gc_eps, taper, ut, tile_lists, stats, ws,
-                           stream, nullptr, false);
+                           stream, nullptr, false, nullptr, cyclic);
+}
+
+extern "C" int mia_letkf_localize_tiles_f64(int taper, const double* grid_xyz, int64_t g0, int64_t g1,
+                                            const double* obs_xyz, int64_t P, int n_coord, const int32_t* coord_group,
+                                            const double* gc_c, int n_r, double gc_eps, int p_max, int extra_blocks,
+                                            void* tile_lists, size_t tile_lists_bytes, int32_t* stats, void* ws, size_t ws_bytes,
+                                            void* stream_) {
+  return localize_tiles_entry(taper, grid_xyz, g0, g1, obs_xyz, P, n_coord, coord_group, gc_c, n_r, nullptr, gc_eps, p_max,
+                              extra_blocks, tile_lists, tile_lists_bytes, stats, ws, ws_bytes, stream_);
+}
+
+extern "C" int mia_letkf_localize_tiles_periodic_f64(int taper, const double* grid_xyz, int64_t g0, int64_t g1,
+                                                     const double* obs_xyz, int64_t P, int n_coord, const int32_t* coord_group,
+                                                     const double* period, const double* gc_c, int n_r, double gc_eps, int p_max,
+                                                     int extra_blocks, void* tile_lists, size_t tile_lists_bytes, int32_t* stats,
+                                                     void* ws, size_t ws_bytes, void* stream_) {
+  if (!period) return MIA_ERR_NULL;
+  return localize_tiles_entry(taper, grid_xyz, g0, g1, obs_xyz, P, n_coord, coord_group, gc_c, n_r, period, gc_eps, p_max,
+                              extra_blocks, tile_lists, tile_lists_bytes, stats, ws, ws_bytes, stream_);
 }

@@ -81,6 +81,21 @@ class ObsIndex:
     coord_group: list
     P: int
     nc: int
+    period: Optional[list] = None      # cyclic coordinates (> 0) the index was built for; None = open
+
+
+def _periods(period, nc: int):
+    """The period argument of the localisation calls as a ctypes array (None: every coordinate open, the plain C entries)."""
+    if period is None:
+        return None
+    per = [0.0 if p is None else float(p) for p in (period if hasattr(period, "__len__") else [period] * nc)]
+    if len(per) != nc:
+        raise ValueError("period needs one entry per coordinate")
+    if any(not (p >= 0.0 and p < float("inf")) for p in per):
+        raise ValueError("period must be finite and >= 0")
+    if not any(p > 0.0 for p in per):
+        return None
+    return (C.c_double * nc)(*per)
 
 
 class LetkfEngine:
@@ -124,12 +139,13 @@ class LetkfEngine:
     def localize(self, grid_xyz, obs_xyz, radii: Sequence[float], coord_group: Optional[Sequence[int]] = None,
                  eps: float = 1e-5, g0: int = 0, g1: Optional[int] = None,
                  p_cap: Optional[int] = None, assume_p_max: Optional[int] = None,
-                 stats_out: Optional[torch.Tensor] = None, taper: int = 0) -> NeighbourLists:
+                 stats_out: Optional[torch.Tensor] = None, taper: int = 0, period=None) -> NeighbourLists:
         """Neighbour lists of grid points [g0, g1).  By default the maximum list length is read back
         (one 8-byte host sync) to size the analysis launch.  With ``assume_p_max`` (e.g. the value of the
         previous cycle on the same geometry) nothing is read back here: the returned lists carry the
         assumption and ``NeighbourLists.confirm()`` checks it later, e.g. after the analysis has been
-        enqueued; the analysis kernel itself flags any point whose list does not fit (never truncates)."""
+        enqueued; the analysis kernel itself flags any point whose list does not fit (never truncates).  ``period``: one entry per
+        coordinate (or a scalar), > 0 = cyclic coordinate with that period (PeriodicMetric), 0 / None = open."""
         grid = self._dev(grid_xyz, torch.float64)
         obs = self._dev(obs_xyz, torch.float64)
         if grid.dim() == 1:
@@ -149,6 +165,16 @@ class LetkfEngine:
             raise ValueError("coord_group needs one entry per coordinate")
         cg = (C.c_int32 * nc)(*coord_group)
         rc = (C.c_double * n_r)(*radii)
+        per = _periods(period, nc)
+
+        def call(cap, cnt, idx, w):
+            if per is None:
+                return self.lib.mia_letkf_localize_taper_f64(
+                    int(taper), _ptr(grid), g0, g1, _ptr(obs), P, nc, cg, rc, n_r, float(eps), cap,
+                    _ptr(cnt), _ptr(idx), _ptr(w), _ptr(stats), _ptr(ws), ws.numel(), self._stream())
+            return self.lib.mia_letkf_localize_taper_periodic_f64(
+                int(taper), _ptr(grid), g0, g1, _ptr(obs), P, nc, cg, per, rc, n_r, float(eps), cap,
+                _ptr(cnt), _ptr(idx), _ptr(w), _ptr(stats), _ptr(ws), ws.numel(), self._stream())
         nbytes = C.c_size_t(0)
         _cabi.check(self.lib.mia_letkf_localize_workspace_bytes(P, nc, C.byref(nbytes)), "localize_workspace_bytes")
         ws = self._workspace("loc", nbytes.value)
@@ -159,19 +185,13 @@ class LetkfEngine:
             cnt = torch.empty(n, dtype=torch.int32, device=self.device)
             idx = torch.empty((n, cap), dtype=torch.int32, device=self.device)
             w = torch.empty((n, cap), dtype=torch.float64, device=self.device)
-            _cabi.check(self.lib.mia_letkf_localize_taper_f64(
-                int(taper), _ptr(grid), g0, g1, _ptr(obs), P, nc, cg, rc, n_r, float(eps), cap,
-                _ptr(cnt), _ptr(idx), _ptr(w), _ptr(stats), _ptr(ws), ws.numel(), self._stream()),
-                "mia_letkf_localize_f64")
+            _cabi.check(call(cap, cnt, idx, w), "mia_letkf_localize_f64")
             return NeighbourLists(cnt, idx, w, cap, int(assume_p_max), g0, g1, stats)
         while True:
             cnt = torch.empty(n, dtype=torch.int32, device=self.device)
             idx = torch.empty((n, cap), dtype=torch.int32, device=self.device)
             w = torch.empty((n, cap), dtype=torch.float64, device=self.device)
-            _cabi.check(self.lib.mia_letkf_localize_taper_f64(
-                int(taper), _ptr(grid), g0, g1, _ptr(obs), P, nc, cg, rc, n_r, float(eps), cap,
-                _ptr(cnt), _ptr(idx), _ptr(w), _ptr(stats), _ptr(ws), ws.numel(), self._stream()),
-                "mia_letkf_localize_f64")
+            _cabi.check(call(cap, cnt, idx, w), "mia_letkf_localize_f64")
             p_max, n_over = (int(v) for v in stats.tolist())   # host sync: sizes the analysis launch
             if n_over == 0:
                 break
@@ -182,12 +202,12 @@ class LetkfEngine:
     # ------------------------------------------------------------ tile route (round 3)
     def localize_tiles(self, grid_xyz, obs_xyz, radii: Sequence[float], p_max: int,
                        coord_group: Optional[Sequence[int]] = None, eps: float = 1e-5, g0: int = 0,
-                       g1: Optional[int] = None, taper: int = 0, extra_blocks: int = 0) -> "TileLists":
+                       g1: Optional[int] = None, taper: int = 0, extra_blocks: int = 0, period=None) -> "TileLists":
         """Tile lists of grid points [g0, g1) (mia_letkf_localize_tiles_f64): per tile of sixteen points the union of
         their Gaspari-Cohn lists and the sqrt(weight) matrix, in the analysis kernel's register layout.  ``p_max`` bounds
         the local observations of a point (e.g. ``NeighbourLists.p_max`` of an earlier call on the geometry),
         ``extra_blocks`` adds sixteen slots each to what a tile's union may hold; the returned object's ``stats`` holds
-        [longest list, tiles whose union did not fit] on the device."""
+        [longest list, tiles whose union did not fit] on the device.  ``period`` as ``localize``."""
         grid = self._dev(grid_xyz, torch.float64)
         obs = self._dev(obs_xyz, torch.float64)
         if grid.dim() == 1:
@@ -211,9 +231,16 @@ class LetkfEngine:
                     "mia_letkf_tile_lists_bytes")
         lists = torch.empty(max(tb.value, 256), dtype=torch.uint8, device=self.device)
         stats = torch.zeros(2, dtype=torch.int32, device=self.device)
-        _cabi.check(self.lib.mia_letkf_localize_tiles_f64(
-            int(taper), _ptr(grid), g0, g1, _ptr(obs), P, nc, cg, rc, len(radii), float(eps), int(p_max), int(extra_blocks),
-            _ptr(lists), lists.numel(), _ptr(stats), _ptr(ws), ws.numel(), self._stream()), "mia_letkf_localize_tiles_f64")
+        per = _periods(period, nc)
+        if per is None:
+            rcode = self.lib.mia_letkf_localize_tiles_f64(
+                int(taper), _ptr(grid), g0, g1, _ptr(obs), P, nc, cg, rc, len(radii), float(eps), int(p_max), int(extra_blocks),
+                _ptr(lists), lists.numel(), _ptr(stats), _ptr(ws), ws.numel(), self._stream())
+        else:
+            rcode = self.lib.mia_letkf_localize_tiles_periodic_f64(
+                int(taper), _ptr(grid), g0, g1, _ptr(obs), P, nc, cg, per, rc, len(radii), float(eps), int(p_max),
+                int(extra_blocks), _ptr(lists), lists.numel(), _ptr(stats), _ptr(ws), ws.numel(), self._stream())
+        _cabi.check(rcode, "mia_letkf_localize_tiles_f64")
         return TileLists(lists, int(p_max), g0, g1, stats, int(extra_blocks))
 
     def pack_split(self, Yb: torch.Tensor, d: torch.Tensor) -> torch.Tensor:
@@ -323,8 +350,9 @@ class LetkfEngine:
             nbrs.p_cap, nbrs.p_max, float(inf_factor), float(rbf_gamma) if rbf_gamma is not None else 0.0, _ptr(out), out.shape[-1],
             out_offset, _ptr(flags), self._stream()), "mia_letkf_analysis_retry_f32")
 
-    def build_index(self, obs_xyz, radii: Sequence[float], coord_group: Optional[Sequence[int]] = None) -> ObsIndex:
-        """Bin the observations into the uniform cell grid used by the fused-localisation analysis."""
+    def build_index(self, obs_xyz, radii: Sequence[float], coord_group: Optional[Sequence[int]] = None, period=None) -> ObsIndex:
+        """Bin the observations into the uniform cell grid used by the fused-localisation analysis (``period`` as ``localize``;
+        ``analysis_fused`` itself takes open indexes only)."""
         obs = self._dev(obs_xyz, torch.float64)
         if obs.dim() == 1:
             obs = obs[:, None].contiguous()
@@ -336,9 +364,14 @@ class LetkfEngine:
         ws = torch.empty(max(nbytes.value, 256), dtype=torch.uint8, device=self.device)
         cg = (C.c_int32 * nc)(*coord_group)
         rc = (C.c_double * len(radii))(*radii)
-        _cabi.check(self.lib.mia_letkf_index_build_f64(_ptr(obs), P, nc, cg, rc, len(radii), _ptr(ws), ws.numel(),
-                                                       self._stream()), "mia_letkf_index_build_f64")
-        return ObsIndex(ws, obs, radii, coord_group, P, nc)
+        per = _periods(period, nc)
+        if per is None:
+            _cabi.check(self.lib.mia_letkf_index_build_f64(_ptr(obs), P, nc, cg, rc, len(radii), _ptr(ws), ws.numel(),
+                                                           self._stream()), "mia_letkf_index_build_f64")
+        else:
+            _cabi.check(self.lib.mia_letkf_index_build_periodic_f64(_ptr(obs), P, nc, cg, per, rc, len(radii), _ptr(ws), ws.numel(),
+                                                                    self._stream()), "mia_letkf_index_build_periodic_f64")
+        return ObsIndex(ws, obs, radii, coord_group, P, nc, None if per is None else list(per))
 
     def analysis_fused(self, X: torch.Tensor, rec: torch.Tensor, grid_xyz, index: ObsIndex, p_max_assumed: int,
                        inf_factor: float = 1.0, eps: float = 1e-5, rbf_gamma: Optional[float] = None,
@@ -353,6 +386,8 @@ class LetkfEngine:
         X = X.to(self.device).contiguous()
         if X.dtype != torch.float32 or rec.dtype != torch.float32:
             raise TypeError("the fused matfun route is float32 only")
+        if index.period is not None:
+            raise _cabi.MiaError("the fused per-point route takes open coordinates: cyclic ones go through localize() or the step driver")
         m, k, G = X.shape
         grid = self._dev(grid_xyz, torch.float64)
         if grid.dim() == 1:

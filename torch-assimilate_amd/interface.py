@@ -302,14 +302,15 @@ class LETKF(ETKF):
         nc = 1 if grid.dim() == 1 else int(grid.shape[1])
         if grid.shape[0] != G or obs.shape[0] != yb.shape[1]:
             return None
+        per = loc.builtin_metric.periods(nc)          # (cyclic coordinates: part of the runner -- a change of period rebuilds it)
         key = (tuple(float(r) for r in loc.radius), tuple(loc.builtin_metric.groups(nc, len(loc.radius))), float(loc.epsilon),
-               float(self.inf_factor), ka.get("rbf_gamma"), nc)
+               float(self.inf_factor), ka.get("rbf_gamma"), nc, None if per is None else tuple(per))
         runner = getattr(self, "_step_runner", None)
         if runner is None or getattr(self, "_step_runner_key", None) != key:
             if runner is not None:
                 runner.close()
             runner = ShardedLetkf(self.engine.device, 0, 1, radii=list(key[0]), coord_group=list(key[1]), eps=key[2],
-                                  inf_factor=key[3], rbf_gamma=key[4])
+                                  inf_factor=key[3], rbf_gamma=key[4], period=per)
             runner._engine = self.engine
             self._step_runner, self._step_runner_key = runner, key
         dev = self.engine.device

@@ -3,7 +3,7 @@
 
 Constructor and ``localize_obs`` keep the reference's signature.  ``dist_func`` may be
 
-* one of the built-in metric descriptors below (``EuclideanMetric`` / ``AbsoluteDistance``):
+* one of the built-in metric descriptors below (``EuclideanMetric`` / ``AbsoluteDistance`` / ``PeriodicMetric``):
   then the whole localisation (distance, taper, mask, compaction) runs on the GPU through the
   cell index of csrc/localize.hip, O(G * local) instead of the reference's O(G * P);
 * any Python callable with the reference's contract ``dist_func(grid_ind, obs_grid) ->
@@ -18,7 +18,7 @@ from typing import Any, Callable, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-__all__ = ["GaspariCohn", "GaspariCohnInf", "EuclideanMetric", "AbsoluteDistance"]
+__all__ = ["GaspariCohn", "GaspariCohnInf", "EuclideanMetric", "AbsoluteDistance", "PeriodicMetric"]
 
 
 class EuclideanMetric:
@@ -33,6 +33,10 @@ class EuclideanMetric:
         if len(cg) != n_coord or max(cg) >= n_r:
             raise ValueError("coord_group does not match the coordinates / radii")
         return cg
+
+    def periods(self, n_coord: int):
+        """Period per coordinate for the GPU routes: None = every coordinate open."""
+        return None
 
     def __call__(self, grid_ind, obs_grid):     # host evaluation, same contract as the reference
         g = np.asarray(grid_ind, dtype=np.float64).reshape(-1)
@@ -52,6 +56,47 @@ class AbsoluteDistance(EuclideanMetric):
 
     def __init__(self):
         super().__init__([0])
+
+
+class PeriodicMetric(EuclideanMetric):
+    """Built-in metric with cyclic coordinates: coordinate c has period ``period[c]`` (> 0: cyclic, taken modulo the period, the
+    displacement is the minimum image ``d - L round(d / L)``; 0 or None: open).  ``period`` is a scalar (every coordinate) or one
+    entry per coordinate.  Radius groups as ``EuclideanMetric``.  A Lorenz-96 ring of N points: ``PeriodicMetric(N)``; a channel
+    cyclic in x: ``PeriodicMetric([Lx, 0])``.  ``__call__`` is the host statement of the distance; the GPU routes evaluate the
+    same distance in the cell index (csrc/localize.hip)."""
+
+    def __init__(self, period, coord_group: Optional[Sequence[int]] = None):
+        super().__init__(coord_group)
+        per = np.atleast_1d(np.asarray([0.0 if p is None else p for p in np.atleast_1d(np.asarray(period, dtype=object))],
+                                       dtype=np.float64))
+        if per.ndim != 1 or per.size == 0 or not np.all(np.isfinite(per)) or np.any(per < 0):
+            raise ValueError("period must be finite and >= 0 (0 / None = open coordinate)")
+        self.period = per
+        if self.coord_group is not None and per.size not in (1, len(self.coord_group)):
+            raise ValueError("period needs one entry per coordinate")
+
+    def periods(self, n_coord: int):
+        if self.period.size == 1:
+            return [float(self.period[0])] * n_coord
+        if self.period.size != n_coord:
+            raise ValueError("period needs one entry per coordinate (%d given, %d coordinates)" % (self.period.size, n_coord))
+        return [float(p) for p in self.period]
+
+    def __call__(self, grid_ind, obs_grid):     # host evaluation, same contract as the reference
+        g = np.asarray(grid_ind, dtype=np.float64).reshape(-1)
+        o = np.asarray(obs_grid, dtype=np.float64)
+        if o.ndim == 1:
+            o = o[:, None]
+        g = g[-o.shape[1]:]                       # tolerate the reference's leading time column
+        per = self.periods(o.shape[1])
+        cg = [0] * o.shape[1] if self.coord_group is None else self.coord_group
+        out = np.zeros((max(cg) + 1, o.shape[0]))
+        for c, grp in enumerate(cg):
+            dx = o[:, c] - g[c]
+            if per[c] > 0:
+                dx = dx - per[c] * np.round(dx / per[c])
+            out[grp] += dx ** 2
+        return tuple(np.sqrt(out))
 
 
 class GaspariCohn:
@@ -94,7 +139,7 @@ class GaspariCohn:
         if metric is not None:
             nc = 1 if np.ndim(grid_xyz) == 1 else np.shape(grid_xyz)[1]
             return engine.localize(grid_xyz, obs_xyz, list(self.radius), metric.groups(nc, len(self.radius)),
-                                   self.epsilon, g0, g1, taper=self._taper)
+                                   self.epsilon, g0, g1, taper=self._taper, period=metric.periods(nc))
         # arbitrary callable: evaluate on the host (user code), in chunks of grid points
         G = len(grid_xyz)
         g1 = G if g1 is None else g1
@@ -125,7 +170,7 @@ class GaspariCohn:
             return None
         nc = 1 if np.ndim(grid_xyz) == 1 else np.shape(grid_xyz)[1]
         return engine.localize_tiles(grid_xyz, obs_xyz, list(self.radius), p_max, metric.groups(nc, len(self.radius)),
-                                     self.epsilon, g0, g1, taper=self._taper, extra_blocks=extra_blocks)
+                                     self.epsilon, g0, g1, taper=self._taper, extra_blocks=extra_blocks, period=metric.periods(nc))
 
 
 class GaspariCohnInf(GaspariCohn):

@@ -233,9 +233,12 @@ class ShardedLetkf:
                  method: str = "auto", fused_localization: bool = False,
                  comm_chunks: int = 4, chunk_compute: Optional[Callable] = None, native_step: bool = True,
                  max_in_flight: int = 3, peer_exchange: str = "auto", copy_results: bool = True, prep_streams: int = 3,
-                 analysis_streams: int = 3, gather: bool = True, fuse_tile_lists="auto", prep_priority: int = 0):
+                 analysis_streams: int = 3, gather: bool = True, fuse_tile_lists="auto", prep_priority: int = 0, period=None):
         self.device, self.rank, self.world = device, rank, world
         self.radii, self.inf_factor, self.coord_group, self.eps = list(radii), inf_factor, coord_group, eps
+        # cyclic coordinates (PeriodicMetric): one period per coordinate or a scalar, > 0 = cyclic, 0 / None = open; every route
+        # of the runner -- the step's bucket / scan index, the redo of declined points, geometry epochs, the engine routes -- takes it
+        self.period = period
         self.rbf_gamma = rbf_gamma
         # gather=False (world > 1): assimilate() / submit() return THIS RANK'S BLOCK of the analysis, (m, k, g1 - g0) with
         # (g0, g1) = block_partition(G, world)[rank]: the analysis stays chunked along `grid`, as the reference's dask arrays do
@@ -302,15 +305,24 @@ class ShardedLetkf:
             self._engine = LetkfEngine(self.device)
         return self._engine
 
+    def _cyclic(self, nc: int = None):
+        """The period as the library takes it: a ctypes array of nc entries, or None when every coordinate is open."""
+        if self.period is None:
+            return None
+        from .engine import _periods
+        if nc is None:
+            nc = len(self.period) if hasattr(self.period, "__len__") else 1
+        return _periods(self.period, nc)
+
     def _engine_shard(self, X, grid_xyz, obs_xyz, Yb, d, g0, g1):
         eng = self.engine
-        fusable = (self.fused_localization and self.method != "eig" and self._p_max_hint is not None and X.dtype == torch.float32
+        fusable = (self.fused_localization and self.method != "eig" and self._cyclic() is None and self._p_max_hint is not None and X.dtype == torch.float32
                    and X.shape[0] <= eng.MATFUN_MAX_ROWS and len(obs_xyz) > 0)
         if fusable:
             # steady state: index build -> one fused kernel (localisation + analysis), then ONE host sync
             # that confirms the assumed list bound while the GPU is already busy / done
             rec = eng.pack_obs(Yb, d, X.dtype)
-            index = eng.build_index(obs_xyz, self.radii, self.coord_group)
+            index = eng.build_index(obs_xyz, self.radii, self.coord_group, period=self.period)
             xa, flags, finish = eng.analysis_fused(X, rec, grid_xyz, index, self._p_max_hint, self.inf_factor,
                                                    self.eps, self.rbf_gamma, g0, g1)
             ok, p_max, n_retry = finish()
@@ -324,7 +336,7 @@ class ShardedLetkf:
         # (Round 1 could replay this launch sequence from a HIP graph; the replay faulted after 15-50 replays, the cause
         #  was never isolated, and the one-call native step driver removed the launch overhead the graph was meant to hide:
         #  the path is gone, see DESIGN.md.)
-        nb = eng.localize(grid_xyz, obs_xyz, self.radii, self.coord_group, self.eps, g0, g1,
+        nb = eng.localize(grid_xyz, obs_xyz, self.radii, self.coord_group, self.eps, g0, g1, period=self.period,
                           assume_p_max=self._p_max_hint)
         if len(obs_xyz) > 0 and not self._no_tile_lists and torch.is_tensor(X):
             # the route the native step driver takes on this geometry (tile lists + split records): the entry-by-entry calls
@@ -336,7 +348,7 @@ class ShardedLetkf:
                                          return_flags=True, method=self.method, defer_retry=True)
         self._note_kernel()
         if not nb.confirm():
-            nb = eng.localize(grid_xyz, obs_xyz, self.radii, self.coord_group, self.eps, g0, g1)
+            nb = eng.localize(grid_xyz, obs_xyz, self.radii, self.coord_group, self.eps, g0, g1, period=self.period)
             xa, flags, finish = eng.analysis(X, Yb, d, nb, self.inf_factor, rbf_gamma=self.rbf_gamma,
                                              return_flags=True, method=self.method, defer_retry=True)
         self.last_retries = finish()
@@ -352,7 +364,7 @@ class ShardedLetkf:
         eng = self.engine
         P = int(Yb.shape[1])
         while eng.tile_route_applies(X, nb.p_max, self._tile_extra, self.rbf_gamma, self.method, P=P, n_points=g1 - g0):
-            tiles = eng.localize_tiles(grid_xyz, obs_xyz, self.radii, nb.p_max, self.coord_group, self.eps, g0, g1,
+            tiles = eng.localize_tiles(grid_xyz, obs_xyz, self.radii, nb.p_max, self.coord_group, self.eps, g0, g1, period=self.period,
                                        extra_blocks=self._tile_extra)
             n_over = int(tiles.stats[1].item())                 # host sync (first call on a geometry only)
             if n_over == 0:
@@ -377,7 +389,7 @@ class ShardedLetkf:
         n_retry = int(retry.item())
         if n_retry:
             if not nb.confirm():                                # (lists built on an assumed bound that did not hold)
-                nb = eng.localize(grid_xyz, obs_xyz, self.radii, self.coord_group, self.eps, g0, g1)
+                nb = eng.localize(grid_xyz, obs_xyz, self.radii, self.coord_group, self.eps, g0, g1, period=self.period)
             eng.retry_points(Xc, Yb, d, nb, self.inf_factor, xa, flags, rbf_gamma=self.rbf_gamma)
         self.last_retries = n_retry
         self._p_max_hint = max(int(tiles.stats[0].item()), 0)
@@ -721,6 +733,7 @@ class ShardedLetkf:
                 slot["ws"] = torch.empty(max(nbytes.value, 256), dtype=torch.uint8, device=X.device)
             cg = [0] * nc if self.coord_group is None else [int(c) for c in self.coord_group]
             slot["cg"] = (C.c_int32 * nc)(*cg)
+            slot["per"] = self._cyclic(nc)
             slot["rc"] = (C.c_double * len(self.radii))(*[float(r) for r in self.radii])
             slot["counters"] = torch.zeros(8, dtype=torch.int32, device=X.device)
             slot["host"] = torch.zeros(8, dtype=torch.int32).pin_memory()
@@ -744,7 +757,8 @@ class ShardedLetkf:
                 opts.append(v.value)
             geom_key = (geometry_id, key, self._tile_extra, self._scan_index, g0, g1, tuple(opts), self.method, self.rbf_gamma,
                         tuple(float(r) for r in self.radii), float(self.eps),
-                        None if self.coord_group is None else tuple(int(c) for c in self.coord_group))
+                        None if self.coord_group is None else tuple(int(c) for c in self.coord_group),
+                        None if slot["per"] is None else tuple(slot["per"]))
         reuse = (geom_key is not None and slot.get("geom") == geom_key and not self._no_tile_lists and not self._fresh_box_once
                  and C_chunks == 1 and st["comm"] is None)
         method = {"auto": 0, "eig": 1, "matfun": 2}[self.method]
@@ -796,11 +810,18 @@ class ShardedLetkf:
         def call(phase):
             # (plain integers for the pointer arguments: ctypes converts them itself, a C.c_void_p object per argument was a
             #  third of this function's host time)
-            rc = lib.mia_letkf_sharded_step_streams_f32(
-                X.data_ptr(), G, m, k, Yb.data_ptr(), d.data_ptr(), P, grid.data_ptr(), obs.data_ptr(), nc, slot["cg"],
-                slot["rc"], len(self.radii), eps, inf, gamma, method, hint, comm_arg,
-                C_chunks, phase, out.data_ptr(), flags.data_ptr(), slot["counters"].data_ptr(), slot["ws"].data_ptr(),
-                slot["ws"].numel(), comp.cuda_stream, side, prep.cuda_stream if prep is not None else None, step_flags)
+            if slot["per"] is not None:
+                rc = lib.mia_letkf_sharded_step_periodic_f32(
+                    X.data_ptr(), G, m, k, Yb.data_ptr(), d.data_ptr(), P, grid.data_ptr(), obs.data_ptr(), nc, slot["cg"], slot["per"],
+                    slot["rc"], len(self.radii), eps, inf, gamma, method, hint, comm_arg,
+                    C_chunks, phase, out.data_ptr(), flags.data_ptr(), slot["counters"].data_ptr(), slot["ws"].data_ptr(),
+                    slot["ws"].numel(), comp.cuda_stream, side, prep.cuda_stream if prep is not None else None, step_flags)
+            else:
+                rc = lib.mia_letkf_sharded_step_streams_f32(
+                    X.data_ptr(), G, m, k, Yb.data_ptr(), d.data_ptr(), P, grid.data_ptr(), obs.data_ptr(), nc, slot["cg"],
+                    slot["rc"], len(self.radii), eps, inf, gamma, method, hint, comm_arg,
+                    C_chunks, phase, out.data_ptr(), flags.data_ptr(), slot["counters"].data_ptr(), slot["ws"].data_ptr(),
+                    slot["ws"].numel(), comp.cuda_stream, side, prep.cuda_stream if prep is not None else None, step_flags)
             if rc != 0:
                 _cabi.check(rc, "mia_letkf_sharded_step_streams_f32")
 
@@ -832,6 +853,7 @@ class ShardedLetkf:
                 a.G, a.m, a.k, a.P, a.n_coord, a.n_r = G, m, k, P, nc, len(self.radii)
                 for i_ in range(nc):
                     a.coord_group[i_] = slot["cg"][i_]
+                    a.period[i_] = slot["per"][i_] if slot["per"] is not None else 0.0
                 for i_ in range(len(self.radii)):
                     a.gc_c[i_] = slot["rc"][i_]
                 a.flags, a.counters, a.ws, a.ws_bytes = flags.data_ptr(), slot["counters"].data_ptr(), slot["ws"].data_ptr(), slot["ws"].numel()
@@ -880,6 +902,7 @@ class ShardedLetkf:
                 a.G, a.m, a.k, a.P, a.n_coord, a.n_r = G, m, k, P, nc, len(self.radii)
                 for i_ in range(nc):
                     a.coord_group[i_] = slot["cg"][i_]
+                    a.period[i_] = slot["per"][i_] if slot["per"] is not None else 0.0
                 for i_ in range(len(self.radii)):
                     a.gc_c[i_] = slot["rc"][i_]
                 a.flags, a.counters, a.ws, a.ws_bytes = flags.data_ptr(), slot["counters"].data_ptr(), slot["ws"].data_ptr(), slot["ws"].numel()
@@ -915,7 +938,14 @@ class ShardedLetkf:
         lib = self.engine.lib
 
         def call(phase):
-            rc = lib.mia_letkf_sharded_step_streams_f32(a.X, a.G, a.m, a.k, a.Yb, a.d, a.P, a.grid_xyz, a.obs_xyz, a.n_coord, a.coord_group,
+            if any(a.period[i_] > 0.0 for i_ in range(a.n_coord)):
+                rc = lib.mia_letkf_sharded_step_periodic_f32(a.X, a.G, a.m, a.k, a.Yb, a.d, a.P, a.grid_xyz, a.obs_xyz, a.n_coord,
+                                                             a.coord_group, a.period, a.gc_c, a.n_r, a.gc_eps, a.inf_factor, a.gamma,
+                                                             a.method, a.p_max_assumed, a.comm, a.n_chunks, phase, a.Xa, a.flags,
+                                                             a.counters, a.ws, a.ws_bytes, a.stream, a.comm_stream, a.prep_stream,
+                                                             a.step_flags)
+            else:
+                rc = lib.mia_letkf_sharded_step_streams_f32(a.X, a.G, a.m, a.k, a.Yb, a.d, a.P, a.grid_xyz, a.obs_xyz, a.n_coord, a.coord_group,
                                                         a.gc_c, a.n_r, a.gc_eps, a.inf_factor, a.gamma, a.method, a.p_max_assumed, a.comm,
                                                         a.n_chunks, phase, a.Xa, a.flags, a.counters, a.ws, a.ws_bytes, a.stream,
                                                         a.comm_stream, a.prep_stream, a.step_flags)
@@ -1093,7 +1123,7 @@ class ShardedLetkf:
         vec = state["vec"]
         if "nb" not in state:
             state["rec"] = eng.pack_obs(Yb, d, X.dtype)
-            nb = eng.localize(grid_xyz, obs_xyz, self.radii, self.coord_group, self.eps, b0, b1,
+            nb = eng.localize(grid_xyz, obs_xyz, self.radii, self.coord_group, self.eps, b0, b1, period=self.period,
                               assume_p_max=self._p_max_hint, stats_out=vec[:2])
             if nb.stats is None:            # exact lists (first call on a geometry): publish their maximum
                 vec[:2].copy_(torch.tensor([nb.p_max, 0], dtype=torch.int32), non_blocking=True)
@@ -1309,12 +1339,12 @@ class ShardedLetkf:
             rec = None if rbf_tiles else (eng.pack_split(Yb, d) if tiles_route else eng.pack_obs(Yb, d, X.dtype))
             e[1].record()
             if fused:
-                index = eng.build_index(obs_xyz, self.radii, self.coord_group)
+                index = eng.build_index(obs_xyz, self.radii, self.coord_group, period=self.period)
                 e[2].record()
                 _, _, fin = eng.analysis_fused(X, rec, grid_xyz, index, self._p_max_hint, self.inf_factor, self.eps,
                                                self.rbf_gamma, g0, g1)
             elif tiles_route:
-                tiles = eng.localize_tiles(grid_xyz, obs_xyz, self.radii, self._p_max_hint, self.coord_group, self.eps, g0, g1,
+                tiles = eng.localize_tiles(grid_xyz, obs_xyz, self.radii, self._p_max_hint, self.coord_group, self.eps, g0, g1, period=self.period,
                                            extra_blocks=self._tile_extra)
                 torch.cuda.synchronize()          # (idle GPU in front of the burst, as on the list route)
                 out = torch.empty((X.shape[0], X.shape[1], g1 - g0), dtype=torch.float32, device=X.device)
@@ -1327,7 +1357,7 @@ class ShardedLetkf:
                 nk = burst
                 fin = lambda: 0
             else:
-                nb = eng.localize(grid_xyz, obs_xyz, self.radii, self.coord_group, self.eps, g0, g1)
+                nb = eng.localize(grid_xyz, obs_xyz, self.radii, self.coord_group, self.eps, g0, g1, period=self.period)
                 # the list step ends in a host read-back, so the GPU is idle here: launch the analysis kernel
                 # `burst` times back to back and divide, otherwise the interval between the two events measures
                 # the host's launch latency (~40 us from Python) on top of the kernel
