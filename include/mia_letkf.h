@@ -437,6 +437,10 @@ int mia_lketkf_kernel_analysis_packed_f64(const double* X, int64_t ldx, int m, i
  * Global (unlocalised) ETKF: one (k, P) solve, ETKF.estimate_weights
  * (interface/etkf.py:99-120) -> weights [k][k]; and the global ensemble transform
  * _apply_weights with 2-D weights (base.py:257-278).
+ * Ensemble size 2 <= k <= 256 on every entry of this block, any P >= 0; k > 256 returns
+ * MIA_ERR_UNSUPPORTED.  P = 0 returns the inflated prior sqrt(inf) I (core/etkf.py:91-95).
+ * flags_opt (one int32 on the device, may be NULL): 0, or MIA_FLAG_NOCONV when the Jacobi
+ * eigensolver reached its sweep cap (the weights are still written).
  * ---------------------------------------------------------------------------------- */
 int mia_etkf_workspace_bytes(int k, int64_t P, int elem_bytes, size_t* bytes);
 int mia_etkf_weights_f32(const float* Yb, const float* d, int k, int64_t P, float inf_factor,

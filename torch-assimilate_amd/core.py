@@ -12,7 +12,7 @@ from typing import Optional
 
 import torch
 
-from .engine import LetkfEngine
+from .engine import LetkfEngine, warn_if_noconv
 from .kernels import kernel_route
 
 __all__ = ["ETKFModule", "KETKFModule"]
@@ -105,7 +105,9 @@ class KETKFModule(ETKFModule):
                     len(scale), perts.shape[-1]))
             sc = torch.as_tensor(scale, device=eng.device, dtype=dtype)
             perts, obs = perts * sc, obs * sc
-        return eng.ketkf_weights(perts, obs, prog, self.inf_factor)
+        W, flags = eng.ketkf_weights(perts, obs, prog, self.inf_factor, return_flags=True)
+        warn_if_noconv(flags, "KETKF")
+        return W
 
     forward = __call__
 

@@ -23,10 +23,21 @@ template <typename T> __device__ inline T t_sin(T x);
 template <> __device__ inline float t_sin<float>(float x) { return sinf(x); }
 template <> __device__ inline double t_sin<double>(double x) { return sin(x); }
 
-// Parallel cyclic Jacobi on the n x n symmetric matrix A (LDS, leading dim lda), n even.
+// Workgroup barrier.  GMEM: the caller also shares data through global memory.  The waves of one
+// workgroup run on one CU and share its vector L1, so the compiler's __syncthreads (a bare s_barrier
+// on gfx950) already orders such stores and loads; the vmcnt(0) wait before it makes every wave's
+// stores complete before any wave passes, independent of that property.
+template <bool GMEM>
+__device__ inline void wg_sync() {
+  if (GMEM) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+}
+
+// Parallel cyclic Jacobi on the n x n symmetric matrix A (leading dim lda), n even.
 // V (nv rows) accumulates the rotations: A_in = V A_out V^T.  Returns true when a sweep
-// needed no rotation.  Must be called by all NT threads of the workgroup.
-template <typename T, int NT>
+// needed no rotation.  Must be called by all NT threads of the workgroup.  cs and iflag are
+// LDS; A and V are LDS, or global memory with GMEM.
+template <typename T, int NT, bool GMEM = false>
 __device__ bool jacobi_lds(T* A, T* V, T* cs, int* iflag, int n, int nv, int lda, T shift,
                            T tol, int max_sweeps) {
   const int tid = threadIdx.x;
@@ -38,7 +49,7 @@ __device__ bool jacobi_lds(T* A, T* V, T* cs, int* iflag, int n, int nv, int lda
     // (the barrier inside the first round orders this store before any flag update)
     for (int r = 0; r < n - 1; ++r) {
       // --- rotation parameters, one pair per thread
-      __syncthreads();
+      wg_sync<GMEM>();
       for (int i = tid; i < nb; i += NT) {
         int p, q;
         if (i == 0) { p = r; q = n - 1; }
@@ -56,7 +67,7 @@ __device__ bool jacobi_lds(T* A, T* V, T* cs, int* iflag, int n, int nv, int lda
         }
         cs[2 * i] = c; cs[2 * i + 1] = s;
       }
-      __syncthreads();
+      wg_sync<GMEM>();
       // --- A <- J^T A J, one 2x2 block per work item
       for (int it = tid; it < nb * nb; it += NT) {
         const int bi = it / nb, bj = it - bi * nb;
@@ -90,10 +101,10 @@ __device__ bool jacobi_lds(T* A, T* V, T* cs, int* iflag, int n, int nv, int lda
         V[row * lda + q2] = s2 * v0 + c2 * v1;
       }
     }
-    __syncthreads();
+    wg_sync<GMEM>();
     if (iflag[sweep & 1] == 0) { converged = true; break; }
   }
-  __syncthreads();
+  wg_sync<GMEM>();
   return converged;
 }
 

@@ -6,6 +6,7 @@ torch is plumbing here (device memory, streams); nothing in this file computes.
 from __future__ import annotations
 
 import ctypes as C
+import warnings
 from dataclasses import dataclass
 from typing import Optional, Sequence
 
@@ -18,6 +19,20 @@ __all__ = ["LetkfEngine", "NeighbourLists", "ObsIndex"]
 
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+MIA_FLAG_NOCONV = 2     # include/mia_letkf.h
+
+
+def _read_solve_flags(flags: torch.Tensor) -> int:
+    """The flag word of a global solve (etkf_weights / ketkf_weights with return_flags=True) on the host: one sync."""
+    return int(flags[0].item())
+
+
+def warn_if_noconv(flags: torch.Tensor, what: str) -> None:
+    """RuntimeWarning when a global solve's eigensolver reached its sweep cap (its weights are still returned)."""
+    if _read_solve_flags(flags) & MIA_FLAG_NOCONV:
+        warnings.warn(what + " eigensolver reached its sweep cap (result returned)", RuntimeWarning)
 
 
 @dataclass
@@ -746,7 +761,10 @@ class LetkfEngine:
         return out
 
     # ------------------------------------------------------------- global ETKF
-    def etkf_weights(self, Yb: torch.Tensor, d: torch.Tensor, inf_factor: float = 1.0) -> torch.Tensor:
+    def etkf_weights(self, Yb: torch.Tensor, d: torch.Tensor, inf_factor: float = 1.0, return_flags: bool = False):
+        """Global ETKF weights (k, k) (ETKFModule on the full block, core/etkf.py:79-103), 2 <= k <= 256
+        (mia_etkf_weights_*).  ``return_flags``: also return the int32 flag word of the solve (one entry on the
+        device; MIA_FLAG_NOCONV when the eigensolver reached its sweep cap)."""
         Yb = Yb.to(self.device).contiguous()
         dtype = Yb.dtype
         d = d.to(device=self.device, dtype=dtype).contiguous().reshape(-1)
@@ -765,11 +783,13 @@ class LetkfEngine:
         fn = getattr(self.lib, "mia_etkf_weights_" + sfx)
         _cabi.check(fn(_ptr(Yb), _ptr(d), k, P, float(inf_factor), _ptr(W), _ptr(flags), _ptr(ws), ws.numel(),
                        self._stream()), "mia_etkf_weights_" + sfx)
-        return W
+        return (W, flags) if return_flags else W
 
-    def ketkf_weights(self, Yb: torch.Tensor, d: torch.Tensor, kernel_program, inf_factor: float = 1.0) -> torch.Tensor:
-        """Global kernelised ETKF weights (k, k) for ANY number of observations (KETKFModule on the full block,
-        core/ketkf.py:65-94): pair statistics accumulated over observation chunks, then one k x k solve."""
+    def ketkf_weights(self, Yb: torch.Tensor, d: torch.Tensor, kernel_program, inf_factor: float = 1.0,
+                      return_flags: bool = False):
+        """Global kernelised ETKF weights (k, k) for ANY number of observations and 2 <= k <= 256 (KETKFModule on the
+        full block, core/ketkf.py:65-94): pair statistics accumulated over observation chunks, then one k x k solve.
+        ``return_flags`` as in :meth:`etkf_weights`."""
         Yb = Yb.to(self.device).contiguous()
         dtype = Yb.dtype if Yb.dtype in (torch.float32, torch.float64) else torch.float64
         Yb = Yb.to(dtype)
@@ -793,7 +813,7 @@ class LetkfEngine:
         fn = getattr(self.lib, "mia_ketkf_weights_" + sfx)
         _cabi.check(fn(_ptr(Yb), _ptr(d), k, P, float(inf_factor), prog, nops, _ptr(W), _ptr(flags), _ptr(ws), ws.numel(),
                        self._stream()), "mia_ketkf_weights_" + sfx)
-        return W
+        return (W, flags) if return_flags else W
 
     def apply_weights(self, X: torch.Tensor, W: torch.Tensor, g0: int = 0, g1: Optional[int] = None) -> torch.Tensor:
         if X.dim() == 2:

@@ -27,7 +27,7 @@ from typing import Callable, Iterable, List, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from .engine import LetkfEngine
+from .engine import LetkfEngine, warn_if_noconv
 from .kernels import kernel_route
 from .localization import GaspariCohn
 
@@ -110,7 +110,9 @@ class ETKF:
         if any(v is not None for v in self._kernel_args().values()):     # kernelised global solve: one "grid point" seeing every observation
             from .core import KETKFModule
             return KETKFModule(self._kernel, self.inf_factor, self.engine)(self._dev(yb), self._dev(d))
-        return self.engine.etkf_weights(self._dev(yb), self._dev(d), self.inf_factor)
+        W, flags = self.engine.etkf_weights(self._dev(yb), self._dev(d), self.inf_factor, return_flags=True)
+        warn_if_noconv(flags, "ETKF")
+        return W
 
     def get_obs_space_variables(self, ens_obs, observations, variances=None, covariances=None):
         """Array-level ``_get_obs_space_variables`` (interface/base.py:359-379) on the device: for every
