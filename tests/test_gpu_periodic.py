@@ -318,3 +318,72 @@ def test_no_host_distance_calls(mia, monkeypatch):
         pts = [0, 1, 5, G - 3, G - 1, 200]
         ref = oracle_points(case, L, c, 1.1, pts)
         assert rel_fro(xa.cpu().numpy().astype(np.float64)[:, :, pts], ref) <= 1e-5
+
+
+def _lists_at(eng, grid, obs, radii, groups, taper, period, cap, quad=True):
+    """per-point lists of one route: cap 32 = quad kernel (thread kernel with quad False), cap 64 = wave kernel"""
+    from torch_assimilate_amd import _cabi
+    old = _cabi.set_option("localize_quad", 1 if quad else 0)
+    try:
+        nb = eng.localize(grid, obs, radii, groups, taper=taper, period=period, assume_p_max=cap)
+        torch.cuda.synchronize()
+    finally:
+        _cabi.set_option("localize_quad", old)
+    assert nb.p_cap == cap
+    return nb.cnt.cpu().numpy(), nb.idx.cpu().numpy(), nb.w.cpu().numpy()
+
+
+def _open_entry_lists(eng, grid, obs, radii, groups, cap):
+    """the same through the open C entry (mia_letkf_localize_taper_f64), which the engine no longer calls"""
+    import ctypes as C
+    from torch_assimilate_amd import _cabi
+    lib = _cabi.lib()
+    g = torch.as_tensor(grid, dtype=torch.float64, device=DEV).contiguous()
+    o = torch.as_tensor(obs, dtype=torch.float64, device=DEV).contiguous()
+    G, nc = g.shape
+    P = o.shape[0]
+    nbytes = C.c_size_t(0)
+    assert lib.mia_letkf_localize_workspace_bytes(P, nc, C.byref(nbytes)) == 0
+    ws = torch.empty(max(nbytes.value, 256), dtype=torch.uint8, device=DEV)
+    cnt = torch.empty(G, dtype=torch.int32, device=DEV)
+    idx = torch.empty((G, cap), dtype=torch.int32, device=DEV)
+    w = torch.empty((G, cap), dtype=torch.float64, device=DEV)
+    stats = torch.empty(2, dtype=torch.int32, device=DEV)
+    torch.cuda.synchronize()
+    rc = lib.mia_letkf_localize_taper_f64(0, g.data_ptr(), 0, G, o.data_ptr(), P, nc, (C.c_int32 * nc)(*groups),
+                                          (C.c_double * len(radii))(*radii), len(radii), 1e-5, cap, cnt.data_ptr(), idx.data_ptr(),
+                                          w.data_ptr(), stats.data_ptr(), ws.data_ptr(), ws.numel(), None)
+    assert rc == 0
+    torch.cuda.synchronize()
+    return cnt.cpu().numpy(), idx.cpu().numpy(), w.cpu().numpy()
+
+
+def _assert_lists_bitwise(a, b, cap):
+    """cnt equal; the first cap entries of idx and w equal bit for bit"""
+    assert np.array_equal(a[0], b[0])
+    assert np.array_equal(a[1][:, :cap], b[1][:, :cap])
+    assert np.array_equal(a[2][:, :cap].view(np.int64), b[2][:, :cap].view(np.int64))
+
+
+OPEN_2D = "open_2d"
+
+
+@pytest.mark.parametrize("name", GEOMS + [OPEN_2D])
+def test_point_lists_bitwise_equal_across_routes(mia, eng, name):
+    """Thread, quad and wave kernels give the same per-point lists bit for bit (the wave kernel's cyclic instantiation included);
+    on an open geometry the periodic entry with an all-zero period gives what the open entry gives."""
+    if name == OPEN_2D:
+        rs = np.random.default_rng(7)
+        grid, obs, period, radii, groups, taper = (mesh(np.arange(20.0), np.arange(20.0)), rs.uniform(0, 20, (150, 2)), None, [2.0],
+                                                   [0, 0], 0)
+    else:
+        grid, obs, period, radii, groups, taper = geometry(name)
+    thread = _lists_at(eng, grid, obs, radii, groups, taper, period, 32, quad=False)
+    quad = _lists_at(eng, grid, obs, radii, groups, taper, period, 32)
+    wave = _lists_at(eng, grid, obs, radii, groups, taper, period, 64)
+    assert thread[0].sum() > 0
+    _assert_lists_bitwise(thread, quad, 32)
+    _assert_lists_bitwise(quad, wave, 32)
+    if name == OPEN_2D:
+        for cap, lists in ((32, quad), (64, wave)):
+            _assert_lists_bitwise(_open_entry_lists(eng, grid, obs, radii, groups, cap), lists, cap)

@@ -364,7 +364,7 @@ struct LocalizeParams {
 // (~30 candidates x ~50 float64 operations) runs with all lanes busy.
 // (106 VGPRs.  Capping it at 80, so that ONE retiring wave of a co-running analysis kernel -- 7 x 72 registers per
 //  SIMD -- makes room, cost 24 spilled registers and gained nothing: 68 us beside the analysis kernel either way)
-// PER: the index has cyclic coordinates (cyc_window_seg / cyc_disp); the open instantiation is the kernel as it was.
+// PER: the index has cyclic coordinates (point_coord / MIA_WINDOW_RANGE / point_disp, mia_localize_dev.h).
 template <bool PER>
 __global__ __launch_bounds__(64) void localize_kernel(LocalizeParams p) {
   MIA_PREP_PRIORITY();
@@ -379,41 +379,15 @@ __global__ __launch_bounds__(64) void localize_kernel(LocalizeParams p) {
     int cg[MIA_MAX_COORD];
     for (int c = 0; c < MIA_MAX_COORD; ++c) { gx[c] = 0.0; cg[c] = 0; }
     for (int c = 0; c < nc; ++c) {
-      gx[c] = q.grid[(p.g0 + pt) * nc + c];
-      if constexpr (PER) point_cell(h, c, gx[c], &gx[c], &cg[c]);
-      else cg[c] = cell_coord(gx[c], h->mn[c], h->invh[c], h->n[c]);
+      point_coord<PER>(h, c, q.grid[(p.g0 + pt) * nc + c], &gx[c], &cg[c]);
     }
     int* my_idx = p.idx + pt * p.p_cap;
     double* my_w = p.w + pt * p.p_cap;
-    const int n_outer = nc == 1 ? 1 : (nc == 2 ? 3 : 9);
-    const int last = nc - 1;
-    int lo_l = cg[last] - 1, hi_l = cg[last] + 1;
-    lo_l = lo_l < 0 ? 0 : lo_l;
-    hi_l = hi_l > h->n[last] - 1 ? h->n[last] - 1 : hi_l;
-    for (int o = 0; o < n_outer * (PER ? 2 : 1); ++o) {
+    MIA_WINDOW_BEGIN(PER, h, nc, cg);
+    for (int o = 0; o < n_steps; ++o) {
       int beg, end;
       CycSeg sg;
-      if constexpr (PER) {
-        if (!cyc_window_seg(h, nc, cg, o >> 1, o & 1, sg)) continue;
-        beg = q.start[sg.c_lo]; end = q.start[sg.c_hi + 1];
-      } else {
-      int base_cell = 0;
-      bool ok = lo_l <= hi_l;
-      if (nc >= 2) {
-        const int d0 = (nc == 2) ? (o - 1) : (o / 3 - 1);
-        const int c0 = cg[0] + d0;
-        ok = ok && c0 >= 0 && c0 < h->n[0];
-        base_cell = c0;
-        if (nc == 3) {
-          const int c1 = cg[1] + (o % 3 - 1);
-          ok = ok && c1 >= 0 && c1 < h->n[1];
-          base_cell = base_cell * h->n[1] + c1;
-        }
-        base_cell *= h->n[last];
-      }
-      if (!ok) continue;
-      beg = q.start[base_cell + lo_l]; end = q.start[base_cell + hi_l + 1];
-      }
+      MIA_WINDOW_RANGE(PER, h, q.start, nc, cg, o, sg, beg, end)
       // four candidates per trip: their (independent) loads are issued together, so the ~1.5 us memory
       // latency is paid once per four candidates instead of once per candidate
       for (int pos0 = beg; pos0 < end; pos0 += 4) {
@@ -425,9 +399,7 @@ __global__ __launch_bounds__(64) void localize_kernel(LocalizeParams p) {
           oj[u] = q.sorted[pos];
           double d2[MIA_MAX_RADII] = {0.0, 0.0, 0.0};
           for (int c = 0; c < nc; ++c) {
-            double dx;
-            if constexpr (PER) dx = cyc_disp(q.sxyz[(int64_t)pos * nc + c], gx[c], sg.s[c], (sg.pw >> c) & 1u, h->period[c], h->inv_period[c]);
-            else dx = q.sxyz[(int64_t)pos * nc + c] - gx[c];
+            const double dx = point_disp<PER>(h, sg, c, q.sxyz[(int64_t)pos * nc + c], gx[c]);
             d2[q.group[c]] += dx * dx;
           }
           double wgt = 1.0;
@@ -477,41 +449,15 @@ __global__ __launch_bounds__(64) void localize_quad_kernel(LocalizeParams p) {
     int cg[MIA_MAX_COORD];
     for (int c = 0; c < MIA_MAX_COORD; ++c) { gx[c] = 0.0; cg[c] = 0; }
     for (int c = 0; c < nc; ++c) {
-      gx[c] = q.grid[(p.g0 + pt) * nc + c];
-      if constexpr (PER) point_cell(h, c, gx[c], &gx[c], &cg[c]);
-      else cg[c] = cell_coord(gx[c], h->mn[c], h->invh[c], h->n[c]);
+      point_coord<PER>(h, c, q.grid[(p.g0 + pt) * nc + c], &gx[c], &cg[c]);
     }
     int* my_idx = p.idx + pt * p.p_cap;
     double* my_w = p.w + pt * p.p_cap;
-    const int n_outer = nc == 1 ? 1 : (nc == 2 ? 3 : 9);
-    const int last = nc - 1;
-    int lo_l = cg[last] - 1, hi_l = cg[last] + 1;
-    lo_l = lo_l < 0 ? 0 : lo_l;
-    hi_l = hi_l > h->n[last] - 1 ? h->n[last] - 1 : hi_l;
-    for (int o = 0; o < n_outer * (PER ? 2 : 1); ++o) {
+    MIA_WINDOW_BEGIN(PER, h, nc, cg);
+    for (int o = 0; o < n_steps; ++o) {
       int beg, end;
       CycSeg sg;
-      if constexpr (PER) {
-        if (!cyc_window_seg(h, nc, cg, o >> 1, o & 1, sg)) continue;
-        beg = q.start[sg.c_lo]; end = q.start[sg.c_hi + 1];
-      } else {
-      int base_cell = 0;
-      bool ok = lo_l <= hi_l;
-      if (nc >= 2) {
-        const int d0 = (nc == 2) ? (o - 1) : (o / 3 - 1);
-        const int c0 = cg[0] + d0;
-        ok = ok && c0 >= 0 && c0 < h->n[0];
-        base_cell = c0;
-        if (nc == 3) {
-          const int c1 = cg[1] + (o % 3 - 1);
-          ok = ok && c1 >= 0 && c1 < h->n[1];
-          base_cell = base_cell * h->n[1] + c1;
-        }
-        base_cell *= h->n[last];
-      }
-      if (!ok) continue;
-      beg = q.start[base_cell + lo_l]; end = q.start[base_cell + hi_l + 1];
-      }
+      MIA_WINDOW_RANGE(PER, h, q.start, nc, cg, o, sg, beg, end)
       // two candidates per lane and trip (positions pos0 + sub and pos0 + 4 + sub: their loads are requested together,
       // half as many dependent memory round trips per point); the survivors of the first four positions are placed
       // before those of the second four, i.e. still in position order
@@ -526,9 +472,7 @@ __global__ __launch_bounds__(64) void localize_quad_kernel(LocalizeParams p) {
           oj[u] = q.sorted[pos];
           double d2[MIA_MAX_RADII] = {0.0, 0.0, 0.0};
           for (int c = 0; c < nc; ++c) {
-            double dx;
-            if constexpr (PER) dx = cyc_disp(q.sxyz[(int64_t)pos * nc + c], gx[c], sg.s[c], (sg.pw >> c) & 1u, h->period[c], h->inv_period[c]);
-            else dx = q.sxyz[(int64_t)pos * nc + c] - gx[c];
+            const double dx = point_disp<PER>(h, sg, c, q.sxyz[(int64_t)pos * nc + c], gx[c]);
             d2[q.group[c]] += dx * dx;
           }
           wgt[u] = 1.0;
@@ -646,13 +590,13 @@ static int taper_launch(const T* r, int64_t n, T* w, hipStream_t stream) {
   return MIA_OK;
 }
 
-int check_period(const double* period, int n_coord, bool* cyclic) {
-  *cyclic = false;
-  if (!period) return MIA_OK;
-  for (int c = 0; c < n_coord; ++c) {
+int check_period(const double* period, int n_coord, const double** out) {
+  bool cyclic = false;
+  for (int c = 0; period && c < n_coord; ++c) {
     if (!(period[c] >= 0.0) || !(period[c] < __builtin_inf())) return MIA_ERR_ARG;      // (NaN, negative, infinite)
-    *cyclic = *cyclic || period[c] > 0.0;
+    cyclic = cyclic || period[c] > 0.0;
   }
+  *out = cyclic ? period : nullptr;
   return MIA_OK;
 }
 
@@ -665,8 +609,6 @@ int index_build_impl(const double* obs_xyz, int64_t P, int n_coord, const int32_
   if (!coord_group || !gc_c) return MIA_ERR_NULL;
   for (int c = 0; c < n_coord; ++c) if (coord_group[c] < 0 || coord_group[c] >= n_r) return MIA_ERR_SIZE;
   for (int r = 0; r < n_r; ++r) if (!(gc_c[r] > 0.0)) return MIA_ERR_SIZE;
-  bool cyclic = false;
-  if (check_period(period, n_coord, &cyclic) != MIA_OK) return MIA_ERR_ARG;
   if (P == 0) return MIA_OK;
   if (!obs_xyz || !ws) return MIA_ERR_NULL;
   if (((uintptr_t)ws) & 255) return MIA_ERR_ALIGN;
@@ -678,8 +620,12 @@ int index_build_impl(const double* obs_xyz, int64_t P, int n_coord, const int32_
   ip.hdr = L.hdr; ip.start = L.start; ip.cursor = L.cursor; ip.sorted = L.sorted; ip.cell_of = L.cell_of; ip.rank_of = L.rank_of;
   ip.sxyz = L.sxyz;
   ip.bucket_total = (long long)L.bucket_total; ip.bidx = L.bidx; ip.bxyz = L.bxyz;
-  for (int c = 0; c < MIA_MAX_COORD; ++c) ip.period[c] = (cyclic && c < n_coord) ? period[c] : 0.0;
-  ip.periodic = cyclic ? 1 : 0;
+  for (int c = 0; c < MIA_MAX_COORD; ++c) ip.period[c] = (period && c < n_coord) ? period[c] : 0.0;
+  ip.periodic = period ? 1 : 0;
+  // (the binning kernels' PER instantiations where some coordinate is cyclic)
+  void (*count_k)(IndexParams) = period ? index_count_kernel<true> : index_count_kernel<false>;
+  void (*scatter_k)(IndexParams) = period ? index_scatter_kernel<true> : index_scatter_kernel<false>;
+  void (*sortcell_k)(IndexParams) = period ? index_sortcell_kernel<true> : index_sortcell_kernel<false>;
   // SINGLE-WAVE workgroups throughout the chain: when steps are pipelined these kernels run beside the previous step's
   // analysis kernel, which fills every SIMD's register file (7 waves x 72 VGPRs at C2).  A lone wave takes the slot of
   // the next analysis wave that retires; a 4-wave workgroup needs one to retire on each SIMD of one CU at the same
@@ -711,19 +657,16 @@ int index_build_impl(const double* obs_xyz, int64_t P, int n_coord, const int32_
   const size_t pack_lds = nb_pack ? (size_t)64 * (ip.pack.kp + 1) * sizeof(float) : 0;      // (kp <= 132: 34 KB)
   index_bbox_dims_kernel<<<dim3(ip.nb_bbox + nb_pack), dim3(kPrepThreads), pack_lds, stream>>>(ip);
   MIA_LAUNCH_CHECK();
-  if (cyclic) index_count_kernel<true><<<dim3(nbP), dim3(kPrepThreads), 0, stream>>>(ip);
-  else index_count_kernel<false><<<dim3(nbP), dim3(kPrepThreads), 0, stream>>>(ip);
+  count_k<<<dim3(nbP), dim3(kPrepThreads), 0, stream>>>(ip);
   MIA_LAUNCH_CHECK();
   index_scan_kernel<<<dim3(1), dim3(64), 0, stream>>>(ip);
   MIA_LAUNCH_CHECK();
   ip.scatter_xyz = sort_cells ? 0 : 1;
-  if (cyclic) index_scatter_kernel<true><<<dim3(nbP), dim3(kPrepThreads), 0, stream>>>(ip);
-  else index_scatter_kernel<false><<<dim3(nbP), dim3(kPrepThreads), 0, stream>>>(ip);
+  scatter_k<<<dim3(nbP), dim3(kPrepThreads), 0, stream>>>(ip);
   MIA_LAUNCH_CHECK();
   if (!sort_cells) return MIA_OK;      // (lazy sort: the scatter has laid the coordinates out; see sort_flagged_lists_kernel)
   const size_t sort_blocks = L.cap < 8192 ? (L.cap ? L.cap : 1) : 8192;      // one wave (cell) per workgroup
-  if (cyclic) index_sortcell_kernel<true><<<dim3((unsigned)sort_blocks), dim3(kPrepThreads), 0, stream>>>(ip);
-  else index_sortcell_kernel<false><<<dim3((unsigned)sort_blocks), dim3(kPrepThreads), 0, stream>>>(ip);
+  sortcell_k<<<dim3((unsigned)sort_blocks), dim3(kPrepThreads), 0, stream>>>(ip);
   MIA_LAUNCH_CHECK();
   return MIA_OK;
 }
@@ -802,13 +745,12 @@ int index_bucket_build_impl(const double* obs_xyz, int64_t P, int n_coord, const
   if (P <= 0 || n_coord < 1 || n_coord > MIA_MAX_COORD || n_r < 1 || n_r > MIA_MAX_RADII) return MIA_ERR_SIZE;
   if (P > 500000000LL) return MIA_ERR_UNSUPPORTED;
   if (!coord_group || !gc_c || !obs_xyz || !ws) return MIA_ERR_NULL;
-  bool cyclic = false;
-  if (check_period(period, n_coord, &cyclic) != MIA_OK) return MIA_ERR_ARG;
   const IndexLayout L = index_layout(ws, P, n_coord);
   if (ws_bytes < L.bytes) return MIA_ERR_WORKSPACE;
   IndexParams ip;
-  for (int c = 0; c < MIA_MAX_COORD; ++c) ip.period[c] = (cyclic && c < n_coord) ? period[c] : 0.0;
-  ip.periodic = cyclic ? 1 : 0;
+  for (int c = 0; c < MIA_MAX_COORD; ++c) ip.period[c] = (period && c < n_coord) ? period[c] : 0.0;
+  ip.periodic = period ? 1 : 0;
+  void (*bucket_k)(IndexParams) = period ? index_bucket_kernel<true> : index_bucket_kernel<false>;
   ip.obs = obs_xyz; ip.P = P; ip.nc = n_coord; ip.cell_cap = (int)L.cap;
   for (int c = 0; c < MIA_MAX_COORD; ++c) ip.cutoff[c] = c < n_coord ? 2.0 * gc_c[coord_group[c]] : 1.0;
   ip.hdr = L.hdr; ip.start = L.start; ip.cursor = L.cursor; ip.sorted = L.sorted; ip.cell_of = L.cell_of; ip.rank_of = L.rank_of;
@@ -840,13 +782,9 @@ int index_bucket_build_impl(const double* obs_xyz, int64_t P, int n_coord, const
     nb = (unsigned)((P + 1 + 63) / 64);      // (record P is the all-zero record)
     lds = split_pack_lean_lds(spack->k);
     if (lds > kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
-    if (lds > 48 * 1024) {
-      MIA_HIP_TRY(hipFuncSetAttribute((const void*)index_bucket_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      MIA_HIP_TRY(hipFuncSetAttribute((const void*)index_bucket_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
+    if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)bucket_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   }
-  if (cyclic) index_bucket_kernel<true><<<dim3(nb), dim3(kPrepThreads), lds, stream>>>(ip);
-  else index_bucket_kernel<false><<<dim3(nb), dim3(kPrepThreads), lds, stream>>>(ip);
+  bucket_k<<<dim3(nb), dim3(kPrepThreads), lds, stream>>>(ip);
   MIA_LAUNCH_CHECK();
   return MIA_OK;
 }
@@ -883,8 +821,6 @@ int localize_impl(const double* grid_xyz, int64_t g0, int64_t g1, const double* 
   if (!coord_group || !gc_c || !stats) return MIA_ERR_NULL;
   for (int c = 0; c < n_coord; ++c) if (coord_group[c] < 0 || coord_group[c] >= n_r) return MIA_ERR_SIZE;
   for (int r = 0; r < n_r; ++r) if (!(gc_c[r] > 0.0)) return MIA_ERR_SIZE;
-  bool cyclic = false;
-  if (check_period(period, n_coord, &cyclic) != MIA_OK) return MIA_ERR_ARG;
   const int64_t ng = g1 - g0;
   if (!stats_zeroed) MIA_HIP_TRY(hipMemsetAsync(stats, 0, 2 * sizeof(int32_t), stream));
   if (ng == 0) return MIA_OK;
@@ -902,7 +838,7 @@ int localize_impl(const double* grid_xyz, int64_t g0, int64_t g1, const double* 
                             zero, header_clean, sort_cells, period);
   if (rc != MIA_OK) return rc;
   return localize_lists_impl(grid_xyz, g0, g1, P, n_coord, coord_group, gc_c, n_r, gc_eps, p_cap, nbr_cnt, nbr_idx, nbr_w, stats, ws,
-                             stream, MIA_PACK_IN_LOCALIZE ? pack : nullptr, taper, cyclic);
+                             stream, MIA_PACK_IN_LOCALIZE ? pack : nullptr, taper, period);
 }
 
 // neighbour lists of grid points [g0, g1) over an index that already exists in `ws` (second half of localize_impl; the
@@ -910,7 +846,7 @@ int localize_impl(const double* grid_xyz, int64_t g0, int64_t g1, const double* 
 int localize_lists_impl(const double* grid_xyz, int64_t g0, int64_t g1, int64_t P, int n_coord, const int32_t* coord_group,
                         const double* gc_c, int n_r, double gc_eps, int p_cap, int32_t* nbr_cnt, int32_t* nbr_idx,
                         double* nbr_w, int32_t* stats, void* ws, hipStream_t stream, const PackJob* pack, int taper,
-                        bool periodic) {
+                        const double* period) {
   const int64_t ng = g1 - g0;
   if (ng <= 0 || P <= 0) return MIA_OK;
   int rc;
@@ -933,8 +869,7 @@ int localize_lists_impl(const double* grid_xyz, int64_t g0, int64_t g1, int64_t 
   if (p_cap >= 64 && ng <= 2147483647LL && !MIA_EXP_FLAG("MIA_LOCALIZE_THREAD")) {   // long lists: one wavefront per grid point
     if (ng + nb_pack > 2147483647LL) return MIA_ERR_UNSUPPORTED;
     lp.nb_main = (unsigned)ng;
-    if (periodic) localize_wave_kernel<true><<<dim3((unsigned)ng + nb_pack), dim3(64), pack_lds, stream>>>(lp);
-    else localize_wave_kernel<false><<<dim3((unsigned)ng + nb_pack), dim3(64), pack_lds, stream>>>(lp);
+    (period ? localize_wave_kernel<true> : localize_wave_kernel<false>)<<<dim3((unsigned)ng + nb_pack), dim3(64), pack_lds, stream>>>(lp);
     MIA_LAUNCH_CHECK();
     return MIA_OK;
   }
@@ -945,16 +880,14 @@ int localize_lists_impl(const double* grid_xyz, int64_t g0, int64_t g1, int64_t 
     const int64_t nbq = (ng + 15) / 16;
     if (nbq + nb_pack > 2147483647LL) return MIA_ERR_UNSUPPORTED;
     lp.nb_main = (unsigned)nbq;
-    if (periodic) localize_quad_kernel<true><<<dim3((unsigned)nbq + nb_pack), dim3(64), pack_lds, stream>>>(lp);
-    else localize_quad_kernel<false><<<dim3((unsigned)nbq + nb_pack), dim3(64), pack_lds, stream>>>(lp);
+    (period ? localize_quad_kernel<true> : localize_quad_kernel<false>)<<<dim3((unsigned)nbq + nb_pack), dim3(64), pack_lds, stream>>>(lp);
     MIA_LAUNCH_CHECK();
     return MIA_OK;
   }
   const int64_t nb = (ng + 63) / 64;
   if (nb + nb_pack > 2147483647LL) return MIA_ERR_UNSUPPORTED;
   lp.nb_main = (unsigned)nb;
-  if (periodic) localize_kernel<true><<<dim3((unsigned)nb + nb_pack), dim3(64), pack_lds, stream>>>(lp);
-  else localize_kernel<false><<<dim3((unsigned)nb + nb_pack), dim3(64), pack_lds, stream>>>(lp);
+  (period ? localize_kernel<true> : localize_kernel<false>)<<<dim3((unsigned)nb + nb_pack), dim3(64), pack_lds, stream>>>(lp);
   MIA_LAUNCH_CHECK();
   return MIA_OK;
 }
@@ -1012,8 +945,7 @@ extern "C" int mia_letkf_index_build_periodic_f64(const double* obs_xyz, int64_t
   (void)hipGetLastError();
   if (!period) return MIA_ERR_NULL;
   if (n_coord < 1 || n_coord > MIA_MAX_COORD) return MIA_ERR_SIZE;
-  bool cyclic = false;
-  if (check_period(period, n_coord, &cyclic) != MIA_OK) return MIA_ERR_ARG;
+  if (check_period(period, n_coord, &period) != MIA_OK) return MIA_ERR_ARG;
   return index_build_impl(obs_xyz, P, n_coord, coord_group, gc_c, n_r, ws, ws_bytes, (hipStream_t)stream, nullptr, nullptr, false,
                           true, period);
 }
@@ -1051,8 +983,7 @@ extern "C" int mia_letkf_localize_taper_periodic_f64(int taper, const double* gr
   if (taper != MIA_TAPER_GC && taper != MIA_TAPER_GC_INF) return MIA_ERR_SIZE;
   if (!period) return MIA_ERR_NULL;
   if (n_coord < 1 || n_coord > MIA_MAX_COORD) return MIA_ERR_SIZE;
-  bool cyclic = false;
-  if (check_period(period, n_coord, &cyclic) != MIA_OK) return MIA_ERR_ARG;
+  if (check_period(period, n_coord, &period) != MIA_OK) return MIA_ERR_ARG;
   return mia::localize_impl(grid_xyz, g0, g1, obs_xyz, P, n_coord, coord_group, gc_c, n_r, gc_eps, p_cap, nbr_cnt,
                             nbr_idx, nbr_w, stats, ws, ws_bytes, (hipStream_t)stream, nullptr, false, nullptr, taper, false, true,
                             period);

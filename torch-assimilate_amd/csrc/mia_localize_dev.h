@@ -184,6 +184,55 @@ __device__ inline void point_cell(const IndexHeader* h, int c, double x, double*
   else { *xr = x; *cell = cell_coord(x, h->mn[c], h->invh[c], h->n[c]); }
 }
 
+// ---- the per-point localisation shared by scan_neighbours and the per-point kernels of localize.hip.  PER: the index has cyclic
+// coordinates; the open instantiations are the plain 3^d window clipped to the grid and the plain difference o - g.
+// a grid point's coordinate c as the kernels read it (xr: reduced on a cyclic axis) and its cell
+template <bool PER>
+__device__ __forceinline__ void point_coord(const IndexHeader* h, int c, double x, double* xr, int* cell) {
+  if constexpr (PER) point_cell(h, c, x, xr, cell);
+  else { *xr = x; *cell = cell_coord(x, h->mn[c], h->invh[c], h->n[c]); }
+}
+// displacement of a candidate's coordinate o from the point's g along c (sg: the window segment of the candidate; open: exactly o - g)
+template <bool PER>
+__device__ __forceinline__ double point_disp(const IndexHeader* h, const CycSeg& sg, int c, double o, double g) {
+  if constexpr (PER) return cyc_disp(o, g, sg.s[c], (sg.pw >> c) & 1u, h->period[c], h->inv_period[c]);
+  else return o - g;
+}
+// The walk over the cell window of a point with cells cg, as two statements of a loop body: MIA_WINDOW_BEGIN before the loop over
+// the steps o < n_steps, MIA_WINDOW_RANGE at the top of its body (it `continue`s past a step outside the grid or empty, else sets
+// beg / end, the step's candidates in the index's cell order, start: the index's per-cell starts).  Open: the 3^(nc-1) rows of outer
+// cells, each with the innermost coordinate's three cells [lo_l, hi_l] clipped to the grid as one range.  PER: two segments per row
+// (cyc_window_seg: a range across the seam is two), sg: their candidates' image shifts.  (Macros, not functions: the open walk
+// written as a function, inlined, compiled to other instructions than the walk written in place.)
+#define MIA_WINDOW_BEGIN(PER, h, nc, cg)                                                                                    \
+  const int n_steps = ((nc) == 1 ? 1 : ((nc) == 2 ? 3 : 9)) * ((PER) ? 2 : 1);                                             \
+  const int last_ = (nc) - 1;                                                                                              \
+  int lo_l = (cg)[last_] - 1, hi_l = (cg)[last_] + 1;                                                                      \
+  lo_l = lo_l < 0 ? 0 : lo_l;                                                                                              \
+  hi_l = hi_l > (h)->n[last_] - 1 ? (h)->n[last_] - 1 : hi_l
+#define MIA_WINDOW_RANGE(PER, h, start, nc, cg, o, sg, beg, end)                                                            \
+  if constexpr (PER) {                                                                                                     \
+    if (!cyc_window_seg(h, nc, cg, (o) >> 1, (o) & 1, sg)) continue;                                                       \
+    beg = (start)[sg.c_lo]; end = (start)[sg.c_hi + 1];                                                                    \
+  } else {                                                                                                                 \
+    int base_cell = 0;                                                                                                     \
+    bool ok = lo_l <= hi_l;                                                                                                \
+    if ((nc) >= 2) {                                                                                                       \
+      const int d0 = ((nc) == 2) ? ((o) - 1) : ((o) / 3 - 1);                                                              \
+      const int c0 = (cg)[0] + d0;                                                                                         \
+      ok = ok && c0 >= 0 && c0 < (h)->n[0];                                                                                \
+      base_cell = c0;                                                                                                      \
+      if ((nc) == 3) {                                                                                                     \
+        const int c1 = (cg)[1] + ((o) % 3 - 1);                                                                            \
+        ok = ok && c1 >= 0 && c1 < (h)->n[1];                                                                              \
+        base_cell = base_cell * (h)->n[1] + c1;                                                                            \
+      }                                                                                                                    \
+      base_cell *= (h)->n[last_];                                                                                          \
+    }                                                                                                                      \
+    if (!ok) continue;                                                                                                     \
+    beg = (start)[base_cell + lo_l]; end = (start)[base_cell + hi_l + 1];                                                  \
+  }
+
 template <typename WT>
 __device__ inline int scan_neighbours(const ScanParams& p, int64_t g, int lane, int cap, int* oidx, WT* ow) {
   const IndexHeader* h = p.hdr;
@@ -330,13 +379,15 @@ static inline IndexLayout index_layout(void* ws, int64_t P, int nc) {
 struct PackJob;
 // up to three small int32 buffers cleared by the first index kernel (only honoured when P > 0: the kernel runs)
 struct ZeroJob { int32_t* ptr[3]; int64_t n[3]; };
-// period: [n_coord] on the host, entry c > 0 = coordinate c is cyclic (nullptr: all open)
+// period (here and in every *_impl / launcher below): nullptr = every coordinate open, else [n_coord] on the host with some
+// entry > 0 (coordinate c is cyclic where period[c] > 0) -- what check_period makes of a public entry's argument
 int index_build_impl(const double* obs_xyz, int64_t P, int n_coord, const int32_t* coord_group,
                      const double* gc_c, int n_r, void* ws, size_t ws_bytes, hipStream_t stream,
                      const PackJob* pack = nullptr, const ZeroJob* zero = nullptr, bool header_clean = false,
                      bool sort_cells = true, const double* period = nullptr);
-// a period argument: nullptr or n_coord finite entries >= 0 (MIA_ERR_ARG otherwise); true when some entry is > 0
-int check_period(const double* period, int n_coord, bool* cyclic);
+// a public entry's period argument (nullptr or n_coord entries): MIA_ERR_ARG unless every entry is finite and >= 0; else *out
+// is the internal convention above -- period itself where some entry is > 0, nullptr where none is
+int check_period(const double* period, int n_coord, const double** out);
 // neighbour lists of grid points [g0, g1) (mia_letkf_localize_f64 without the argument checks of the C entry);
 // pack: float32 record packing job executed inside the first index kernel; stats_zeroed: stats are cleared by
 // the caller or listed in `zero`
@@ -348,7 +399,7 @@ int localize_impl(const double* grid_xyz, int64_t g0, int64_t g1, const double* 
 int localize_lists_impl(const double* grid_xyz, int64_t g0, int64_t g1, int64_t P, int n_coord, const int32_t* coord_group,
                         const double* gc_c, int n_r, double gc_eps, int p_cap, int32_t* nbr_cnt, int32_t* nbr_idx,
                         double* nbr_w, int32_t* stats, void* ws, hipStream_t stream, const PackJob* pack, int taper,
-                        bool periodic = false);
+                        const double* period = nullptr);
 // lists of the points flagged MIA_FLAG_RETRY into the order a sorted index gives (see sort_flagged_lists_kernel)
 int sort_flagged_lists(const int32_t* flags, const int32_t* nbr_cnt, int32_t* nbr_idx, double* nbr_w, int64_t ng, int p_cap,
                        void* ws, int64_t P, int n_coord, hipStream_t stream);

@@ -405,7 +405,7 @@ int split_pack_launch(const float* Yb, const float* d, int k, int64_t P, void* r
 int tile_lists_launch(const double* grid_xyz, int64_t g0, int64_t ng, int64_t P, int n_coord, const int32_t* coord_group,
                       const double* gc_c, int n_r, double gc_eps, int taper, int ut, void* tile_lists, int32_t* stats,
                       void* index_ws, hipStream_t stream, const SplitPackJob* pack, bool bucket = false, const int* counts = nullptr,
-                      bool periodic = false);
+                      const double* period = nullptr);
 // letkf_tile2.hip
 // housekeeping the analysis launch does for the bucket index (see Tile2Params)
 struct Tile2Params {

@@ -778,6 +778,9 @@ static bool count_arrays_clean_for_scan(void* ws) {
   return false;
 }
 
+// the coordinates of a step's period argument that check_period reads (a step with a bad n_coord is refused later, as MIA_ERR_SIZE)
+static inline int period_coords(int n_coord) { return n_coord >= 1 && n_coord <= MIA_MAX_COORD ? n_coord : 0; }
+
 static int step_impl(const float* X, int64_t G, int m, int k, const float* Yb, const float* d, int64_t P,
                      const double* grid_xyz, const double* obs_xyz, int n_coord, const int32_t* coord_group,
                      const double* gc_c, int n_r, double gc_eps, float inf_factor, float gamma, int method, int p_max_assumed,
@@ -787,10 +790,8 @@ static int step_impl(const float* X, int64_t G, int m, int k, const float* Yb, c
                      StepDecision* dec_io, const double* period) {
   const bool do1 = stage != 2, do2 = stage != 1;
   if (kdone_out) *kdone_out = nullptr;
+  // (period: checked by the entry, nullptr = open -- every index build of the step takes it)
   if (!X || !Xa || !flags || !counters || !ws || !grid_xyz || !coord_group || !gc_c) return MIA_ERR_NULL;
-  bool cyclic = false;      // (period: nullptr or [n_coord] on the host, > 0 = cyclic coordinate -- every index build of the step takes it)
-  if (n_coord >= 1 && n_coord <= MIA_MAX_COORD && mia::check_period(period, n_coord, &cyclic) != MIA_OK) return MIA_ERR_ARG;
-  if (!cyclic) period = nullptr;
   if (P > 0 && (!Yb || !d || !obs_xyz)) return MIA_ERR_NULL;
   if (method < 0 || method > 2 || (phase != 0 && phase != 1)) return MIA_ERR_SIZE;
   if ((uintptr_t)ws % 256) return MIA_ERR_ALIGN;
@@ -913,7 +914,7 @@ static int step_impl(const float* X, int64_t G, int m, int k, const float* Yb, c
     tl_loc.scan.start = tl_counts;
     tl_loc.stats = ctr;
     tl_loc.longest_bound = pm_tl;
-    tl_loc.periodic = cyclic ? 1 : 0;
+    tl_loc.periodic = period ? 1 : 0;
   }
   (void)hipGetLastError();
   if (exch || peer) {
@@ -971,7 +972,7 @@ static int step_impl(const float* X, int64_t G, int m, int k, const float* Yb, c
       if (!tl_fused) {
         rc = mia::tile_lists_launch(grid_xyz, b0, b1 - b0, P, n_coord, coord_group, gc_c, n_r, gc_eps, MIA_TAPER_GC, L.ut,
                                     base + L.tl, ctr, base + L.loc, ps, (tl_bucket || tl_rbf) ? nullptr : &sj, tl_bucket, tl_counts,
-                                    cyclic);
+                                    period);
         if (rc != MIA_OK) return rc;
       }
     } else if (b1 > b0) {
@@ -1048,7 +1049,7 @@ static int step_impl(const float* X, int64_t G, int m, int k, const float* Yb, c
         }
         rc = mia::localize_lists_impl(grid_xyz, c0, c1, P, n_coord, coord_group, gc_c, n_r, gc_eps, L.cap, const_cast<int32_t*>(ccnt),
                                       const_cast<int32_t*>(cidx), const_cast<double*>(cw), (int32_t*)(base + L.scratch),
-                                      base + L.loc, (hipStream_t)stream, nullptr, MIA_TAPER_GC, cyclic);
+                                      base + L.loc, (hipStream_t)stream, nullptr, MIA_TAPER_GC, period);
         if (rc != MIA_OK) return rc;
         rc = mia::sort_flagged_lists(cfl, ccnt, const_cast<int32_t*>(cidx), const_cast<double*>(cw), c1 - c0, (int)L.cap,
                                      base + L.loc, P, n_coord, (hipStream_t)stream);
@@ -1168,6 +1169,22 @@ static int step_impl(const float* X, int64_t G, int m, int k, const float* Yb, c
   return MIA_OK;
 }
 
+// the body of the two step entries below (period: as the periodic entry takes it, nullptr = open)
+static int step_entry(const float* X, int64_t G, int m, int k, const float* Yb, const float* d, int64_t P, const double* grid_xyz,
+                      const double* obs_xyz, int n_coord, const int32_t* coord_group, const double* period, const double* gc_c, int n_r,
+                      double gc_eps, float inf_factor, float gamma, int method, int p_max_assumed, mia_comm_t* comm, int n_chunks,
+                      int phase, float* Xa, int32_t* flags, int32_t* counters, void* ws, size_t ws_bytes, void* stream,
+                      void* comm_stream, void* prep_stream, int step_flags) {
+  if (mia::check_period(period, period_coords(n_coord), &period) != MIA_OK) return MIA_ERR_ARG;
+  hipEvent_t pe = nullptr;
+  uint32_t seq = 0;
+  const hipEvent_t t0 = t_time_start, t1 = t_time_stop;
+  t_time_start = t_time_stop = nullptr;
+  return step_impl(X, G, m, k, Yb, d, P, grid_xyz, obs_xyz, n_coord, coord_group, gc_c, n_r, gc_eps, inf_factor, gamma, method,
+                   p_max_assumed, comm, n_chunks, phase, Xa, flags, counters, ws, ws_bytes, stream, comm_stream, prep_stream,
+                   step_flags, 0, &pe, &seq, t0, t1, nullptr, nullptr, period);
+}
+
 extern "C" int mia_letkf_sharded_step_streams_f32(const float* X, int64_t G, int m, int k,
                                                   const float* Yb, const float* d, int64_t P,
                                                   const double* grid_xyz, const double* obs_xyz, int n_coord,
@@ -1177,13 +1194,9 @@ extern "C" int mia_letkf_sharded_step_streams_f32(const float* X, int64_t G, int
                                                   float* Xa, int32_t* flags, int32_t* counters,
                                                   void* ws, size_t ws_bytes, void* stream, void* comm_stream,
                                                   void* prep_stream, int step_flags) {
-  hipEvent_t pe = nullptr;
-  uint32_t seq = 0;
-  const hipEvent_t t0 = t_time_start, t1 = t_time_stop;
-  t_time_start = t_time_stop = nullptr;
-  return step_impl(X, G, m, k, Yb, d, P, grid_xyz, obs_xyz, n_coord, coord_group, gc_c, n_r, gc_eps, inf_factor, gamma, method,
-                   p_max_assumed, comm, n_chunks, phase, Xa, flags, counters, ws, ws_bytes, stream, comm_stream, prep_stream,
-                   step_flags, 0, &pe, &seq, t0, t1, nullptr, nullptr, nullptr);
+  return step_entry(X, G, m, k, Yb, d, P, grid_xyz, obs_xyz, n_coord, coord_group, nullptr, gc_c, n_r, gc_eps, inf_factor, gamma,
+                    method, p_max_assumed, comm, n_chunks, phase, Xa, flags, counters, ws, ws_bytes, stream, comm_stream, prep_stream,
+                    step_flags);
 }
 
 extern "C" int mia_letkf_sharded_step_periodic_f32(const float* X, int64_t G, int m, int k, const float* Yb, const float* d, int64_t P,
@@ -1193,13 +1206,9 @@ extern "C" int mia_letkf_sharded_step_periodic_f32(const float* X, int64_t G, in
                                                    float* Xa, int32_t* flags, int32_t* counters, void* ws, size_t ws_bytes, void* stream,
                                                    void* comm_stream, void* prep_stream, int step_flags) {
   if (!period) return MIA_ERR_NULL;
-  hipEvent_t pe = nullptr;
-  uint32_t seq = 0;
-  const hipEvent_t t0 = t_time_start, t1 = t_time_stop;
-  t_time_start = t_time_stop = nullptr;
-  return step_impl(X, G, m, k, Yb, d, P, grid_xyz, obs_xyz, n_coord, coord_group, gc_c, n_r, gc_eps, inf_factor, gamma, method,
-                   p_max_assumed, comm, n_chunks, phase, Xa, flags, counters, ws, ws_bytes, stream, comm_stream, prep_stream,
-                   step_flags, 0, &pe, &seq, t0, t1, nullptr, nullptr, period);
+  return step_entry(X, G, m, k, Yb, d, P, grid_xyz, obs_xyz, n_coord, coord_group, period, gc_c, n_r, gc_eps, inf_factor, gamma,
+                    method, p_max_assumed, comm, n_chunks, phase, Xa, flags, counters, ws, ws_bytes, stream, comm_stream, prep_stream,
+                    step_flags);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1215,7 +1224,7 @@ extern "C" int mia_letkf_sharded_step_periodic_f32(const float* X, int64_t G, in
 namespace {
 struct StepJob {
   const float* X; int64_t G; int m, k; const float* Yb; const float* d; int64_t P; const double* grid; const double* obs;
-  int n_coord; int32_t cg[MIA_MAX_COORD]; double rc_[MIA_MAX_RADII]; int n_r; double per[MIA_MAX_COORD] = {0.0, 0.0, 0.0}; double eps; float inf, gamma; int method, hint;
+  int n_coord; int32_t cg[MIA_MAX_COORD]; double rc_[MIA_MAX_RADII]; int n_r; double per[MIA_MAX_COORD] = {0.0, 0.0, 0.0}; bool cyclic = false; double eps; float inf, gamma; int method, hint;
   mia_comm_t* comm; int n_chunks, phase; float* Xa; int32_t* flags; int32_t* counters; void* ws; size_t ws_bytes;
   void *stream, *comm_stream, *prep_stream; int step_flags;
   int32_t* host8; void *after, *on; void** done_event; void *t0, *t1;
@@ -1233,7 +1242,7 @@ struct StepJob {
     struct Scope { Scope(const int* o) { mia::option_override(o); } ~Scope() { mia::option_override(nullptr); } } scope(opts);
     return step_impl(X, G, m, k, Yb, d, P, grid, obs, n_coord, cg, rc_, n_r, eps, inf, gamma, method, hint, comm, n_chunks, phase,
                      Xa, flags, counters, ws, ws_bytes, stream, comm_stream, prep_stream, step_flags, stage, &pe, &seq,
-                     (hipEvent_t)t0, (hipEvent_t)t1, stage == 2 ? &kdone : nullptr, &dec, per);
+                     (hipEvent_t)t0, (hipEvent_t)t1, stage == 2 ? &kdone : nullptr, &dec, cyclic ? per : nullptr);
   }
 };
 struct LaunchThreads {
@@ -1473,10 +1482,10 @@ static int step_submit(const float* X, int64_t G, int m, int k, const float* Yb,
                        void** done_event, void* time_start_event, void* time_stop_event, void** job_out, const double* period) {
   if (!job_out || !coord_group || !gc_c) return MIA_ERR_NULL;
   if (n_coord < 1 || n_coord > MIA_MAX_COORD || n_r < 1 || n_r > MIA_MAX_RADII) return MIA_ERR_SIZE;
-  bool cyclic = false;
-  if (mia::check_period(period, n_coord, &cyclic) != MIA_OK) return MIA_ERR_ARG;
+  if (mia::check_period(period, n_coord, &period) != MIA_OK) return MIA_ERR_ARG;
   StepJob* j = new StepJob();
-  for (int c = 0; c < n_coord; ++c) j->per[c] = cyclic ? period[c] : 0.0;
+  j->cyclic = period != nullptr;
+  for (int c = 0; c < n_coord; ++c) j->per[c] = period ? period[c] : 0.0;
   j->X = X; j->G = G; j->m = m; j->k = k; j->Yb = Yb; j->d = d; j->P = P; j->grid = grid_xyz; j->obs = obs_xyz;
   j->n_coord = n_coord; j->n_r = n_r; j->eps = gc_eps; j->inf = inf_factor; j->gamma = gamma; j->method = method;
   for (int c = 0; c < n_coord; ++c) j->cg[c] = coord_group[c];
@@ -1542,6 +1551,8 @@ extern "C" int mia_letkf_step_submit_args(const mia_step_args_t* a, void** job_o
 // mia_letkf_step_readback (+ mia_event_synchronize and a copy of the counters, when out8 is given) do, in one call.
 extern "C" int mia_letkf_step_run_args(const mia_step_args_t* a, int32_t* out8) {
   if (!a || !a->done_event || !a->host8) return MIA_ERR_NULL;
+  const double* period = nullptr;
+  if (mia::check_period(a->period, period_coords(a->n_coord), &period) != MIA_OK) return MIA_ERR_ARG;
   int rc = mia_letkf_step_drain();       // (a synchronous step must not overtake queued ones)
   if (rc != MIA_OK) return rc;
   if (a->in_event) {
@@ -1554,7 +1565,7 @@ extern "C" int mia_letkf_step_run_args(const mia_step_args_t* a, int32_t* out8) 
   rc = step_impl(a->X, a->G, a->m, a->k, a->Yb, a->d, a->P, a->grid_xyz, a->obs_xyz, a->n_coord, a->coord_group, a->gc_c, a->n_r, a->gc_eps,
                  a->inf_factor, a->gamma, a->method, a->p_max_assumed, a->comm, a->n_chunks, a->phase, a->Xa, a->flags, a->counters, a->ws,
                  a->ws_bytes, a->stream, a->comm_stream, a->prep_stream, a->step_flags & ~MIA_STEP_NO_JOIN, 0, &pe, &seq,
-                 (hipEvent_t)a->time_start_event, (hipEvent_t)a->time_stop_event, nullptr, nullptr, a->period);
+                 (hipEvent_t)a->time_start_event, (hipEvent_t)a->time_stop_event, nullptr, nullptr, period);
   if (rc != MIA_OK) return rc;
   rc = mia_letkf_step_readback(a->counters, a->host8, a->after_stream, a->on_stream, a->done_event);
   if (rc != MIA_OK || !out8) return rc;

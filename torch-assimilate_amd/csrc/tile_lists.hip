@@ -88,9 +88,18 @@ __global__ __launch_bounds__(64) void localize_tiles_kernel(TileLocParams p) {
   }
 }
 
+// the tile-list kernel for a launch (PER: the index has cyclic coordinates)
+template <bool PER>
+static void (*tiles_kernel(bool bucket, int taper, int nc))(TileLocParams) {
+#define MIA_TL_PICK(B, T) (nc == 1 ? localize_tiles_kernel<B, 1, T, PER> : (nc == 2 ? localize_tiles_kernel<B, 2, T, PER> : localize_tiles_kernel<B, 3, T, PER>))
+  if (bucket) return taper == MIA_TAPER_GC_INF ? MIA_TL_PICK(true, MIA_TAPER_GC_INF) : MIA_TL_PICK(true, MIA_TAPER_GC);
+  return taper == MIA_TAPER_GC_INF ? MIA_TL_PICK(false, MIA_TAPER_GC_INF) : MIA_TL_PICK(false, MIA_TAPER_GC);
+#undef MIA_TL_PICK
+}
+
 int tile_lists_launch(const double* grid_xyz, int64_t g0, int64_t ng, int64_t P, int n_coord, const int32_t* coord_group,
                       const double* gc_c, int n_r, double gc_eps, int taper, int ut, void* tile_lists, int32_t* stats,
-                      void* index_ws, hipStream_t stream, const SplitPackJob* pack, bool bucket, const int* counts, bool periodic) {
+                      void* index_ws, hipStream_t stream, const SplitPackJob* pack, bool bucket, const int* counts, const double* period) {
   if (ng < 0 || P < 0 || ut < 1 || ut > 6) return MIA_ERR_SIZE;
   if (!tile_lists || !stats) return MIA_ERR_NULL;
   const TileListLayout L = tile_list_layout(ng, ut);
@@ -123,13 +132,7 @@ int tile_lists_launch(const double* grid_xyz, int64_t g0, int64_t ng, int64_t P,
   if (rc != MIA_OK) return rc;
   if (bucket && counts) tp.scan.start = counts;      // (which of the layout's two per-cell count arrays this step's build filled)
   tp.nb_main = (unsigned)L.ntile;
-  void (*kern)(TileLocParams) = nullptr;
-#define MIA_TL_PICK(B, T)                                                                                                  \
-  if (periodic) kern = n_coord == 1 ? localize_tiles_kernel<B, 1, T, true> : (n_coord == 2 ? localize_tiles_kernel<B, 2, T, true> : localize_tiles_kernel<B, 3, T, true>); \
-  else kern = n_coord == 1 ? localize_tiles_kernel<B, 1, T> : (n_coord == 2 ? localize_tiles_kernel<B, 2, T> : localize_tiles_kernel<B, 3, T>)
-  if (bucket) { if (taper == MIA_TAPER_GC_INF) MIA_TL_PICK(true, MIA_TAPER_GC_INF); else MIA_TL_PICK(true, MIA_TAPER_GC); }
-  else { if (taper == MIA_TAPER_GC_INF) MIA_TL_PICK(false, MIA_TAPER_GC_INF); else MIA_TL_PICK(false, MIA_TAPER_GC); }
-#undef MIA_TL_PICK
+  void (*kern)(TileLocParams) = period ? tiles_kernel<true>(bucket, taper, n_coord) : tiles_kernel<false>(bucket, taper, n_coord);
   if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   kern<<<dim3((unsigned)(L.ntile + nb_pack)), dim3(64), lds, stream>>>(tp);
   MIA_LAUNCH_CHECK();
@@ -170,8 +173,7 @@ static int localize_tiles_entry(int taper, const double* grid_xyz, int64_t g0, i
   if (g1 < g0 || g0 < 0 || P < 0 || p_max < 0 || extra_blocks < 0) return MIA_ERR_SIZE;
   if (n_coord < 1 || n_coord > MIA_MAX_COORD || n_r < 1 || n_r > MIA_MAX_RADII) return MIA_ERR_SIZE;
   if (!coord_group || !gc_c || !stats || !tile_lists) return MIA_ERR_NULL;
-  bool cyclic = false;
-  if (check_period(period, n_coord, &cyclic) != MIA_OK) return MIA_ERR_ARG;
+  if (check_period(period, n_coord, &period) != MIA_OK) return MIA_ERR_ARG;
   const int ut = tile_ut_for(p_max) + extra_blocks;
   if (ut > 6) return MIA_ERR_UNSUPPORTED;
   if (tile_lists_bytes < tile_list_layout(g1 - g0, ut).bytes) return MIA_ERR_WORKSPACE;
@@ -182,7 +184,7 @@ static int localize_tiles_entry(int taper, const double* grid_xyz, int64_t g0, i
     if (rc != MIA_OK) return rc;
   }
   return tile_lists_launch(grid_xyz, g0, g1 - g0, P, n_coord, coord_group, gc_c, n_r, gc_eps, taper, ut, tile_lists, stats, ws,
-                           stream, nullptr, false, nullptr, cyclic);
+                           stream, nullptr, false, nullptr, period);
 }
 
 extern "C" int mia_letkf_localize_tiles_f64(int taper, const double* grid_xyz, int64_t g0, int64_t g1,

@@ -113,6 +113,11 @@ def _periods(period, nc: int):
     return (C.c_double * nc)(*per)
 
 
+def _period_arg(per, nc: int):
+    """What the periodic C entries take for ``_periods``' result: the array itself, or all zeros (= the open entry) for None."""
+    return per if per is not None else (C.c_double * nc)()
+
+
 class LetkfEngine:
     """One engine per process / GPU.  All work is enqueued on the current torch stream of
     ``device``; results are ordinary device tensors."""
@@ -180,13 +185,9 @@ class LetkfEngine:
             raise ValueError("coord_group needs one entry per coordinate")
         cg = (C.c_int32 * nc)(*coord_group)
         rc = (C.c_double * n_r)(*radii)
-        per = _periods(period, nc)
+        per = _period_arg(_periods(period, nc), nc)
 
         def call(cap, cnt, idx, w):
-            if per is None:
-                return self.lib.mia_letkf_localize_taper_f64(
-                    int(taper), _ptr(grid), g0, g1, _ptr(obs), P, nc, cg, rc, n_r, float(eps), cap,
-                    _ptr(cnt), _ptr(idx), _ptr(w), _ptr(stats), _ptr(ws), ws.numel(), self._stream())
             return self.lib.mia_letkf_localize_taper_periodic_f64(
                 int(taper), _ptr(grid), g0, g1, _ptr(obs), P, nc, cg, per, rc, n_r, float(eps), cap,
                 _ptr(cnt), _ptr(idx), _ptr(w), _ptr(stats), _ptr(ws), ws.numel(), self._stream())
@@ -200,13 +201,13 @@ class LetkfEngine:
             cnt = torch.empty(n, dtype=torch.int32, device=self.device)
             idx = torch.empty((n, cap), dtype=torch.int32, device=self.device)
             w = torch.empty((n, cap), dtype=torch.float64, device=self.device)
-            _cabi.check(call(cap, cnt, idx, w), "mia_letkf_localize_f64")
+            _cabi.check(call(cap, cnt, idx, w), "mia_letkf_localize_taper_periodic_f64")
             return NeighbourLists(cnt, idx, w, cap, int(assume_p_max), g0, g1, stats)
         while True:
             cnt = torch.empty(n, dtype=torch.int32, device=self.device)
             idx = torch.empty((n, cap), dtype=torch.int32, device=self.device)
             w = torch.empty((n, cap), dtype=torch.float64, device=self.device)
-            _cabi.check(call(cap, cnt, idx, w), "mia_letkf_localize_f64")
+            _cabi.check(call(cap, cnt, idx, w), "mia_letkf_localize_taper_periodic_f64")
             p_max, n_over = (int(v) for v in stats.tolist())   # host sync: sizes the analysis launch
             if n_over == 0:
                 break
@@ -246,16 +247,11 @@ class LetkfEngine:
                     "mia_letkf_tile_lists_bytes")
         lists = torch.empty(max(tb.value, 256), dtype=torch.uint8, device=self.device)
         stats = torch.zeros(2, dtype=torch.int32, device=self.device)
-        per = _periods(period, nc)
-        if per is None:
-            rcode = self.lib.mia_letkf_localize_tiles_f64(
-                int(taper), _ptr(grid), g0, g1, _ptr(obs), P, nc, cg, rc, len(radii), float(eps), int(p_max), int(extra_blocks),
-                _ptr(lists), lists.numel(), _ptr(stats), _ptr(ws), ws.numel(), self._stream())
-        else:
-            rcode = self.lib.mia_letkf_localize_tiles_periodic_f64(
-                int(taper), _ptr(grid), g0, g1, _ptr(obs), P, nc, cg, per, rc, len(radii), float(eps), int(p_max),
-                int(extra_blocks), _ptr(lists), lists.numel(), _ptr(stats), _ptr(ws), ws.numel(), self._stream())
-        _cabi.check(rcode, "mia_letkf_localize_tiles_f64")
+        per = _period_arg(_periods(period, nc), nc)
+        _cabi.check(self.lib.mia_letkf_localize_tiles_periodic_f64(
+            int(taper), _ptr(grid), g0, g1, _ptr(obs), P, nc, cg, per, rc, len(radii), float(eps), int(p_max),
+            int(extra_blocks), _ptr(lists), lists.numel(), _ptr(stats), _ptr(ws), ws.numel(), self._stream()),
+            "mia_letkf_localize_tiles_periodic_f64")
         return TileLists(lists, int(p_max), g0, g1, stats, int(extra_blocks))
 
     def pack_split(self, Yb: torch.Tensor, d: torch.Tensor) -> torch.Tensor:
@@ -380,12 +376,8 @@ class LetkfEngine:
         cg = (C.c_int32 * nc)(*coord_group)
         rc = (C.c_double * len(radii))(*radii)
         per = _periods(period, nc)
-        if per is None:
-            _cabi.check(self.lib.mia_letkf_index_build_f64(_ptr(obs), P, nc, cg, rc, len(radii), _ptr(ws), ws.numel(),
-                                                           self._stream()), "mia_letkf_index_build_f64")
-        else:
-            _cabi.check(self.lib.mia_letkf_index_build_periodic_f64(_ptr(obs), P, nc, cg, per, rc, len(radii), _ptr(ws), ws.numel(),
-                                                                    self._stream()), "mia_letkf_index_build_periodic_f64")
+        _cabi.check(self.lib.mia_letkf_index_build_periodic_f64(_ptr(obs), P, nc, cg, _period_arg(per, nc), rc, len(radii), _ptr(ws),
+                                                                ws.numel(), self._stream()), "mia_letkf_index_build_periodic_f64")
         return ObsIndex(ws, obs, radii, coord_group, P, nc, None if per is None else list(per))
 
     def analysis_fused(self, X: torch.Tensor, rec: torch.Tensor, grid_xyz, index: ObsIndex, p_max_assumed: int,

@@ -672,7 +672,7 @@ class ShardedLetkf:
         import ctypes as C
         import torch.distributed as dist
         from . import _cabi
-        from .engine import _ptr
+        from .engine import _period_arg, _ptr
         eng = self.engine
         if self._p_max_hint is None:
             for h in list(self._in_flight):                       # drain: the exact-list route is synchronous
@@ -733,7 +733,7 @@ class ShardedLetkf:
                 slot["ws"] = torch.empty(max(nbytes.value, 256), dtype=torch.uint8, device=X.device)
             cg = [0] * nc if self.coord_group is None else [int(c) for c in self.coord_group]
             slot["cg"] = (C.c_int32 * nc)(*cg)
-            slot["per"] = self._cyclic(nc)
+            slot["per"] = _period_arg(self._cyclic(nc), nc)          # (all zero: open)
             slot["rc"] = (C.c_double * len(self.radii))(*[float(r) for r in self.radii])
             slot["counters"] = torch.zeros(8, dtype=torch.int32, device=X.device)
             slot["host"] = torch.zeros(8, dtype=torch.int32).pin_memory()
@@ -758,7 +758,7 @@ class ShardedLetkf:
             geom_key = (geometry_id, key, self._tile_extra, self._scan_index, g0, g1, tuple(opts), self.method, self.rbf_gamma,
                         tuple(float(r) for r in self.radii), float(self.eps),
                         None if self.coord_group is None else tuple(int(c) for c in self.coord_group),
-                        None if slot["per"] is None else tuple(slot["per"]))
+                        tuple(slot["per"]))
         reuse = (geom_key is not None and slot.get("geom") == geom_key and not self._no_tile_lists and not self._fresh_box_once
                  and C_chunks == 1 and st["comm"] is None)
         method = {"auto": 0, "eig": 1, "matfun": 2}[self.method]
@@ -810,20 +810,13 @@ class ShardedLetkf:
         def call(phase):
             # (plain integers for the pointer arguments: ctypes converts them itself, a C.c_void_p object per argument was a
             #  third of this function's host time)
-            if slot["per"] is not None:
-                rc = lib.mia_letkf_sharded_step_periodic_f32(
-                    X.data_ptr(), G, m, k, Yb.data_ptr(), d.data_ptr(), P, grid.data_ptr(), obs.data_ptr(), nc, slot["cg"], slot["per"],
-                    slot["rc"], len(self.radii), eps, inf, gamma, method, hint, comm_arg,
-                    C_chunks, phase, out.data_ptr(), flags.data_ptr(), slot["counters"].data_ptr(), slot["ws"].data_ptr(),
-                    slot["ws"].numel(), comp.cuda_stream, side, prep.cuda_stream if prep is not None else None, step_flags)
-            else:
-                rc = lib.mia_letkf_sharded_step_streams_f32(
-                    X.data_ptr(), G, m, k, Yb.data_ptr(), d.data_ptr(), P, grid.data_ptr(), obs.data_ptr(), nc, slot["cg"],
-                    slot["rc"], len(self.radii), eps, inf, gamma, method, hint, comm_arg,
-                    C_chunks, phase, out.data_ptr(), flags.data_ptr(), slot["counters"].data_ptr(), slot["ws"].data_ptr(),
-                    slot["ws"].numel(), comp.cuda_stream, side, prep.cuda_stream if prep is not None else None, step_flags)
+            rc = lib.mia_letkf_sharded_step_periodic_f32(
+                X.data_ptr(), G, m, k, Yb.data_ptr(), d.data_ptr(), P, grid.data_ptr(), obs.data_ptr(), nc, slot["cg"], slot["per"],
+                slot["rc"], len(self.radii), eps, inf, gamma, method, hint, comm_arg,
+                C_chunks, phase, out.data_ptr(), flags.data_ptr(), slot["counters"].data_ptr(), slot["ws"].data_ptr(),
+                slot["ws"].numel(), comp.cuda_stream, side, prep.cuda_stream if prep is not None else None, step_flags)
             if rc != 0:
-                _cabi.check(rc, "mia_letkf_sharded_step_streams_f32")
+                _cabi.check(rc, "mia_letkf_sharded_step_periodic_f32")
 
         self._fresh_box_once = False
         slot["ws_clean"] = False            # (until this step has been collected without an error)
@@ -853,7 +846,7 @@ class ShardedLetkf:
                 a.G, a.m, a.k, a.P, a.n_coord, a.n_r = G, m, k, P, nc, len(self.radii)
                 for i_ in range(nc):
                     a.coord_group[i_] = slot["cg"][i_]
-                    a.period[i_] = slot["per"][i_] if slot["per"] is not None else 0.0
+                    a.period[i_] = slot["per"][i_]
                 for i_ in range(len(self.radii)):
                     a.gc_c[i_] = slot["rc"][i_]
                 a.flags, a.counters, a.ws, a.ws_bytes = flags.data_ptr(), slot["counters"].data_ptr(), slot["ws"].data_ptr(), slot["ws"].numel()
@@ -902,7 +895,7 @@ class ShardedLetkf:
                 a.G, a.m, a.k, a.P, a.n_coord, a.n_r = G, m, k, P, nc, len(self.radii)
                 for i_ in range(nc):
                     a.coord_group[i_] = slot["cg"][i_]
-                    a.period[i_] = slot["per"][i_] if slot["per"] is not None else 0.0
+                    a.period[i_] = slot["per"][i_]
                 for i_ in range(len(self.radii)):
                     a.gc_c[i_] = slot["rc"][i_]
                 a.flags, a.counters, a.ws, a.ws_bytes = flags.data_ptr(), slot["counters"].data_ptr(), slot["ws"].data_ptr(), slot["ws"].numel()
@@ -938,19 +931,13 @@ class ShardedLetkf:
         lib = self.engine.lib
 
         def call(phase):
-            if any(a.period[i_] > 0.0 for i_ in range(a.n_coord)):
-                rc = lib.mia_letkf_sharded_step_periodic_f32(a.X, a.G, a.m, a.k, a.Yb, a.d, a.P, a.grid_xyz, a.obs_xyz, a.n_coord,
-                                                             a.coord_group, a.period, a.gc_c, a.n_r, a.gc_eps, a.inf_factor, a.gamma,
-                                                             a.method, a.p_max_assumed, a.comm, a.n_chunks, phase, a.Xa, a.flags,
-                                                             a.counters, a.ws, a.ws_bytes, a.stream, a.comm_stream, a.prep_stream,
-                                                             a.step_flags)
-            else:
-                rc = lib.mia_letkf_sharded_step_streams_f32(a.X, a.G, a.m, a.k, a.Yb, a.d, a.P, a.grid_xyz, a.obs_xyz, a.n_coord, a.coord_group,
-                                                        a.gc_c, a.n_r, a.gc_eps, a.inf_factor, a.gamma, a.method, a.p_max_assumed, a.comm,
-                                                        a.n_chunks, phase, a.Xa, a.flags, a.counters, a.ws, a.ws_bytes, a.stream,
-                                                        a.comm_stream, a.prep_stream, a.step_flags)
+            rc = lib.mia_letkf_sharded_step_periodic_f32(a.X, a.G, a.m, a.k, a.Yb, a.d, a.P, a.grid_xyz, a.obs_xyz, a.n_coord,
+                                                         a.coord_group, a.period, a.gc_c, a.n_r, a.gc_eps, a.inf_factor, a.gamma,
+                                                         a.method, a.p_max_assumed, a.comm, a.n_chunks, phase, a.Xa, a.flags,
+                                                         a.counters, a.ws, a.ws_bytes, a.stream, a.comm_stream, a.prep_stream,
+                                                         a.step_flags)
             if rc != 0:
-                _cabi.check(rc, "mia_letkf_sharded_step_streams_f32")
+                _cabi.check(rc, "mia_letkf_sharded_step_periodic_f32")
         return call
 
     def _native_finish(self, h: "PendingStep"):
