@@ -117,9 +117,8 @@ static void caller(int id, int n_steps) {
       rc2 = mia_letkf_step_submit_args(&a, &s.job);
       CHECK(rc2 == MIA_OK);
       if (it % 2 == 0) {          // collected at once, in one call
-        int32_t out8[8]; int bn = 0;
-        CHECK(mia_letkf_step_collect(s.job, &s.event, s.host8, streams[0], 1, out8, &bn) == MIA_OK); s.job = nullptr;
-        CHECK(bn >= 1 && bn <= 4);
+        int32_t out8[8];
+        CHECK(mia_letkf_step_collect(s.job, &s.event, s.host8, streams[0], 1, out8) == MIA_OK); s.job = nullptr;
       }
       if (t0) { float ms = 0; (void)mia_timing_event_elapsed_ms(t0, t1, &ms); CHECK(mia_timing_event_release(t0) == MIA_OK); CHECK(mia_timing_event_release(t1) == MIA_OK); }
     } else {
@@ -128,7 +127,6 @@ static void caller(int id, int n_steps) {
                                   s.host8, comm ? streams[1] : streams[0], streams[1], &s.event, nullptr, nullptr, &s.job);
       CHECK(rc2 == MIA_OK);
     }
-    if (id == 1 && it % 6 == 1) { CHECK(mia_set_option("step_coalesce", (it / 6) % 3) == MIA_OK); }      // launch coalescing on / off while steps are in flight
     if (it % 13 == 6) {          // the caller gives a workspace up between steps (a new geometry): release, then reuse the address
       if (s.job) { CHECK(mia_letkf_step_join(s.job) == MIA_OK); } s.job = nullptr;
       CHECK(mia_letkf_step_workspace_release(s.ws) == MIA_OK);
@@ -155,9 +153,7 @@ int main(int argc, char** argv) {
   for (auto& t : th) t.join();
   CHECK(mia_letkf_step_drain() == MIA_OK);
   CHECK(mia_set_option("tile_fused", -1) == MIA_OK);
-  CHECK(mia_set_option("step_coalesce", -1) == MIA_OK);
-  long long co_l = 0, co_s = 0, trace[8 * 16];
-  CHECK(mia_letkf_step_coalesce_stats(&co_l, &co_s) == MIA_OK && co_s >= co_l);
+  long long trace[8 * 16];
   CHECK(mia_debug_step_trace(trace, 16) == 16);
   CHECK(mia_last_analysis_kernel(name, (int)sizeof name) == MIA_OK);
   double a = 0, b = 0; long long n = 0;

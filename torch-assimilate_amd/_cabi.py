@@ -113,13 +113,11 @@ _PROTOS = {
                                vp, vp, vp, C.POINTER(vp), vp, vp, C.POINTER(vp)], i32),
     "mia_letkf_step_submit_args": ([vp, vp], i32),
     "mia_letkf_step_run_args": ([vp, vp], i32),
-    "mia_letkf_step_collect": ([vp, vp, vp, vp, i32, vp, vp], i32),
+    "mia_letkf_step_collect": ([vp, vp, vp, vp, i32, vp], i32),
     "mia_timing_event_acquire": ([C.POINTER(vp)], i32),
     "mia_timing_event_release": ([vp], i32),
     "mia_timing_event_elapsed_ms": ([vp, vp, C.POINTER(C.c_float)], i32),
     "mia_letkf_step_join": ([vp], i32),
-    "mia_letkf_step_join_info": ([vp, C.POINTER(C.c_int)], i32),
-    "mia_letkf_step_coalesce_stats": ([C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)], i32),
     "mia_debug_step_trace": ([C.POINTER(C.c_longlong), i32], i32),
     "mia_letkf_step_drain": ([], i32),
     "mia_letkf_step_readback": ([vp, vp, vp, vp, C.POINTER(vp)], i32),
@@ -233,10 +231,8 @@ class TimingEvent:
 
 
 def step_coalesce_stats():
-    """mia_letkf_step_coalesce_stats: (analysis launches made by the launch thread's collector, steps they carried) so far."""
-    a, b = C.c_longlong(0), C.c_longlong(0)
-    check(lib().mia_letkf_step_coalesce_stats(C.byref(a), C.byref(b)), "mia_letkf_step_coalesce_stats")
-    return int(a.value), int(b.value)
+    """Always (0, 0): every step has an analysis launch of its own; bench.py reads the value."""
+    return 0, 0
 
 
 def last_analysis_kernel() -> str:

@@ -74,7 +74,6 @@ class PendingStep:
 
     def __init__(self, runner, state, out=None):
         self._runner, self._st, self._out = runner, state, out
-        self.batch_n = 1        # steps that shared this step's analysis launch (known once the step has been joined)
 
     def result(self) -> torch.Tensor:
         """The (m, k, G) analysis; performs the step's host read-back the first time it is called."""
@@ -260,8 +259,6 @@ class ShardedLetkf:
         self._in_flight = []
         self._time_next = False        # time_next_step(): the next native step brackets its analysis kernel with events
         self.kernel_timings = []       # [(start, stop)] torch events recorded on the analysis stream by the library
-        self.kernel_batch = {}         # (start, stop) -> steps in the launch those events bracket (launch coalescing; absent: 1)
-        self.last_batch_n = 1          # steps that shared the analysis launch of the step finished last
         # (eight measured best at config 2: 2.61e9 analyses/s against 2.41e9 with sixteen -- more steps in flight are more kernels sharing
         #  the chip, profiles/r05_coalesce.txt; rounds 1-4 capped the argument at eight silently)
         self.max_in_flight = max(1, min(int(max_in_flight), 16))
@@ -954,15 +951,11 @@ class ShardedLetkf:
                 # the result; THIS step's event only: the analysis stream as a whole also holds the later steps)
                 import ctypes as C
                 if "out8" not in slot:
-                    slot["out8"], slot["bn"] = (C.c_int32 * 8)(), C.c_int(1)
-                    slot["bn_ref"] = C.byref(slot["bn"])
+                    slot["out8"] = (C.c_int32 * 8)()
                 rc = self.engine.lib.mia_letkf_step_collect(p["job"], C.byref(p["ev"]), slot["host"].data_ptr(),
-                                                            torch._C._cuda_getCurrentRawStream(p["dev_index"]), 1, slot["out8"], slot["bn_ref"])
+                                                            torch._C._cuda_getCurrentRawStream(p["dev_index"]), 1, slot["out8"])
                 if rc != 0:
                     _cabi.check(rc, "mia_letkf_sharded_step_streams_f32 (launch thread)")
-                self.last_batch_n = h.batch_n = slot["bn"].value
-                if p["timing"] is not None:
-                    self.kernel_batch[p["timing"]] = h.batch_n
                 cnt = list(slot["out8"])
                 p["waited"] = True
             else:
@@ -1268,18 +1261,15 @@ class ShardedLetkf:
         self._time_next = True
 
     def kernel_ms(self):
-        """Mean duration (ms) of the analysis LAUNCHES timed so far inside real steps, or None.  With launch coalescing
-        (option ``step_coalesce``) a launch holds the tiles of :meth:`kernel_steps_per_launch` steps."""
+        """Mean duration (ms) of the analysis LAUNCHES timed so far inside real steps, or None."""
         if not self.kernel_timings:
             return None
         torch.cuda.synchronize(self.device)
         return sum(a.elapsed_time(b) for a, b in self.kernel_timings) / len(self.kernel_timings)
 
     def kernel_steps_per_launch(self):
-        """Mean number of steps in the launches :meth:`kernel_ms` averages over (1.0 without coalescing)."""
-        if not self.kernel_timings:
-            return 1.0
-        return sum(self.kernel_batch.get(t, 1) for t in self.kernel_timings) / len(self.kernel_timings)
+        """Always 1.0: every step has an analysis launch of its own; bench.py reads the value."""
+        return 1.0
 
     def mean_degree(self):
         """Mean Chebyshev degree of the last matfun launch (flags bits 8-15), None for the eigensolver route."""
