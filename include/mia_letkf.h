@@ -367,6 +367,34 @@ int mia_letkf_analysis_retry_f32(const float* X, int64_t ldx, int m, int k, int6
                                  int p_cap, int p_max, float inf_factor, float gamma,
                                  float* Xa, int64_t ldo, int64_t o0, int32_t* flags, void* stream);
 
+/* The eigensolver-free route in FLOAT64, on tiles of sixteen grid points (csrc/letkf_tile64.hip): what the drop-in classes
+ * run in their default working precision (pytassim/interface/base.py:68,73,106-118).  Replaces the same reference code as
+ * mia_letkf_analysis_packed_f64 -- ETKFModule (core/etkf.py:57-103) under wrapper_localization (interface/wrapper.py:86-98)
+ * followed by _apply_weights (interface/base.py:257-278) -- with the matrix functions of mia_letkf_analysis_matfun_f32
+ * applied by a Chebyshev recurrence whose every product is a v_mfma_f64_16x16x4_f64.  Same argument meaning as
+ * mia_letkf_analysis_packed_f64 (float64 records of mia_letkf_pack_obs_f64, per-point lists of any metric); flags and
+ * retry_count are required.  gamma must be <= 0 (MIA_ERR_UNSUPPORTED otherwise: the float64 RBF filter stays on
+ * mia_letkf_analysis_packed_f64).  Shapes: 2 <= k <= 64, p_max <= k, any m; everything else returns MIA_ERR_UNSUPPORTED
+ * before any launch, as does the option "tile" = 0 (the A/B switch, shared with the float32 tile route) and a stream that is
+ * being captured while the float64 coefficient table does not exist yet (this route has no in-kernel coefficients: the
+ * caller takes mia_letkf_analysis_packed_f64, as before this route existed).  The table's truncation target is exp(-26)
+ * and its degree cap 127; the option "cheb_dmax" belongs to the float32 tables and does NOT apply here.  Points above
+ * the cap get MIA_FLAG_RETRY, are counted in *retry_count (device int32, zeroed by the caller) and left untouched in Xa;
+ * mia_letkf_analysis_retry_f64 -- the Jacobi kernel restricted to the flagged points -- redoes them.
+ * mia_letkf_matfun_f64_cover: 1 when the shape is inside the route, 0 when not (host only, no device work). */
+int mia_letkf_analysis_matfun_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
+                                  const double* rec, int64_t P,
+                                  const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w,
+                                  int p_cap, int p_max, double inf_factor, double gamma,
+                                  double* Xa, int64_t ldo, int64_t o0, int32_t* flags, int32_t* retry_count,
+                                  void* stream);
+int mia_letkf_analysis_retry_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
+                                 const double* rec, int64_t P,
+                                 const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w,
+                                 int p_cap, int p_max, double inf_factor, double gamma,
+                                 double* Xa, int64_t ldo, int64_t o0, int32_t* flags, void* stream);
+int mia_letkf_matfun_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P);
+
 /* Kernelised variant: KETKFModule with RBFKernel(gamma) (core/ketkf.py:65-94,
  * kernels/rbf.py:75-81,110-111), same localisation and transform (LKETKF,
  * interface/lketkf.py:77). */

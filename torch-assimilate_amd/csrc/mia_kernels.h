@@ -54,6 +54,16 @@ int tile_split_analysis_launch(const float* X, int64_t ldx, int m, int k, int64_
                                int32_t* retry_count, int dmax, const int2* tab_hdr, const float2* tab_c, hipStream_t stream,
                                int seg_len, int64_t seg_stride, int32_t* done);
 
+// letkf_tile64.hip: the float64 analysis with sixteen grid points per wavefront, every product a v_mfma_f64_16x16x4_f64
+// (dual route, 2 <= k <= 64, p_max <= k, any number of state rows), from float64 records and per-point lists.
+// tile64_route_covers: shape test (host only); tile64_analysis_launch: MIA_ERR_UNSUPPORTED outside it, with the option
+// tile = 0, and when the float64 coefficient table cannot be had (stream being captured).
+bool tile64_route_covers(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t ng);
+int tile64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t ng, const double* rec,
+                           const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                           double inf_factor, double* Xa, int64_t ldo, int64_t o0, int32_t* flags, int32_t* retry_count,
+                           hipStream_t stream);
+
 // Completion event for the next tile-kernel launch of this thread (set by the step driver around the analysis call of a
 // step in flight): the launch then carries the event in its own dispatch packet (hipExtLaunchKernel) instead of the caller
 // recording a marker packet behind it -- one packet less between two kernels of the analysis queue.  Cleared by the launch

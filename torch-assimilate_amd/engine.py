@@ -569,8 +569,9 @@ class LetkfEngine:
 
         ``method``: "eig" = fused Jacobi eigensolver kernel (always available, the only one that can
         return the weights); "matfun" = eigensolver-free Chebyshev matrix-function route (float32, few
-        state rows, no weights), with the eigensolver redoing the grid points it declines; "auto" picks
-        matfun when it applies.  With ``defer_retry`` the (8-byte, synchronising) read of the decline
+        state rows, no weights), with the eigensolver redoing the grid points it declines; "matfun64" =
+        the same route in float64 on tiles of sixteen points (2 <= k <= 64, p_max <= k, plain ETKF core,
+        no weights); "auto" picks matfun / matfun64 by the state's dtype when it applies.  With ``defer_retry`` the (8-byte, synchronising) read of the decline
         counter is left to the caller: the return value gains a trailing callable that must be invoked.
         ``retry`` (1 int32, zeroed by the caller) / ``flags`` (n int32): caller-owned counter and flag
         buffers, e.g. one counter shared by the launches of several sub-ranges.
@@ -590,8 +591,8 @@ class LetkfEngine:
             self._keep_rec = rec      # (a record buffer packed during HIP-graph capture must outlive the capture)
         if rec.dtype != dtype or rec.shape[1] != (k + 1 + 3) // 4 * 4:
             raise ValueError("packed records do not match the state's dtype / ensemble size")
-        if method not in ("auto", "eig", "matfun"):
-            raise ValueError("method must be 'auto', 'eig' or 'matfun'")
+        if method not in ("auto", "eig", "matfun", "matfun64"):
+            raise ValueError("method must be 'auto', 'eig', 'matfun' or 'matfun64'")
         P = rec.shape[0]
         n = nbrs.g1 - nbrs.g0
         if out is None:
@@ -651,9 +652,30 @@ class LetkfEngine:
         can_matfun = dtype == torch.float32 and not return_weights and n > 0
         if method == "matfun" and not can_matfun:
             raise ValueError("the matfun route needs float32 and cannot return the weights")
+        # float64 on tiles (csrc/letkf_tile64.hip): plain ETKF core, no weights.  "auto" falls back to the Jacobi kernel
+        # where the shape is outside the route; "matfun64" names the route and raises there instead.
+        can_matfun64 = dtype == torch.float64 and not return_weights and rbf_gamma is None
+        if method == "matfun64" and not can_matfun64:
+            raise ValueError("the matfun64 route needs float64, the plain ETKF core and cannot return the weights")
         use_matfun = can_matfun and (method == "matfun" or (method == "auto" and m <= self.MATFUN_MAX_ROWS))
         finish = None
-        if use_matfun:
+        if can_matfun64 and n > 0 and method in ("auto", "matfun64"):
+            if retry is None:
+                retry = torch.zeros(1, dtype=torch.int32, device=self.device)
+            rc = self.lib.mia_letkf_analysis_matfun_f64(*args, _ptr(flags), _ptr(retry), self._stream())
+            if rc == -3 and method == "auto":      # shape outside the tile kernel (or tile = 0): the Jacobi kernel below
+                pass
+            else:
+                _cabi.check(rc, "mia_letkf_analysis_matfun_f64")
+                use_matfun = True
+
+                def finish():
+                    n_retry = int(retry.item())          # host sync (8 bytes)
+                    if n_retry:
+                        _cabi.check(self.lib.mia_letkf_analysis_retry_f64(*args, _ptr(flags), self._stream()),
+                                    "mia_letkf_analysis_retry_f64")
+                    return n_retry
+        elif use_matfun:
             if retry is None:
                 retry = torch.zeros(1, dtype=torch.int32, device=self.device)
             rc = self.lib.mia_letkf_analysis_matfun_f32(*args, _ptr(flags), _ptr(retry), self._stream())

@@ -54,8 +54,10 @@ class ETKF:
         self.post_transform = post_transform
         self.weight_save_path = weight_save_path
         self.forward_model = forward_model
-        # the reference's working precision: float64 unless the caller says otherwise (interface/base.py:68,73).  The float32
-        # tile kernels -- the benchmarked hot path -- are chosen with an explicit dtype=torch.float32
+        # the reference's working precision: float64 unless the caller says otherwise (interface/base.py:68,73).  The local
+        # analysis then runs on the float64 tile kernel (csrc/letkf_tile64.hip: per-point lists, every product on the matrix
+        # cores) where its shape is covered, on the Jacobi kernel otherwise; an explicit dtype=torch.float32 chooses the
+        # float32 tile kernels and the step driver -- the benchmarked hot path
         self._dtype = torch.float64
         self.dtype = dtype
         self._engine = engine
@@ -334,7 +336,9 @@ class LETKF(ETKF):
         """The fused analysis on the TILE route -- tile lists from the built-in metric, then letkf_tile2_kernel / letkf_tile2p_kernel
         (plain ETKF core: split records) or lketkf_tile_kernel (RBF / Gauss kernel: the perturbations themselves) -- where it
         applies: float32, a built-in distance, a shape the kernels take (mia_letkf_tiles_cover).  Declined points are redone by
-        the eigensolver kernel from the per-point lists.  Returns (Xa, flags) or None: the caller takes the per-point route."""
+        the eigensolver kernel from the per-point lists.  Returns (Xa, flags) or None: the caller takes the per-point route
+        (float64, the default dtype: ``engine.analysis(method="auto")`` forms the tiles' unions itself from the per-point lists of
+        any metric and runs letkf_tile64_kernel; no explicit ``dtype=torch.float32`` is needed to reach a tile kernel)."""
         eng = self.engine
         ka = self._kernel_args()
         gamma = ka.get("rbf_gamma")
