@@ -672,7 +672,7 @@ int mia_event_destroy(void* event);
  * analysis / exchange / read-back stage) and the number of steps handed to them. */
 int mia_letkf_step_launch_stats(double* prep_us, double* rest_us, long long* steps);
 int mia_comm_set_place_stream(mia_comm_t* comm, void* stream);
-/* Direct exchange (csrc/sharded_step.hip, "Direct exchange"): library-owned, peer-mapped result buffers, so that every rank
+/* Direct exchange (csrc/step_comm.hip, "Direct exchange"): library-owned, peer-mapped result buffers, so that every rank
  * writes its block of the analysis ensemble straight into all peers' (m, k, G) result over its xGMI links -- no ring, no
  * staging, no placement copy.  No reference counterpart (the reference's only distribution is dask on one host,
  * interface/letkf.py:118-131).

@@ -8,10 +8,16 @@
 // etkf.py:169-207); the reference has no multi-device path, its unit of distribution is the
 // dask chunk of grid points (letkf.py:118-131), which is the block / chunk here.
 //
-// RCCL is bound at run time (dlopen of the library the process already uses, normally torch's bundled
-// librccl.so) so that this library keeps loading on machines without RCCL and never pulls in a second
-// HIP runtime.
-#include <dlfcn.h>
+// The file in reading order: the workspace layout; events, the per-workspace table and the once-per-step StepDecision; the small
+// stream / event entries; the step itself -- its arguments as one block (mia_step_args_t) plus a StepState, and step_impl as
+//   step_plan     every decision that follows from the arguments, the layout and the communicator
+//   step_decide   the step's decision about its workspace, taken where the preparation is enqueued, and what follows from it
+//   step_prepare  phase 0, stage 1: clears, records / index / lists on the preparation stream, the ordering events
+//   step_analyse  phase 0, stage 2: the waits, the one-launch-over-pieces forms, analyse_piece per piece
+//   step_redo     phase 1: declined points, piece by piece
+//   exchange_piece  wait or segment wait, all-gather, placement
+// -- the entries that fill a block from positional parameters; the launch threads and the submitted-step entries.
+// The communicator, the placement kernel and the direct peer exchange are step_comm.hip (mia_step_comm.h).
 #include <array>
 #include <atomic>
 #include <chrono>
@@ -28,260 +34,12 @@
 #include "mia_kernels.h"
 #include "mia_options.h"
 #include "mia_pack_dev.h"
+#include "mia_step_comm.h"
 #include "mia_tiles.h"
 
-// ---- the few RCCL declarations needed (ABI of rccl.h 2.x: opaque comm, 128-byte id, C enums)
-typedef struct ncclComm* ncclComm_t;
-typedef struct { char internal[128]; } ncclUniqueId;
-enum { kNcclSuccess = 0, kNcclInt32 = 2, kNcclFloat32 = 7, kNcclMax = 2, kNcclUint8 = 1 };
-typedef int (*pfn_ncclGetUniqueId)(ncclUniqueId*);
-typedef int (*pfn_ncclCommInitRank)(ncclComm_t*, int, ncclUniqueId, int);
-typedef int (*pfn_ncclCommDestroy)(ncclComm_t);
-typedef int (*pfn_ncclAllGather)(const void*, void*, size_t, int, ncclComm_t, hipStream_t);
-typedef int (*pfn_ncclAllReduce)(const void*, void*, size_t, int, int, ncclComm_t, hipStream_t);
-typedef const char* (*pfn_ncclGetErrorString)(int);
+using mia::kMaxChunks;
 
 namespace {
-
-struct RcclApi {
-  void* handle = nullptr;
-  pfn_ncclGetUniqueId GetUniqueId = nullptr;
-  pfn_ncclCommInitRank CommInitRank = nullptr;
-  pfn_ncclCommDestroy CommDestroy = nullptr;
-  pfn_ncclAllGather AllGather = nullptr;
-  pfn_ncclAllReduce AllReduce = nullptr;
-  pfn_ncclGetErrorString GetErrorString = nullptr;
-} g_rccl;
-
-char g_comm_error[512] = "";
-
-void set_error(const char* what, int code) {
-  const char* msg = (g_rccl.GetErrorString && code > 0) ? g_rccl.GetErrorString(code) : "";
-  snprintf(g_comm_error, sizeof(g_comm_error), "%s (code %d) %s", what, code, msg);
-}
-
-constexpr int kMaxChunks = 16;   // pieces per block; events: [c] piece c, [kMaxChunks-1] records packed (pieces <= 15)
-constexpr int kMaxRanks = 16, kMaxSlots = 8;     // direct exchange: ranks of one node, steps in flight
-// synchronisation area of one rank, in uint32 words: per slot [kMaxRanks] ready, [kMaxRanks] free, [kMaxRanks][4] counters
-constexpr int kSyncSlotWords = kMaxRanks * 6;
-constexpr size_t kSyncBytes = (size_t)kMaxSlots * kSyncSlotWords * sizeof(uint32_t);
-
-}  // namespace
-
-struct mia_comm {
-  int rank = 0, world = 1;
-  ncclComm_t nccl = nullptr;
-  mia_allgather_fn ag = nullptr;
-  mia_allreduce_max_i32_fn ar = nullptr;
-  void* ctx = nullptr;
-  hipEvent_t ev[kMaxChunks + 2] = {};
-  hipEvent_t evp[kMaxChunks] = {};      // piece c gathered (exchange stream -> placement stream)
-  hipStream_t place_stream = nullptr;   // optional: mia_comm_set_place_stream
-  int n_ev = 0;
-  // ---- direct (peer-mapped) exchange, see "Direct exchange" below
-  int peer_slots = 0;                    // result buffers this rank owns (one per step in flight)
-  size_t peer_bytes = 0;                 // bytes of one result buffer
-  float* peer_buf[kMaxRanks][kMaxSlots] = {};   // [rank][slot]: rank's result buffers as mapped into this process
-  uint32_t* peer_sync[kMaxRanks] = {};   // [rank]: its synchronisation area (fine-grained device memory)
-  bool peer_owned = false;               // buffers of `rank` were allocated by mia_comm_peer_alloc (freed on destroy)
-  bool peer_opened[kMaxRanks] = {};      // mapped through hipIpcOpenMemHandle (closed on destroy)
-  int peer_ready = 0;                    // every rank attached
-  uint32_t peer_seq[kMaxSlots] = {};     // exchanges done per slot (the sequence number the flags carry)
-  // bound of the device-side waits for the peers' flags, in polls of ~1-2 us (mia_comm_peer_wait_bound).  Ranks of a real run
-  // drift apart by seconds (I/O of one rank between steps, a first-step table build, a debugger): the default is ~1 minute --
-  // an RCCL collective would simply wait; a waiter that gives up raises error bit 2, it never hangs the grid
-  int peer_wait_polls = 1 << 25;
-};
-
-namespace {
-
-int comm_events(mia_comm* c) {
-  if (c->n_ev) return MIA_OK;
-  for (int i = 0; i < kMaxChunks + 2; ++i) MIA_HIP_TRY(hipEventCreateWithFlags(&c->ev[i], hipEventDisableTiming));
-  for (int i = 0; i < kMaxChunks; ++i) MIA_HIP_TRY(hipEventCreateWithFlags(&c->evp[i], hipEventDisableTiming));
-  c->n_ev = kMaxChunks + 2;
-  return MIA_OK;
-}
-
-int comm_allgather(mia_comm* c, const void* send, void* recv, size_t bytes, hipStream_t s) {
-  if (c->ag) return c->ag(c->ctx, send, recv, bytes, (void*)s) == 0 ? MIA_OK : MIA_ERR_COMM;
-  int rc = g_rccl.AllGather(send, recv, bytes, kNcclUint8, c->nccl, s);
-  if (rc != kNcclSuccess) { set_error("ncclAllGather failed", rc); return MIA_ERR_COMM; }
-  return MIA_OK;
-}
-
-int comm_allreduce_max(mia_comm* c, int32_t* buf, int n, hipStream_t s) {
-  if (c->ar) return c->ar(c->ctx, buf, n, (void*)s) == 0 ? MIA_OK : MIA_ERR_COMM;
-  int rc = g_rccl.AllReduce(buf, buf, (size_t)n, kNcclInt32, kNcclMax, c->nccl, s);
-  if (rc != kNcclSuccess) { set_error("ncclAllReduce failed", rc); return MIA_ERR_COMM; }
-  return MIA_OK;
-}
-
-// gathered chunk [world][rows][nc]  ->  result rows [rows][G] at columns r * n + off + i
-// (i < nc, off + i < n, column < G).  x: column (4 per thread when everything is 4-aligned), y: row, z: rank.
-// Every rank's piece carries a 16-byte trailer {longest list, truncated lists, declined points, error bits};
-// with ctr_out the first thread also folds the trailers: ctr_out[0..3] = this rank's, [4..7] = max over ranks
-// (the all-reduce of the redo decision rides on the last piece's all-gather instead of being a collective).
-// Single-wave workgroups, four column groups per lane: with steps in flight this kernel runs beside a later step's
-// analysis kernel, which fills every SIMD's register file -- a lone wave takes the slot of the next analysis wave that
-// retires, a 4-wave workgroup waits for one to retire on every SIMD of a CU at once (see localize.hip).
-constexpr int kPlaceThreads = 64, kPlaceUnroll = 4;
-template <int VEC>
-__global__ void __launch_bounds__(kPlaceThreads) place_chunk_kernel(const float* __restrict__ gath, float* __restrict__ out,
-                                                          int64_t G, int64_t n, int64_t off, int nc, int rows,
-                                                          size_t rank_stride /* floats */, int32_t* ctr_out, int rank) {
-  const int r = blockIdx.z, row = blockIdx.y;
-  if (ctr_out && blockIdx.x == 0 && row == 0 && r == 0 && threadIdx.x < 4) {
-    int mx = 0, own = 0;
-    for (int q = 0; q < (int)gridDim.z; ++q) {
-      const int v = reinterpret_cast<const int32_t*>(gath + (size_t)q * rank_stride + (size_t)rows * nc)[threadIdx.x];
-      mx = q == 0 ? v : (threadIdx.x == 3 ? (mx | v) : (v > mx ? v : mx));
-      if (q == rank) own = v;
-    }
-    ctr_out[threadIdx.x] = own;
-    ctr_out[4 + threadIdx.x] = mx;
-  }
-#pragma unroll
-  for (int u = 0; u < kPlaceUnroll; ++u) {
-  const int i = ((blockIdx.x * kPlaceUnroll + u) * kPlaceThreads + threadIdx.x) * VEC;
-  if (i >= nc) return;
-  const int64_t in_block = off + i;
-  const int64_t col = (int64_t)r * n + in_block;
-  const float* src = gath + (size_t)r * rank_stride + (size_t)row * (size_t)nc + i;
-  float* dst = out + (size_t)row * (size_t)G + col;
-  if (VEC == 4) {
-    if (in_block + 3 < n && col + 3 < G) {
-      *reinterpret_cast<float4*>(dst) = *reinterpret_cast<const float4*>(src);
-      continue;
-    }
-  }
-#pragma unroll
-  for (int v = 0; v < VEC; ++v)
-    if (i + v < nc && in_block + v < n && col + v < G) dst[v] = src[v];
-  }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Direct exchange.  The all-gather of the analysis ensemble moves world x (m k n) floats into every rank; RCCL's ring
-// forwards each block hop by hop (per-link bound, (world - 1) latencies) into a staging buffer that a placement kernel then
-// copies into the (m, k, G) result.  xGMI is point to point, so every rank can instead WRITE ITS BLOCK STRAIGHT INTO THE
-// RESULT BUFFER OF ALL PEERS, over its world - 1 links at once: the result buffers are library-owned, exported with
-// hipIpcGetMemHandle and mapped by every rank of the node.  Per step and slot, with sequence number q:
-//   submit       free[slot][me] = q in every peer's sync area: "my buffer `slot` may be overwritten for step q" (its previous
-//                result was collected, or the caller would not reuse the slot)
-//   analysis     this rank's block, written into its own result buffer (no staging)
-//   exchange stream:  wait  free[slot][p] >= q for all peers
-//                     push  block (16-byte accesses) + this rank's four redo counters -> every peer
-//                     signal ready[slot][me] = q in every peer's sync area (a kernel of its own: the push kernel's end is the
-//                            system-scope release of its stores)
-//                     wait  ready[slot][p] >= q for all peers; fold the counters (max over ranks)
-// Flags live in fine-grained device memory and are accessed with system-scope atomics; waits are bounded (error bit 1 of
-// counters[3] / [7], never a hung grid).  No collective, no staging copy, no placement kernel: 2 x block bytes of local HBM
-// traffic instead of 2 x world x block.  RCCL stays the fallback (and the route of the first, exact-list step).
-struct PeerPtrs { float* buf[kMaxRanks]; uint32_t* sync[kMaxRanks]; };
-
-__global__ void __launch_bounds__(64) peer_flag_kernel(PeerPtrs pp, int world, int word, uint32_t value) {
-  const int p = threadIdx.x;      // one lane per rank (own area included: keeps the arithmetic uniform)
-  if (p < world) __hip_atomic_store(pp.sync[p] + word, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-__global__ void __launch_bounds__(64) peer_wait_kernel(const uint32_t* flags /* [kMaxRanks] of this rank's area */, int world,
-                                                       int rank, uint32_t seq, int32_t* err, int max_polls,
-                                                       const int32_t* ctr_all /* [kMaxRanks][4] or null */, int32_t* counters) {
-  const int p = threadIdx.x;
-  bool ok = false;
-  for (int poll = 0; poll < max_polls; ++poll) {
-    const uint32_t v = (p < world && p != rank) ? __hip_atomic_load(flags + p, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) : seq;
-    ok = (int32_t)(v - seq) >= 0;
-    if (__all(ok)) break;
-    __builtin_amdgcn_s_sleep(32);
-  }
-  if (!__all(ok) && p == 0) atomicOr(err, 2);      // exit condition every wave reaches: ~seconds, then report
-  if (ctr_all && p < 4) {                             // redo decision: max over the ranks' counters (or of the error bits)
-    int mx = 0;
-    for (int q = 0; q < world; ++q) {
-      const int v = __hip_atomic_load(ctr_all + q * 4 + p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      mx = q == 0 ? v : (p == 3 ? (mx | v) : (v > mx ? v : mx));
-    }
-    counters[4 + p] = p == 3 ? (mx | counters[3]) : mx;
-  }
-}
-
-// block [rows][n] at column b0 of the (rows, G) result -> the same place in every peer's buffer; blockIdx.z = peer
-__global__ void __launch_bounds__(256) peer_push_kernel(PeerPtrs pp, int world, int rank, int64_t G, int64_t b0, int64_t n,
-                                                        int rows, int slot_word0, const int32_t* own_counters) {
-  int peer = blockIdx.z;
-  if (peer >= rank) ++peer;                           // (world - 1 peers)
-  const float* src = pp.buf[rank] + (size_t)blockIdx.y * G + b0;
-  float* dst = pp.buf[peer] + (size_t)blockIdx.y * G + b0;
-  if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < 4) {      // this rank's counters: to the peer, and (once) to itself
-    const int32_t v = own_counters[threadIdx.x];
-    __hip_atomic_store(reinterpret_cast<int32_t*>(pp.sync[peer]) + slot_word0 + 2 * kMaxRanks + 4 * rank + threadIdx.x, v,
-                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    if (blockIdx.z == 0)
-      __hip_atomic_store(reinterpret_cast<int32_t*>(pp.sync[rank]) + slot_word0 + 2 * kMaxRanks + 4 * rank + threadIdx.x, v,
-                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-  // 16-byte accesses where source and destination rows are aligned alike (b0, G multiples of 4), scalars otherwise
-  const bool vec = ((G | b0) & 3) == 0 && ((reinterpret_cast<uintptr_t>(pp.buf[rank]) | reinterpret_cast<uintptr_t>(pp.buf[peer])) & 15) == 0;
-  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  if (vec) {
-    const int64_t n4 = n >> 2;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride)
-      reinterpret_cast<float4*>(dst)[i] = reinterpret_cast<const float4*>(src)[i];
-    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] = src[i];
-  } else {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) dst[i] = src[i];
-  }
-}
-
-int peer_slot_of(const mia_comm* c, const float* Xa) {
-  if (!c || !c->peer_ready) return -1;
-  for (int s = 0; s < c->peer_slots; ++s)
-    if (c->peer_buf[c->rank][s] == Xa) return s;
-  return -1;
-}
-
-PeerPtrs peer_ptrs(const mia_comm* c, int slot) {
-  PeerPtrs pp;
-  for (int r = 0; r < kMaxRanks; ++r) {
-    pp.buf[r] = r < c->world ? c->peer_buf[r][slot] : nullptr;
-    pp.sync[r] = r < c->world ? c->peer_sync[r] : nullptr;
-  }
-  return pp;
-}
-
-// first half of an exchange: new sequence number, "my buffer of this slot may be overwritten" to every peer (stream ps)
-int peer_begin(mia_comm* c, int slot, hipStream_t ps, uint32_t* seq_out) {
-  const uint32_t seq = ++c->peer_seq[slot];
-  peer_flag_kernel<<<1, 64, 0, ps>>>(peer_ptrs(c, slot), c->world, slot * kSyncSlotWords + kMaxRanks + c->rank, seq);
-  MIA_LAUNCH_CHECK();
-  *seq_out = seq;
-  return MIA_OK;
-}
-
-// second half, on the exchange stream cs (the caller has ordered it behind the block's producer): wait for the peers'
-// buffers, push block [rows][b0, b1) and the four counters, signal, wait for the peers' blocks, fold the counters
-int peer_finish(mia_comm* c, int slot, uint32_t seq, int64_t G, int64_t b0, int64_t b1, int rows, int32_t* counters,
-                hipStream_t cs) {
-  const int world = c->world, rank = c->rank, sw0 = slot * kSyncSlotWords;
-  const PeerPtrs pp = peer_ptrs(c, slot);
-  const uint32_t* my = c->peer_sync[rank] + sw0;
-  peer_wait_kernel<<<1, 64, 0, cs>>>(my + kMaxRanks, world, rank, seq, counters + 3, c->peer_wait_polls, nullptr, nullptr);
-  MIA_LAUNCH_CHECK();
-  const int64_t nb = b1 > b0 ? b1 - b0 : 0;
-  unsigned gx = (unsigned)((nb / 4 + 255) / 256);
-  gx = gx < 1 ? 1 : (gx > 64 ? 64 : gx);
-  peer_push_kernel<<<dim3(gx, (unsigned)(nb ? rows : 1), (unsigned)(world - 1)), 256, 0, cs>>>(pp, world, rank, G, nb ? b0 : 0, nb,
-                                                                                          rows, sw0, counters);
-  MIA_LAUNCH_CHECK();
-  peer_flag_kernel<<<1, 64, 0, cs>>>(pp, world, sw0 + rank, seq);
-  MIA_LAUNCH_CHECK();
-  peer_wait_kernel<<<1, 64, 0, cs>>>(my, world, rank, seq, counters + 3, c->peer_wait_polls,
-                                     reinterpret_cast<const int32_t*>(my + 2 * kMaxRanks), counters);
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
-}
 
 struct StepLayout {
   size_t rec, loc, cnt, idx, w, done, bufs, gath, total;
@@ -334,321 +92,6 @@ int step_layout(int64_t G, int m, int k, int64_t P, int n_coord, int world, int 
 
 }  // namespace
 
-static int prep_event_fwd(hipEvent_t* ev);      // (ring of ordering events, defined with the step driver below)
-
-extern "C" const char* mia_comm_last_error(void) { return g_comm_error; }
-
-extern "C" int mia_comm_load(const char* rccl_path) {
-  if (g_rccl.handle) return MIA_OK;
-  const char* path = (rccl_path && rccl_path[0]) ? rccl_path : "librccl.so";
-  void* h = dlopen(path, RTLD_NOW | RTLD_GLOBAL);
-  if (!h) {
-    snprintf(g_comm_error, sizeof(g_comm_error), "dlopen(%s) failed: %s", path, dlerror());
-    return MIA_ERR_COMM;
-  }
-  RcclApi api;
-  api.handle = h;
-  api.GetUniqueId = (pfn_ncclGetUniqueId)dlsym(h, "ncclGetUniqueId");
-  api.CommInitRank = (pfn_ncclCommInitRank)dlsym(h, "ncclCommInitRank");
-  api.CommDestroy = (pfn_ncclCommDestroy)dlsym(h, "ncclCommDestroy");
-  api.AllGather = (pfn_ncclAllGather)dlsym(h, "ncclAllGather");
-  api.AllReduce = (pfn_ncclAllReduce)dlsym(h, "ncclAllReduce");
-  api.GetErrorString = (pfn_ncclGetErrorString)dlsym(h, "ncclGetErrorString");
-  if (!api.GetUniqueId || !api.CommInitRank || !api.CommDestroy || !api.AllGather || !api.AllReduce) {
-    snprintf(g_comm_error, sizeof(g_comm_error), "%s does not export the RCCL collectives", path);
-    return MIA_ERR_COMM;
-  }
-  g_rccl = api;
-  return MIA_OK;
-}
-
-extern "C" int mia_comm_unique_id(void* id128) {
-  if (!id128) return MIA_ERR_NULL;
-  if (!g_rccl.handle) { set_error("mia_comm_load was not called", 0); return MIA_ERR_COMM; }
-  ncclUniqueId id;
-  int rc = g_rccl.GetUniqueId(&id);
-  if (rc != kNcclSuccess) { set_error("ncclGetUniqueId failed", rc); return MIA_ERR_COMM; }
-  memcpy(id128, id.internal, 128);
-  return MIA_OK;
-}
-
-extern "C" int mia_comm_create(const void* id128, int rank, int world, mia_comm_t** out) {
-  if (!id128 || !out) return MIA_ERR_NULL;
-  if (world <= 0 || rank < 0 || rank >= world) return MIA_ERR_SIZE;
-  if (!g_rccl.handle) { set_error("mia_comm_load was not called", 0); return MIA_ERR_COMM; }
-  ncclUniqueId id;
-  memcpy(id.internal, id128, 128);
-  mia_comm* c = new mia_comm();
-  c->rank = rank;
-  c->world = world;
-  int rc = g_rccl.CommInitRank(&c->nccl, world, id, rank);
-  if (rc != kNcclSuccess) { set_error("ncclCommInitRank failed", rc); delete c; return MIA_ERR_COMM; }
-  *out = c;
-  return MIA_OK;
-}
-
-extern "C" int mia_comm_create_custom(int rank, int world, mia_allgather_fn allgather,
-                                      mia_allreduce_max_i32_fn allreduce_max, void* ctx, mia_comm_t** out) {
-  if (!allgather || !allreduce_max || !out) return MIA_ERR_NULL;
-  if (world <= 0 || rank < 0 || rank >= world) return MIA_ERR_SIZE;
-  mia_comm* c = new mia_comm();
-  c->rank = rank;
-  c->world = world;
-  c->ag = allgather;
-  c->ar = allreduce_max;
-  c->ctx = ctx;
-  *out = c;
-  return MIA_OK;
-}
-
-// a communicator that only carries the block partition (rank, world): for steps whose analysis STAYS block-sharded
-// (MIA_STEP_NO_GATHER -- what the reference's dask chunks along `grid` do, interface/letkf.py:118-131); no exchange can run on it
-extern "C" int mia_comm_create_partition(int rank, int world, mia_comm_t** out) {
-  if (!out) return MIA_ERR_NULL;
-  if (world <= 0 || rank < 0 || rank >= world) return MIA_ERR_SIZE;
-  mia_comm* c = new mia_comm();
-  c->rank = rank;
-  c->world = world;
-  *out = c;
-  return MIA_OK;
-}
-
-extern "C" int mia_comm_set_place_stream(mia_comm_t* c, void* stream) {
-  if (!c) return MIA_ERR_NULL;
-  c->place_stream = (hipStream_t)stream;
-  return MIA_OK;
-}
-
-// ---- direct exchange: buffers, handles, attachment (protocol: see "Direct exchange" above)
-extern "C" int mia_comm_peer_alloc(mia_comm_t* c, size_t result_bytes, int n_slots, void* ipc_handles_out) {
-  if (!c) return MIA_ERR_NULL;
-  if (n_slots < 1 || n_slots > kMaxSlots || result_bytes == 0 || c->world > kMaxRanks) return MIA_ERR_SIZE;
-  if (c->peer_slots) return MIA_ERR_UNSUPPORTED;          // one allocation per communicator
-  (void)hipGetLastError();
-  hipIpcMemHandle_t* hs = reinterpret_cast<hipIpcMemHandle_t*>(ipc_handles_out);
-  static_assert(sizeof(hipIpcMemHandle_t) == 64, "the handle table of mia_comm_peer_alloc / _open is 64 bytes per entry");
-  for (int s = 0; s < n_slots; ++s) {
-    void* b = nullptr;
-    if (hipMalloc(&b, mia::align_up(result_bytes, 256)) != hipSuccess) { set_error("hipMalloc of a result buffer failed", 0); (void)hipGetLastError(); return MIA_ERR_COMM; }
-    c->peer_buf[c->rank][s] = (float*)b;
-    c->peer_slots = s + 1;
-    c->peer_owned = true;
-    if (hs && hipIpcGetMemHandle(&hs[s], b) != hipSuccess) { set_error("hipIpcGetMemHandle(result buffer) failed", 0); (void)hipGetLastError(); return MIA_ERR_COMM; }
-  }
-  void* sy = nullptr;
-  if (hipExtMallocWithFlags(&sy, kSyncBytes, hipDeviceMallocFinegrained) != hipSuccess) { set_error("fine-grained allocation of the sync area failed", 0); (void)hipGetLastError(); return MIA_ERR_COMM; }
-  c->peer_sync[c->rank] = (uint32_t*)sy;
-  if (hipMemset(sy, 0, kSyncBytes) != hipSuccess) { (void)hipGetLastError(); return MIA_ERR_COMM; }
-  if (hs && hipIpcGetMemHandle(&hs[n_slots], sy) != hipSuccess) { set_error("hipIpcGetMemHandle(sync area) failed", 0); (void)hipGetLastError(); return MIA_ERR_COMM; }
-  c->peer_bytes = result_bytes;
-  if (c->world == 1) c->peer_ready = 1;
-  return MIA_OK;
-}
-
-static void peer_check_ready(mia_comm* c) {
-  int ok = c->peer_slots > 0;
-  for (int r = 0; r < c->world && ok; ++r) {
-    ok = c->peer_sync[r] != nullptr;
-    for (int s = 0; s < c->peer_slots && ok; ++s) ok = c->peer_buf[r][s] != nullptr;
-  }
-  c->peer_ready = ok;
-}
-
-// all_handles: [world][n_slots + 1] handles as every rank's mia_comm_peer_alloc filled them (any all-gather of the host's)
-extern "C" int mia_comm_peer_open(mia_comm_t* c, const void* all_handles) {
-  if (!c || !all_handles) return MIA_ERR_NULL;
-  if (!c->peer_slots) return MIA_ERR_SIZE;
-  (void)hipGetLastError();
-  const hipIpcMemHandle_t* hs = reinterpret_cast<const hipIpcMemHandle_t*>(all_handles);
-  const int per = c->peer_slots + 1;
-  for (int r = 0; r < c->world; ++r) {
-    if (r == c->rank) continue;
-    for (int s = 0; s < per; ++s) {
-      void* ptr = nullptr;
-      if (hipIpcOpenMemHandle(&ptr, hs[(size_t)r * per + s], hipIpcMemLazyEnablePeerAccess) != hipSuccess) {
-        set_error("hipIpcOpenMemHandle failed", r);
-        (void)hipGetLastError();
-        return MIA_ERR_COMM;
-      }
-      if (s < c->peer_slots) c->peer_buf[r][s] = (float*)ptr; else c->peer_sync[r] = (uint32_t*)ptr;
-    }
-    c->peer_opened[r] = true;
-  }
-  peer_check_ready(c);
-  return c->peer_ready ? MIA_OK : MIA_ERR_COMM;
-}
-
-// in-process attachment of a peer's buffers (ranks that share an address space: tests, one process driving several GPUs)
-extern "C" int mia_comm_peer_attach(mia_comm_t* c, int peer, void* const* result_bufs, void* sync_area) {
-  if (!c || !result_bufs || !sync_area) return MIA_ERR_NULL;
-  if (peer < 0 || peer >= c->world || peer == c->rank || !c->peer_slots) return MIA_ERR_SIZE;
-  for (int s = 0; s < c->peer_slots; ++s) c->peer_buf[peer][s] = (float*)result_bufs[s];
-  c->peer_sync[peer] = (uint32_t*)sync_area;
-  peer_check_ready(c);
-  return MIA_OK;
-}
-
-extern "C" int mia_comm_peer_wait_bound(mia_comm_t* c, int log2_polls) {
-  if (!c) return MIA_ERR_NULL;
-  if (log2_polls < 10 || log2_polls > 30) return MIA_ERR_SIZE;
-  c->peer_wait_polls = 1 << log2_polls;
-  return MIA_OK;
-}
-
-extern "C" void* mia_comm_peer_buffer(mia_comm_t* c, int slot) {
-  return (c && slot >= 0 && slot < c->peer_slots) ? (void*)c->peer_buf[c->rank][slot] : nullptr;
-}
-extern "C" void* mia_comm_peer_sync_area(mia_comm_t* c) { return c ? (void*)c->peer_sync[c->rank] : nullptr; }
-
-// The exchange alone: block [rows][b0, b1) of result buffer `slot` (already written by work enqueued on `stream`) goes to
-// every peer; when `stream` has passed this call, the peers' blocks have landed in this rank's buffer and counters[4..7]
-// hold the maximum over the ranks of everybody's counters[0..3] (device int32[8]).  All ranks call it in the same order.
-extern "C" int mia_comm_peer_exchange(mia_comm_t* c, int slot, int rows, int64_t G, int64_t b0, int64_t b1, int32_t* counters,
-                                      void* stream) {
-  if (!c || !counters) return MIA_ERR_NULL;
-  if (!c->peer_ready || slot < 0 || slot >= c->peer_slots || rows < 1 || G < 1 || b0 < 0 || b1 > G) return MIA_ERR_SIZE;
-  if ((size_t)rows * G * sizeof(float) > c->peer_bytes) return MIA_ERR_SIZE;
-  if (c->world == 1) return MIA_OK;
-  (void)hipGetLastError();
-  uint32_t seq = 0;
-  int rc = peer_begin(c, slot, (hipStream_t)stream, &seq);
-  if (rc != MIA_OK) return rc;
-  return peer_finish(c, slot, seq, G, b0, b1, rows, counters, (hipStream_t)stream);
-}
-
-// A waiter of the last exchange on `slot` gave up (error bit 2 of counters[3] / [7]): wait AGAIN for the peers' ready flags of that
-// exchange and fold the counters once more -- a peer that has not raised its flag within the bound is late (a first-step table
-// build, I/O between two steps, a debugger), and its push does not depend on anything this rank does.  Clears error bit 2 first; it
-// is set again if this wait gives up too.  The caller decides how often to come back before it calls the peer dead.
-__global__ void __launch_bounds__(64) peer_clear_timeout_kernel(int32_t* counters) {
-  if (threadIdx.x == 0) { counters[3] &= ~2; counters[7] &= ~2; }
-}
-extern "C" int mia_comm_peer_rewait(mia_comm_t* c, int slot, int32_t* counters, void* stream) {
-  if (!c || !counters) return MIA_ERR_NULL;
-  if (!c->peer_ready || slot < 0 || slot >= c->peer_slots) return MIA_ERR_SIZE;
-  if (c->world == 1) return MIA_OK;
-  (void)hipGetLastError();
-  hipStream_t cs = (hipStream_t)stream;
-  const uint32_t* my = c->peer_sync[c->rank] + slot * kSyncSlotWords;
-  peer_clear_timeout_kernel<<<1, 64, 0, cs>>>(counters);
-  MIA_LAUNCH_CHECK();
-  peer_wait_kernel<<<1, 64, 0, cs>>>(my, c->world, c->rank, c->peer_seq[slot], counters + 3, c->peer_wait_polls,
-                                     reinterpret_cast<const int32_t*>(my + 2 * kMaxRanks), counters);
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
-}
-
-extern "C" int mia_comm_destroy(mia_comm_t* c) {
-  if (!c) return MIA_OK;
-  for (int r = 0; r < c->world && r < kMaxRanks; ++r) {
-    if (r == c->rank || !c->peer_opened[r]) continue;
-    for (int s = 0; s < c->peer_slots; ++s) if (c->peer_buf[r][s]) (void)hipIpcCloseMemHandle(c->peer_buf[r][s]);
-    if (c->peer_sync[r]) (void)hipIpcCloseMemHandle(c->peer_sync[r]);
-  }
-  if (c->peer_owned) {
-    for (int s = 0; s < c->peer_slots; ++s) if (c->peer_buf[c->rank][s]) (void)hipFree(c->peer_buf[c->rank][s]);
-    if (c->peer_sync[c->rank]) (void)hipFree(c->peer_sync[c->rank]);
-  }
-  (void)hipGetLastError();
-  for (int i = 0; i < c->n_ev; ++i) (void)hipEventDestroy(c->ev[i]);
-  if (c->n_ev)
-    for (int i = 0; i < kMaxChunks; ++i) (void)hipEventDestroy(c->evp[i]);
-  if (c->nccl && g_rccl.CommDestroy) g_rccl.CommDestroy(c->nccl);
-  delete c;
-  return MIA_OK;
-}
-
-// Host-overhead helpers of the pipelined step loop (one ctypes call each instead of five torch calls): the eight counters
-// of a step are copied to pinned host memory on `on_stream` once `after_stream` has passed its current point, and an event
-// the library owns (created on first use, reused by the caller for the same slot) marks the copy's completion.
-extern "C" int mia_letkf_step_readback(const int32_t* counters, int32_t* host8, void* after_stream, void* on_stream,
-                                       void** done_event) {
-  if (!counters || !host8 || !done_event) return MIA_ERR_NULL;
-  (void)hipGetLastError();
-  hipStream_t a = (hipStream_t)after_stream, o = (hipStream_t)on_stream;
-  hipEvent_t ev = (hipEvent_t)*done_event;
-  if (!ev) {
-    MIA_HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    *done_event = (void*)ev;
-  }
-  if (a != o) {
-    hipEvent_t pe;
-    int rc = prep_event_fwd(&pe);
-    if (rc != MIA_OK) return rc;
-    MIA_HIP_TRY(hipEventRecord(pe, a));
-    MIA_HIP_TRY(hipStreamWaitEvent(o, pe, 0));
-  }
-  MIA_HIP_TRY(hipMemcpyAsync(host8, counters, 8 * sizeof(int32_t), hipMemcpyDeviceToHost, o));
-  MIA_HIP_TRY(hipEventRecord(ev, o));
-  return MIA_OK;
-}
-static int readback_after_event(const int32_t* counters, int32_t* host8, hipEvent_t after, void* on_stream, void** done_event) {
-  if (!counters || !host8 || !done_event || !after) return MIA_ERR_NULL;
-  (void)hipGetLastError();
-  hipStream_t o = (hipStream_t)on_stream;
-  hipEvent_t ev = (hipEvent_t)*done_event;
-  if (!ev) {
-    MIA_HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    *done_event = (void*)ev;
-  }
-  MIA_HIP_TRY(hipStreamWaitEvent(o, after, 0));
-  MIA_HIP_TRY(hipMemcpyAsync(host8, counters, 8 * sizeof(int32_t), hipMemcpyDeviceToHost, o));
-  MIA_HIP_TRY(hipEventRecord(ev, o));
-  return MIA_OK;
-}
-extern "C" int mia_event_synchronize(void* event) {
-  if (!event) return MIA_ERR_NULL;
-  MIA_HIP_TRY(hipEventSynchronize((hipEvent_t)event));
-  return MIA_OK;
-}
-// `dst` waits for everything enqueued on `src` so far (an event of the caller's, created on first use): the two runtime calls
-// of torch's Stream.wait_stream without its per-call Python objects (~8 us of a ~25 us submit)
-extern "C" int mia_stream_wait_stream(void* dst_stream, void* src_stream, void** event_io) {
-  if (!event_io) return MIA_ERR_NULL;
-  (void)hipGetLastError();
-  if (!*event_io) {
-    hipEvent_t e = nullptr;
-    MIA_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    *event_io = (void*)e;
-  }
-  MIA_HIP_TRY(hipEventRecord((hipEvent_t)*event_io, (hipStream_t)src_stream));
-  MIA_HIP_TRY(hipStreamWaitEvent((hipStream_t)dst_stream, (hipEvent_t)*event_io, 0));
-  return MIA_OK;
-}
-
-extern "C" int mia_stream_wait_event(void* stream, void* event) {
-  if (!event) return MIA_ERR_NULL;
-  MIA_HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)event, 0));
-  return MIA_OK;
-}
-extern "C" int mia_event_destroy(void* event) {
-  if (event) (void)hipEventDestroy((hipEvent_t)event);
-  return MIA_OK;
-}
-
-extern "C" int mia_letkf_sharded_step_workspace_bytes(int64_t G, int m, int k, int64_t P, int n_coord, int world,
-                                                      int n_chunks, int p_max_assumed, size_t* bytes) {
-  if (!bytes) return MIA_ERR_NULL;
-  StepLayout L;
-  int rc = step_layout(G, m, k, P, n_coord, world, n_chunks, p_max_assumed, &L);
-  if (rc != MIA_OK) return rc;
-  *bytes = L.total;
-  return MIA_OK;
-}
-
-extern "C" int mia_letkf_sharded_step_f32(const float* X, int64_t G, int m, int k,
-                                          const float* Yb, const float* d, int64_t P,
-                                          const double* grid_xyz, const double* obs_xyz, int n_coord,
-                                          const int32_t* coord_group, const double* gc_c, int n_r, double gc_eps,
-                                          float inf_factor, float gamma, int method, int p_max_assumed,
-                                          mia_comm_t* comm, int n_chunks, int phase,
-                                          float* Xa, int32_t* flags, int32_t* counters,
-                                          void* ws, size_t ws_bytes, void* stream, void* comm_stream) {
-  return mia_letkf_sharded_step_streams_f32(X, G, m, k, Yb, d, P, grid_xyz, obs_xyz, n_coord, coord_group, gc_c, n_r,
-                                            gc_eps, inf_factor, gamma, method, p_max_assumed, comm, n_chunks, phase, Xa,
-                                            flags, counters, ws, ws_bytes, stream, comm_stream, nullptr, 0);
-}
-
 namespace {
 // one-shot profiling hook (mia_letkf_step_timing_events)
 thread_local hipEvent_t t_time_start = nullptr, t_time_stop = nullptr;
@@ -678,21 +121,12 @@ int prep_event(hipEvent_t* ev) {
 }
 }  // namespace
 
-static int prep_event_fwd(hipEvent_t* ev) { return prep_event(ev); }
-
 extern "C" int mia_letkf_step_timing_events(void* start_event, void* stop_event) {
   if ((start_event == nullptr) != (stop_event == nullptr)) return MIA_ERR_NULL;
   t_time_start = (hipEvent_t)start_event;
   t_time_stop = (hipEvent_t)stop_event;
   return MIA_OK;
 }
-
-// stage 0: the whole step.  The launch threads split it: stage 1 = what goes to the preparation stream (free flags of the
-// direct exchange, records, index, lists) up to the event that orders the analysis behind it (*pe_io, *seq_io out);
-// stage 2 = everything from that wait on (analysis, exchange), with *pe_io / *seq_io as stage 1 left them.
-constexpr int kStepPrepDone = 0x100;      // internal step flag: the launch thread has waited for the preparation on the host
-
-static inline char* base_of(void* ws) { return (char*)ws; }
 
 // what the tile lists held by a step workspace were built for (geometry epochs, MIA_STEP_REUSE_LISTS)
 struct GeomStamp {
@@ -778,77 +212,227 @@ static bool count_arrays_clean_for_scan(void* ws) {
   return false;
 }
 
-// the coordinates of a step's period argument that check_period reads (a step with a bad n_coord is refused later, as MIA_ERR_SIZE)
-static inline int period_coords(int n_coord) { return n_coord >= 1 && n_coord <= MIA_MAX_COORD ? n_coord : 0; }
+// Host-overhead helpers of the pipelined step loop (one ctypes call each instead of five torch calls): the eight counters
+// of a step are copied to pinned host memory on `on_stream` once `after_stream` has passed its current point, and an event
+// the library owns (created on first use, reused by the caller for the same slot) marks the copy's completion.
+extern "C" int mia_letkf_step_readback(const int32_t* counters, int32_t* host8, void* after_stream, void* on_stream,
+                                       void** done_event) {
+  if (!counters || !host8 || !done_event) return MIA_ERR_NULL;
+  (void)hipGetLastError();
+  hipStream_t a = (hipStream_t)after_stream, o = (hipStream_t)on_stream;
+  hipEvent_t ev = (hipEvent_t)*done_event;
+  if (!ev) {
+    MIA_HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    *done_event = (void*)ev;
+  }
+  if (a != o) {
+    hipEvent_t pe;
+    int rc = prep_event(&pe);
+    if (rc != MIA_OK) return rc;
+    MIA_HIP_TRY(hipEventRecord(pe, a));
+    MIA_HIP_TRY(hipStreamWaitEvent(o, pe, 0));
+  }
+  MIA_HIP_TRY(hipMemcpyAsync(host8, counters, 8 * sizeof(int32_t), hipMemcpyDeviceToHost, o));
+  MIA_HIP_TRY(hipEventRecord(ev, o));
+  return MIA_OK;
+}
+static int readback_after_event(const int32_t* counters, int32_t* host8, hipEvent_t after, void* on_stream, void** done_event) {
+  if (!counters || !host8 || !done_event || !after) return MIA_ERR_NULL;
+  (void)hipGetLastError();
+  hipStream_t o = (hipStream_t)on_stream;
+  hipEvent_t ev = (hipEvent_t)*done_event;
+  if (!ev) {
+    MIA_HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    *done_event = (void*)ev;
+  }
+  MIA_HIP_TRY(hipStreamWaitEvent(o, after, 0));
+  MIA_HIP_TRY(hipMemcpyAsync(host8, counters, 8 * sizeof(int32_t), hipMemcpyDeviceToHost, o));
+  MIA_HIP_TRY(hipEventRecord(ev, o));
+  return MIA_OK;
+}
+extern "C" int mia_event_synchronize(void* event) {
+  if (!event) return MIA_ERR_NULL;
+  MIA_HIP_TRY(hipEventSynchronize((hipEvent_t)event));
+  return MIA_OK;
+}
+// `dst` waits for everything enqueued on `src` so far (an event of the caller's, created on first use): the two runtime calls
+// of torch's Stream.wait_stream without its per-call Python objects (~8 us of a ~25 us submit)
+extern "C" int mia_stream_wait_stream(void* dst_stream, void* src_stream, void** event_io) {
+  if (!event_io) return MIA_ERR_NULL;
+  (void)hipGetLastError();
+  if (!*event_io) {
+    hipEvent_t e = nullptr;
+    MIA_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    *event_io = (void*)e;
+  }
+  MIA_HIP_TRY(hipEventRecord((hipEvent_t)*event_io, (hipStream_t)src_stream));
+  MIA_HIP_TRY(hipStreamWaitEvent((hipStream_t)dst_stream, (hipEvent_t)*event_io, 0));
+  return MIA_OK;
+}
 
-static int step_impl(const float* X, int64_t G, int m, int k, const float* Yb, const float* d, int64_t P,
-                     const double* grid_xyz, const double* obs_xyz, int n_coord, const int32_t* coord_group,
-                     const double* gc_c, int n_r, double gc_eps, float inf_factor, float gamma, int method, int p_max_assumed,
-                     mia_comm_t* comm, int n_chunks, int phase, float* Xa, int32_t* flags, int32_t* counters, void* ws,
-                     size_t ws_bytes, void* stream, void* comm_stream, void* prep_stream, int step_flags, int stage,
-                     hipEvent_t* pe_io, uint32_t* seq_io, hipEvent_t t_start, hipEvent_t t_stop, hipEvent_t* kdone_out,
-                     StepDecision* dec_io, const double* period) {
-  const bool do1 = stage != 2, do2 = stage != 1;
-  if (kdone_out) *kdone_out = nullptr;
-  // (period: checked by the entry, nullptr = open -- every index build of the step takes it)
-  if (!X || !Xa || !flags || !counters || !ws || !grid_xyz || !coord_group || !gc_c) return MIA_ERR_NULL;
-  if (P > 0 && (!Yb || !d || !obs_xyz)) return MIA_ERR_NULL;
-  if (method < 0 || method > 2 || (phase != 0 && phase != 1)) return MIA_ERR_SIZE;
-  if ((uintptr_t)ws % 256) return MIA_ERR_ALIGN;
-  const int world = comm ? comm->world : 1, rank = comm ? comm->rank : 0;
-  if (!comm) n_chunks = 1;
+extern "C" int mia_stream_wait_event(void* stream, void* event) {
+  if (!event) return MIA_ERR_NULL;
+  MIA_HIP_TRY(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)event, 0));
+  return MIA_OK;
+}
+extern "C" int mia_event_destroy(void* event) {
+  if (event) (void)hipEventDestroy((hipEvent_t)event);
+  return MIA_OK;
+}
+
+extern "C" int mia_letkf_sharded_step_workspace_bytes(int64_t G, int m, int k, int64_t P, int n_coord, int world,
+                                                      int n_chunks, int p_max_assumed, size_t* bytes) {
+  if (!bytes) return MIA_ERR_NULL;
+  StepLayout L;
+  int rc = step_layout(G, m, k, P, n_coord, world, n_chunks, p_max_assumed, &L);
+  if (rc != MIA_OK) return rc;
+  *bytes = L.total;
+  return MIA_OK;
+}
+
+extern "C" int mia_letkf_sharded_step_f32(const float* X, int64_t G, int m, int k,
+                                          const float* Yb, const float* d, int64_t P,
+                                          const double* grid_xyz, const double* obs_xyz, int n_coord,
+                                          const int32_t* coord_group, const double* gc_c, int n_r, double gc_eps,
+                                          float inf_factor, float gamma, int method, int p_max_assumed,
+                                          mia_comm_t* comm, int n_chunks, int phase,
+                                          float* Xa, int32_t* flags, int32_t* counters,
+                                          void* ws, size_t ws_bytes, void* stream, void* comm_stream) {
+  return mia_letkf_sharded_step_streams_f32(X, G, m, k, Yb, d, P, grid_xyz, obs_xyz, n_coord, coord_group, gc_c, n_r,
+                                            gc_eps, inf_factor, gamma, method, p_max_assumed, comm, n_chunks, phase, Xa,
+                                            flags, counters, ws, ws_bytes, stream, comm_stream, nullptr, 0);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The step.  Its arguments travel as ONE block (mia_step_args_t, include/mia_letkf.h) from the ABI boundary to the last launch;
+// beside it a step carries only its own state (StepState).  step_impl is: plan, decide, then prepare | analyse | redo, each piece
+// of the exchange route through exchange_piece.
+constexpr int kStepPrepDone = 0x100;      // internal step flag: the launch thread has waited for the preparation on the host
+
+// What a step carries from call to call besides its arguments: the one-call form makes one on its stack, a step in flight keeps it in
+// its job.  stage 0: the whole step.  The launch threads split it: stage 1 = what goes to the preparation stream (free flags of the
+// direct exchange, records, index, lists) up to the event that orders the analysis behind it (pe, seq out); stage 2 = everything
+// from that wait on (analysis, exchange), with pe / seq as stage 1 left them.
+struct StepState {
+  int stage = 0;
+  int flags = 0;                   // the block's step_flags as this call takes them (the one-call block entry drops MIA_STEP_NO_JOIN,
+                                   // the analysis thread adds kStepPrepDone): set where a step enters, copied into the plan
+                                   // (StepPlan::flags), which is what the parts read
+  hipEvent_t pe = nullptr;         // the preparation is enqueued (recorded on the preparation stream when that is a stream of its own)
+  uint32_t seq = 0;                // sequence number of the direct exchange
+  hipEvent_t kdone = nullptr;      // completion event carried by the analysis launch itself (stage 2), if any
+  StepDecision dec;                // what stage 1 decided about the workspace's lists and count arrays, for stage 2
+};
+
+static inline bool step_tables_fit(int n_coord, int n_r) {      // (the block's coordinate-group, radius and period arrays)
+  return n_coord >= 1 && n_coord <= MIA_MAX_COORD && n_r >= 1 && n_r <= MIA_MAX_RADII;
+}
+// the period of a block in the internal convention of the index builds (check_period): the block's array where some coordinate is
+// cyclic, nullptr where none is; MIA_ERR_ARG unless every entry is finite and >= 0.  (A block with a bad n_coord is refused by the
+// plan, as MIA_ERR_SIZE: no entry is read.)
+static inline int step_period(const mia_step_args_t& a, const double** period) {
+  const int n = a.n_coord >= 1 && a.n_coord <= MIA_MAX_COORD ? a.n_coord : 0;
+  return mia::check_period(a.period, n, period) != MIA_OK ? MIA_ERR_ARG : MIA_OK;
+}
+
+// Every decision of a step that follows from its arguments, the layout and the communicator -- evaluated identically by stage 1,
+// stage 2 and a redo call (phase 1) of the same step -- and, once step_decide has run, what follows from the step's decision.
+struct StepPlan {
+  StepLayout L;
+  int flags;                       // the step's flags as this call takes them (StepState::flags): what every part reads,
+                                   // never the block's step_flags
+  int world, rank, n_chunks;       // (n_chunks: pieces actually taken -- one without a communicator, with NO_GATHER, on the peer route)
+  int peer_slot, extra, pm_tl, rows;
   // exchange route: any real multi-rank world; a one-rank communicator takes it only when chunking is asked
   // for (lets a single-GPU box drive the RCCL calls and the chunk pipeline)
   // direct exchange: Xa is one of the communicator's peer-mapped result buffers (every rank passes the same slot)
   // MIA_STEP_NO_GATHER: this rank analyses its block of the partition and keeps it -- Xa is the block, (m k, block length),
   // nothing is exchanged and no counter is reduced over the ranks (every rank validates its own step)
-  const bool no_gather = comm && (step_flags & MIA_STEP_NO_GATHER) != 0;
-  if (no_gather) n_chunks = 1;
-  if (comm && !no_gather && world > 1 && !comm->nccl && !comm->ag) return MIA_ERR_COMM;      // (a partition-only communicator)
-  const int peer_slot = (comm && world > 1 && !no_gather) ? peer_slot_of(comm, Xa) : -1;
-  const bool peer = peer_slot >= 0;
-  if (peer) n_chunks = 1;
-  const bool exch = comm && !peer && !no_gather && (world > 1 || n_chunks > 1);
-  StepLayout L;
-  int rc = step_layout(G, m, k, P, n_coord, world, n_chunks, p_max_assumed, &L, (step_flags >> 4) & 7);
+  bool no_gather, peer, exch;
+  bool signal_mode;                // MIA_SEGMENT_SIGNAL=0: one launch + one event per piece instead of the segmented launch (fallback / A-B runs)
+  bool lazy, tl_route, tl_rbf, tl_bucket, want_fused, eig_only;
+  int64_t b0, b1;                  // this rank's block of grid points
+  hipStream_t s, cs, ps;           // analysis, exchange, preparation (records, index, lists)
+  const double* period;            // nullptr = open -- every index build of the step takes it
+  const int2* tl_th;               // coefficient table of the tile kernels
+  const float2* tl_tc;
+  GeomStamp stamp;
+  char* base;                      // the workspace and its parts
+  float* rec;
+  int32_t *cnt, *idx, *done, *ctr;
+  double* w;
+  size_t gath_stride, done_ints;
+  // ---- from the step's decision (step_decide)
+  bool tl_reuse, tl_fused, cnt_must_clear, zero_in_kernel, carried;
+  int* tl_counts;
+  mia::Tile2Housekeeping tl_hk;
+  const mia::Tile2Housekeeping* hk;      // &tl_hk where the analysis launch does the housekeeping, else nullptr
+  mia::Tile2Loc tl_loc;
+  const mia::Tile2Loc* loc;              // &tl_loc where the analysis wavefronts localise, else nullptr
+};
+
+static int step_plan(const mia_step_args_t& a, const StepState& st, StepPlan* plan) {
+  StepPlan& p = *plan;
+  if (step_period(a, &p.period) != MIA_OK) return MIA_ERR_ARG;
+  if (!a.X || !a.Xa || !a.flags || !a.counters || !a.ws || !a.grid_xyz) return MIA_ERR_NULL;
+  if (a.P > 0 && (!a.Yb || !a.d || !a.obs_xyz)) return MIA_ERR_NULL;
+  if (a.method < 0 || a.method > 2 || (a.phase != 0 && a.phase != 1)) return MIA_ERR_SIZE;
+  if ((uintptr_t)a.ws % 256) return MIA_ERR_ALIGN;
+  if (!step_tables_fit(a.n_coord, a.n_r)) return MIA_ERR_SIZE;
+  mia_comm* comm = a.comm;
+  const int m = a.m, k = a.k, flags = p.flags = st.flags;
+  const int64_t G = a.G, P = a.P;
+  p.world = comm ? comm->world : 1;
+  p.rank = comm ? comm->rank : 0;
+  p.n_chunks = comm ? a.n_chunks : 1;
+  p.no_gather = comm && (flags & MIA_STEP_NO_GATHER) != 0;
+  if (p.no_gather) p.n_chunks = 1;
+  if (comm && !p.no_gather && p.world > 1 && !comm->nccl && !comm->ag) return MIA_ERR_COMM;      // (a partition-only communicator)
+  p.peer_slot = (comm && p.world > 1 && !p.no_gather) ? mia::peer_slot_of(comm, a.Xa) : -1;
+  p.peer = p.peer_slot >= 0;
+  if (p.peer) p.n_chunks = 1;
+  p.exch = comm && !p.peer && !p.no_gather && (p.world > 1 || p.n_chunks > 1);
+  p.extra = (flags >> 4) & 7;      // MIA_STEP_TILE_EXTRA
+  StepLayout& L = p.L;
+  int rc = step_layout(G, m, k, P, a.n_coord, p.world, p.n_chunks, a.p_max_assumed, &L, p.extra);
   if (rc != MIA_OK) return rc;
-  if (ws_bytes < L.total) return MIA_ERR_WORKSPACE;
-  if ((exch || peer) && !comm_stream) return MIA_ERR_NULL;
-  if (peer && (size_t)m * k * G * sizeof(float) > comm->peer_bytes) return MIA_ERR_SIZE;
-  hipStream_t s = (hipStream_t)stream, cs = (hipStream_t)comm_stream;
-  hipStream_t ps = prep_stream ? (hipStream_t)prep_stream : s;      // records, index, lists
-  // MIA_SEGMENT_SIGNAL=0: one launch + one event per piece instead of the segmented launch (fallback / A-B runs)
-  const bool signal_mode = mia::option(MIA_OPT_SEGMENT_SIGNAL) != 0;
+  if (a.ws_bytes < L.total) return MIA_ERR_WORKSPACE;
+  if ((p.exch || p.peer) && !a.comm_stream) return MIA_ERR_NULL;
+  if (p.peer && (size_t)m * k * G * sizeof(float) > comm->peer_bytes) return MIA_ERR_SIZE;
+  p.s = (hipStream_t)a.stream;
+  p.cs = (hipStream_t)a.comm_stream;
+  p.ps = a.prep_stream ? (hipStream_t)a.prep_stream : p.s;
+  p.signal_mode = mia::option(MIA_OPT_SEGMENT_SIGNAL) != 0;
+  p.b0 = (int64_t)p.rank * L.n < G ? (int64_t)p.rank * L.n : G;
+  p.b1 = p.b0 + L.n < G ? p.b0 + L.n : G;
+  const int64_t blk = p.b1 - p.b0;
+  p.pm_tl = a.p_max_assumed < L.cap ? a.p_max_assumed : L.cap;
+  p.eig_only = a.method == 1;   // auto = matfun at every m (it wins at every m measured, tools/time_rows.py)
+  p.rows = m * k;
   // Lazy sort: when the block's analysis is ONE plain launch that the sixteen-points-per-wavefront kernel will take -- it
   // ranks every tile's union by observation index itself, so the order inside a neighbour list means nothing to it -- the
   // observation index is built WITHOUT its per-cell sort (one kernel and one launch gap less in the preparation chain), and
   // only a redo of declined points (phase 1: the eigensolver kernel, which sums in list order) first puts the lists of
   // exactly those points into the order a sorted index gives.  The rule is evaluated from the call's arguments, so phase 0
-  // and phase 1 of a step agree; the analysis call below is checked against it.
-  const int64_t blk = (int64_t)rank * L.n < G ? (((int64_t)rank * L.n + L.n < G ? (int64_t)rank * L.n + L.n : G) - (int64_t)rank * L.n) : 0;
-  const bool lazy = mia::option(MIA_OPT_STEP_LAZY_SORT) != 0 && !exch && n_chunks == 1 && method != 1 && blk > 0 && P > 0 &&
-                    L.cap <= 128 &&
-                    mia::cheb_tile_will_serve(m, k, p_max_assumed < L.cap ? p_max_assumed : L.cap, L.cap, gamma, G, G, blk,
-                                              (hipStream_t)(prep_stream ? prep_stream : stream));
+  // and phase 1 of a step agree; the analysis call is checked against it (analyse_piece).
+  p.lazy = mia::option(MIA_OPT_STEP_LAZY_SORT) != 0 && !p.exch && p.n_chunks == 1 && !p.eig_only && blk > 0 && P > 0 && L.cap <= 128 &&
+           mia::cheb_tile_will_serve(m, k, p.pm_tl, L.cap, a.gamma, G, G, blk, p.ps);
   // Tile route (round 3): the localisation kernel emits tile-shaped lists (union + sqrt(rho) matrix per sixteen points), the
   // records are packed as scaled half pairs, and letkf_tile2_kernel analyses from both -- no per-point lists are written or
   // read.  Taken when the block's analysis is one plain launch of a shape the kernel covers; a tile whose union does not fit
   // its slots is counted in counters[1] and the caller repeats the step with MIA_STEP_NO_TILE_LISTS (scattered grids).
   // Declined points (phase 1) are redone from per-point lists built then, over the index this step left in its workspace.
-  const int pm_tl = p_max_assumed < L.cap ? p_max_assumed : L.cap;
-  const int2* tl_th = nullptr;
-  const float2* tl_tc = nullptr;
+  p.tl_th = nullptr;
+  p.tl_tc = nullptr;
   // (gamma > 0: the RBF-kernelised filter on the same tile lists -- lketkf_tile_kernel reads Yb and d themselves, no records)
-  const bool tl_rbf = gamma > 0.0f;
-  const bool tl_route = mia::option(MIA_OPT_TILE_LISTS) != 0 && !(step_flags & MIA_STEP_NO_TILE_LISTS) && (n_chunks == 1 || exch) &&
-                        method != 1 && blk > 0 && P > 0 && L.ut <= 6 && mia::option(MIA_OPT_TILE) != 0 &&
-                        (tl_rbf ? mia::lketkf_tile_covers(m, k, pm_tl, (step_flags >> 4) & 7, G, exch ? L.nc : (no_gather ? blk : G), blk, P) &&
-                                      mia::cheb_primal_table((hipStream_t)(prep_stream ? prep_stream : stream), &tl_th, &tl_tc)
-                                : mia::option(MIA_OPT_TILE_SPLIT) != 0 &&
-                                      mia::tile2_covers(m, k, pm_tl, (step_flags >> 4) & 7, G, exch ? L.nc : (no_gather ? blk : G), blk) &&
-                                      mia::tile2_records_addressable(k, P) &&
-                                      mia::cheb_dual_table((hipStream_t)(prep_stream ? prep_stream : stream), &tl_th, &tl_tc));
-  const bool tl_bucket = tl_route && mia::option(MIA_OPT_BUCKET_INDEX) != 0 && !(step_flags & MIA_STEP_SCAN_INDEX);
+  p.tl_rbf = a.gamma > 0.0f;
+  const int64_t ldo = p.exch ? L.nc : (p.no_gather ? blk : G);
+  p.tl_route = mia::option(MIA_OPT_TILE_LISTS) != 0 && !(flags & MIA_STEP_NO_TILE_LISTS) && (p.n_chunks == 1 || p.exch) && !p.eig_only &&
+               blk > 0 && P > 0 && L.ut <= 6 && mia::option(MIA_OPT_TILE) != 0 &&
+               (p.tl_rbf ? mia::lketkf_tile_covers(m, k, p.pm_tl, p.extra, G, ldo, blk, P) && mia::cheb_primal_table(p.ps, &p.tl_th, &p.tl_tc)
+                         : mia::option(MIA_OPT_TILE_SPLIT) != 0 && mia::tile2_covers(m, k, p.pm_tl, p.extra, G, ldo, blk) &&
+                               mia::tile2_records_addressable(k, P) && mia::cheb_dual_table(p.ps, &p.tl_th, &p.tl_tc));
+  p.tl_bucket = p.tl_route && mia::option(MIA_OPT_BUCKET_INDEX) != 0 && !(flags & MIA_STEP_SCAN_INDEX);
   // geometry epoch: the tile lists this workspace holds are used again (the caller vouches for unchanged coordinates, radii,
   // eps and block); only the split records are rebuilt.  Nothing to clear after the analysis: no index was built
   // ... and the library checks what it can: a stamp of what this workspace's lists were built for (route, format, block, radii,
@@ -857,332 +441,402 @@ static int step_impl(const float* X, int64_t G, int m, int k, const float* Yb, c
   // Fused localisation (letkf_tile2f.hip): the analysis wavefronts build their tiles' lists themselves over the bucket index -- no
   // list kernel, no lists in memory (the workspace's stamp says so: route 0).  Not when the caller declares a geometry epoch: the
   // lists are what an epoch keeps.
-  const bool want_fused = tl_route && tl_bucket && !tl_rbf && !(step_flags & (MIA_STEP_REUSE_LISTS | MIA_STEP_KEEP_LISTS)) &&
-                          mia::option(MIA_OPT_TILE_FUSED) != 0 && mia::tile2f_covers(m, k, L.ut, n_coord);
-  GeomStamp stamp_now;
-  memset(&stamp_now, 0, sizeof stamp_now);
-  stamp_now.route = (tl_route && !want_fused) ? (tl_rbf ? 2 : 1) : 0;
-  stamp_now.ut = L.ut; stamp_now.bucket = tl_bucket ? 1 : 0; stamp_now.n_coord = n_coord; stamp_now.n_r = n_r;
-  stamp_now.G = G; stamp_now.P = P; stamp_now.rank = rank; stamp_now.world = world; stamp_now.k = k; stamp_now.eps = gc_eps;
-  for (int i = 0; i < n_r && i < MIA_MAX_RADII; ++i) stamp_now.rc[i] = gc_c[i];
-  for (int i = 0; i < n_coord && i < MIA_MAX_COORD; ++i) stamp_now.cg[i] = coord_group[i];
-  for (int i = 0; i < n_coord && i < MIA_MAX_COORD; ++i) stamp_now.per[i] = period ? period[i] : 0.0;
-  // (decided once per step -- where its preparation is enqueued; the analysis stage and a redo of declined points read the decision)
-  StepDecision dec_local;
-  StepDecision& D = dec_io ? *dec_io : dec_local;
-  if (phase == 0 && do1) {
-    D.reuse = geom_reuse_decision(ws, stamp_now, tl_route && (step_flags & MIA_STEP_REUSE_LISTS) != 0, true);
-    count_array_decision(ws, true, tl_bucket && !D.reuse, want_fused && !D.reuse, &D.cnt_use, &D.fused, &D.must_clear);
-    D.set = true;
-  } else if (!D.set) {      // (a redo of declined points, phase 1: a call of its own -- what the table still knows)
-    D.reuse = geom_reuse_decision(ws, stamp_now, false, false);
-    count_array_decision(ws, false, false, false, &D.cnt_use, &D.fused, &D.must_clear);
-  }
-  const bool tl_reuse = D.reuse, tl_fused = D.fused, cnt_must_clear = D.must_clear;
-  const int cnt_use = D.cnt_use;
-  // (the analysis launch puts the OTHER per-cell count array and the build's error word back to zero, see Tile2Params / GeomEntry)
-  mia::Tile2Housekeeping tl_hk{nullptr, nullptr, nullptr, nullptr};
-  int* tl_counts = nullptr;
-  if (tl_bucket && !tl_reuse) {
-    const mia::IndexLayout IL = mia::index_layout(base_of(ws) + L.loc, P, n_coord);
-    tl_counts = cnt_use ? IL.start : IL.cursor;
-    tl_hk = mia::Tile2Housekeeping{cnt_use ? IL.cursor : IL.start, &IL.hdr->ncell, &IL.hdr->err, nullptr};      // (err_out: below, once ctr is known)
-  }
+  p.want_fused = p.tl_route && p.tl_bucket && !p.tl_rbf && !(flags & (MIA_STEP_REUSE_LISTS | MIA_STEP_KEEP_LISTS)) &&
+                 mia::option(MIA_OPT_TILE_FUSED) != 0 && mia::tile2f_covers(m, k, L.ut, a.n_coord);
+  GeomStamp& stamp = p.stamp;
+  memset(&stamp, 0, sizeof stamp);
+  stamp.route = (p.tl_route && !p.want_fused) ? (p.tl_rbf ? 2 : 1) : 0;
+  stamp.ut = L.ut; stamp.bucket = p.tl_bucket ? 1 : 0; stamp.n_coord = a.n_coord; stamp.n_r = a.n_r;
+  stamp.G = G; stamp.P = P; stamp.rank = p.rank; stamp.world = p.world; stamp.k = k; stamp.eps = a.gc_eps;
+  for (int i = 0; i < a.n_r; ++i) stamp.rc[i] = a.gc_c[i];
+  for (int i = 0; i < a.n_coord; ++i) stamp.cg[i] = a.coord_group[i];
+  for (int i = 0; i < a.n_coord; ++i) stamp.per[i] = p.period ? p.period[i] : 0.0;
+  p.base = (char*)a.ws;
+  p.rec = (float*)(p.base + L.rec);
+  p.cnt = (int32_t*)(p.base + L.cnt);
+  p.idx = (int32_t*)(p.base + L.idx);
+  p.w = (double*)(p.base + L.w);
+  p.done = (int32_t*)(p.base + L.done);
+  p.gath_stride = mia::align_up(L.send_bytes * p.world, 256);
+  p.done_ints = (size_t)p.n_chunks * 64 * mia::kSlotStride;
+  // exchange route: the redo counters live in the trailer of the last piece and travel with its all-gather
+  p.ctr = p.exch ? (int32_t*)(p.base + L.bufs + L.chunk_bytes * (p.n_chunks - 1) + (size_t)p.rows * L.nc * sizeof(float)) : a.counters;
   // a step in flight whose analysis is ONE plain launch (stage 2 after the host-side wait): the launch carries its completion
   // (and timing) events in its own dispatch packet
-  const bool carried = kdone_out && phase == 0 && !exch && !peer && n_chunks == 1 && method != 1 && (step_flags & kStepPrepDone) &&
-                       (!t_start == !t_stop);
-  char* base = (char*)ws;
-  float* rec = (float*)(base + L.rec);
-  int32_t* cnt = (int32_t*)(base + L.cnt);
-  int32_t* idx = (int32_t*)(base + L.idx);
-  double* w = (double*)(base + L.w);
-  const int64_t b0 = (int64_t)rank * L.n < G ? (int64_t)rank * L.n : G;
-  const int64_t b1 = b0 + L.n < G ? b0 + L.n : G;
-  const bool eig_only = method == 1;   // auto = matfun at every m (it wins at every m measured, tools/time_rows.py)
-  const int rows = m * k;
-  const size_t gath_stride = mia::align_up(L.send_bytes * world, 256);
-  int32_t* done = (int32_t*)(base + L.done);
-  // exchange route: the redo counters live in the trailer of the last piece and travel with its all-gather
-  int32_t* ctr = exch ? (int32_t*)(base + L.bufs + L.chunk_bytes * (n_chunks - 1) + (size_t)rows * L.nc * sizeof(float))
-                      : counters;
-  tl_hk.err_out = ctr + 3;
-  mia::Tile2Loc tl_loc;
-  if (tl_fused) {
-    rc = mia::make_scan_params(&tl_loc.scan, grid_xyz, P, n_coord, coord_group, gc_c, n_r, gc_eps, base + L.loc, MIA_TAPER_GC, true);
-    if (rc != MIA_OK) return rc;
-    tl_loc.scan.start = tl_counts;
-    tl_loc.stats = ctr;
-    tl_loc.longest_bound = pm_tl;
-    tl_loc.periodic = period ? 1 : 0;
-  }
-  (void)hipGetLastError();
-  if (exch || peer) {
-    rc = comm_events(comm);
-    if (rc != MIA_OK) return rc;
-  }
-  uint32_t seq = *seq_io;
-  if (peer && do1) {      // "my buffer of this slot may be overwritten": told to every peer before anything else of the step
-    rc = peer_begin(comm, peer_slot, ps, &seq);
-    if (rc != MIA_OK) return rc;
-    *seq_io = seq;
-  }
+  p.carried = st.stage == 2 && a.phase == 0 && !p.exch && !p.peer && p.n_chunks == 1 && !p.eig_only && (flags & kStepPrepDone) &&
+              (!a.time_start_event == !a.time_stop_event);
+  return MIA_OK;
+}
 
-  bool segmented = false, tl_block = false;
-  if (phase == 0) {
-    // counters[0..3] = {longest list, truncated lists, declined points, error bits} of this rank; [4..7] = max over ranks.
-    // They, the trailer copy and the segment slots are cleared by the first index kernel when it runs
-    // (every fill launch of its own costs ~5-8 us of the ~100 us this phase takes)
-    const bool zero_in_kernel = P > 0 && b1 > b0 && !tl_reuse;
-    const size_t done_ints = (size_t)n_chunks * 64 * mia::kSlotStride;
-    if (do1) {
-    if (!zero_in_kernel) {
-      MIA_HIP_TRY(hipMemsetAsync(counters, 0, 8 * sizeof(int32_t), ps));
-      if (exch) {
-        MIA_HIP_TRY(hipMemsetAsync(ctr, 0, 4 * sizeof(int32_t), ps));
-        MIA_HIP_TRY(hipMemsetAsync(done, 0, done_ints * sizeof(int32_t), ps));
-      }
-    }
-    if (b1 > b0 && tl_reuse) {
-      if (!tl_rbf) {
-        rc = mia::split_pack_launch(Yb, d, k, P, base + L.hrec, ps);
-        if (rc != MIA_OK) return rc;
-      }
-    } else if (b1 > b0 && tl_route) {
-      const mia::ZeroJob zj{{counters, exch ? ctr : nullptr, exch ? done : nullptr},
-                            {8, exch ? 4 : 0, exch ? (int64_t)done_ints : 0}};
-      // bucket index: one kernel over the cell grid this workspace already holds (validated per observation); the first step on a
-      // workspace, or one sent back by error bit 8, runs the bounding-box kernel first
-      // (the split records ride in the bucket kernel -- small, and no LDS of its own -- rather than in the tile-list kernel, whose
-      //  occupancy the packing's 10 KB of LDS per workgroup would cap)
-      const mia::SplitPackJob sj{Yb, d, (unsigned char*)(base + L.hrec), k};
-      if (tl_bucket)
-        rc = mia::index_bucket_build_impl(obs_xyz, P, n_coord, coord_group, gc_c, n_r, base + L.loc, L.loc_bytes, ps,
-                                          zero_in_kernel ? &zj : nullptr,
-                                          !(step_flags & MIA_STEP_WS_CLEAN) || (step_flags & MIA_STEP_FRESH_BOX) || cnt_must_clear,
-                                          tl_rbf ? nullptr : &sj,
-                                          tl_counts, period);
-      else {
-        const bool arrays_clean = count_arrays_clean_for_scan(ws);      // (a scan-based build counts in array 0)
-        rc = mia::index_build_impl(obs_xyz, P, n_coord, coord_group, gc_c, n_r, base + L.loc, L.loc_bytes, ps, nullptr,
-                                   zero_in_kernel ? &zj : nullptr, (step_flags & MIA_STEP_WS_CLEAN) != 0 && arrays_clean, false,
-                                   period);
-      }
-      if (rc != MIA_OK) return rc;
-      if (!tl_fused) {
-        rc = mia::tile_lists_launch(grid_xyz, b0, b1 - b0, P, n_coord, coord_group, gc_c, n_r, gc_eps, MIA_TAPER_GC, L.ut,
-                                    base + L.tl, ctr, base + L.loc, ps, (tl_bucket || tl_rbf) ? nullptr : &sj, tl_bucket, tl_counts,
-                                    period);
-        if (rc != MIA_OK) return rc;
-      }
-    } else if (b1 > b0) {
-      // the record packing rides inside the first index kernel too (independent work, no launch of its own)
-      const mia::PackJob job{Yb, d, rec, k, (k + 1 + 3) / 4 * 4};
-      const mia::ZeroJob zj{{counters, exch ? ctr : nullptr, exch ? done : nullptr},
-                            {8, exch ? 4 : 0, exch ? (int64_t)done_ints : 0}};
-      rc = mia::localize_impl(grid_xyz, b0, b1, obs_xyz, P, n_coord, coord_group, gc_c, n_r, gc_eps, L.cap,
-                              cnt, idx, w, ctr, base + L.loc, L.loc_bytes, ps, P > 0 ? &job : nullptr, true,
-                              zero_in_kernel ? &zj : nullptr, MIA_TAPER_GC,
-                              (step_flags & MIA_STEP_WS_CLEAN) != 0 && count_arrays_clean_for_scan(ws), !lazy, period);
-      if (rc != MIA_OK) return rc;
-    }
-    if (ps != s) {   // the analysis stream starts once the preparation stream has produced records and lists
-      rc = prep_event(pe_io);
-      if (rc != MIA_OK) return rc;
-      MIA_HIP_TRY(hipEventRecord(*pe_io, ps));
-    }
-    if (exch) MIA_HIP_TRY(hipEventRecord(comm->ev[kMaxChunks], ps));
-    }   // do1
-    if (!do2) return MIA_OK;
-    if (ps != s && !(step_flags & kStepPrepDone)) MIA_HIP_TRY(hipStreamWaitEvent(s, *pe_io, 0));
-    // the side stream starts once the lists exist (and the slots it polls have been cleared)
-    if (exch) MIA_HIP_TRY(hipStreamWaitEvent(cs, comm->ev[kMaxChunks], 0));
-    if (t_start && !carried) MIA_HIP_TRY(hipEventRecord(t_start, s));   // (after the wait for the lists: kernel time only)
-    // tile route with several pieces: ONE launch over the block, every tile writes into its piece's buffer; the pieces are
-    // exchanged once it has finished (the kernel is a fraction of one piece's all-gather: nothing to overlap inside it)
-    if (tl_route && n_chunks > 1 && b1 > b0) {
-      rc = tl_rbf ? mia::lketkf_tile_launch(X, G, m, k, b0, b1 - b0, Yb, d, P, base + L.tl, L.ut, inf_factor, gamma,
-                                            (float*)(base + L.bufs), L.nc, 0, flags, ctr + 2, mia::option(MIA_OPT_CHEB_DMAX), tl_th, tl_tc, s,
-                                            (int)L.nc, (int64_t)(L.chunk_bytes / sizeof(float)), (tl_bucket && !tl_reuse) ? &tl_hk : nullptr)
-                  : mia::tile2_analysis_launch(X, G, m, k, b0, b1 - b0, base + L.hrec, P, base + L.tl, L.ut, inf_factor,
-                                      (float*)(base + L.bufs), L.nc, 0, flags, ctr + 2, mia::option(MIA_OPT_CHEB_DMAX), tl_th, tl_tc, s,
-                                      (int)L.nc, (int64_t)(L.chunk_bytes / sizeof(float)), (tl_bucket && !tl_reuse) ? &tl_hk : nullptr,
-                                      tl_fused ? &tl_loc : nullptr);
-      if (rc != MIA_OK) return rc;
-      tl_block = true;
-    }
-    // one launch over the whole block whose segments are exchanged as they complete (no kernel boundary, no
-    // event between the pieces: a 1e5-point block in 4 launches costs 292 us instead of 245 us on MI355X)
-    if (!tl_block && exch && n_chunks > 1 && !eig_only && b1 > b0 && signal_mode) {
-      rc = mia::cheb_analysis_launch(X, G, m, k, b0, b1 - b0, rec, cnt, idx, w, L.cap, p_max_assumed < L.cap ? p_max_assumed : L.cap,
-                                     inf_factor, gamma > 0.0f ? 1 : 0, gamma, (float*)(base + L.bufs), L.nc, 0, flags,
-                                     ctr + 2, nullptr, nullptr, s, (int)L.nc, (int64_t)(L.chunk_bytes / sizeof(float)), done);
-      if (rc == MIA_OK) segmented = true;
-      else if (rc != MIA_ERR_UNSUPPORTED) return rc;
+// The step's decision about its workspace (lists reused? which count array? localised in the kernel?): taken once per step, where its
+// preparation is enqueued (`take`), read by the analysis stage from the step's state and by a redo call from what the table still
+// knows; then the parts of the plan that follow from it.
+static int step_decide(const mia_step_args_t& a, bool take, StepState* st, StepPlan* plan) {
+  StepPlan& p = *plan;
+  StepDecision& D = st->dec;
+  if (take) {
+    D.reuse = geom_reuse_decision(a.ws, p.stamp, p.tl_route && (p.flags & MIA_STEP_REUSE_LISTS) != 0, true);
+    count_array_decision(a.ws, true, p.tl_bucket && !D.reuse, p.want_fused && !D.reuse, &D.cnt_use, &D.fused, &D.must_clear);
+    D.set = true;
+  } else if (!D.set) {      // (a redo of declined points, phase 1: a call of its own -- what the table still knows)
+    D.reuse = geom_reuse_decision(a.ws, p.stamp, false, false);
+    count_array_decision(a.ws, false, false, false, &D.cnt_use, &D.fused, &D.must_clear);
+  }
+  p.tl_reuse = D.reuse; p.tl_fused = D.fused; p.cnt_must_clear = D.must_clear;
+  // (the analysis launch puts the OTHER per-cell count array and the build's error word back to zero, see Tile2Params / GeomEntry)
+  p.tl_hk = mia::Tile2Housekeeping{nullptr, nullptr, nullptr, nullptr};
+  p.tl_counts = nullptr;
+  p.hk = nullptr;
+  if (p.tl_bucket && !p.tl_reuse) {
+    const mia::IndexLayout IL = mia::index_layout(p.base + p.L.loc, a.P, a.n_coord);
+    p.tl_counts = D.cnt_use ? IL.start : IL.cursor;
+    p.tl_hk = mia::Tile2Housekeeping{D.cnt_use ? IL.cursor : IL.start, &IL.hdr->ncell, &IL.hdr->err, nullptr};
+    p.hk = &p.tl_hk;
+  }
+  p.tl_hk.err_out = p.ctr + 3;
+  p.loc = nullptr;
+  if (p.tl_fused) {
+    const int rc = mia::make_scan_params(&p.tl_loc.scan, a.grid_xyz, a.P, a.n_coord, a.coord_group, a.gc_c, a.n_r, a.gc_eps, p.base + p.L.loc,
+                                         MIA_TAPER_GC, true);
+    if (rc != MIA_OK) return rc;
+    p.tl_loc.scan.start = p.tl_counts;
+    p.tl_loc.stats = p.ctr;
+    p.tl_loc.longest_bound = p.pm_tl;
+    p.tl_loc.periodic = p.period ? 1 : 0;
+    p.loc = &p.tl_loc;
+  }
+  // counters[0..3] = {longest list, truncated lists, declined points, error bits} of this rank; [4..7] = max over ranks.
+  // They, the trailer copy and the segment slots are cleared by the first index kernel when it runs
+  // (every fill launch of its own costs ~5-8 us of the ~100 us this phase takes)
+  p.zero_in_kernel = a.P > 0 && p.b1 > p.b0 && !p.tl_reuse;
+  return MIA_OK;
+}
+
+// prepare (phase 0, stage 1): clears, then records / index / lists on the preparation stream, then the events that order the
+// analysis and the exchange stream behind it
+static int step_prepare(const mia_step_args_t& a, const StepPlan& p, StepState* st) {
+  const StepLayout& L = p.L;
+  char* base = p.base;
+  const hipStream_t ps = p.ps;
+  const int flags = p.flags;
+  const bool have_block = p.b1 > p.b0;
+  int rc = MIA_OK;
+  if (!p.zero_in_kernel) {
+    MIA_HIP_TRY(hipMemsetAsync(a.counters, 0, 8 * sizeof(int32_t), ps));
+    if (p.exch) {
+      MIA_HIP_TRY(hipMemsetAsync(p.ctr, 0, 4 * sizeof(int32_t), ps));
+      MIA_HIP_TRY(hipMemsetAsync(p.done, 0, p.done_ints * sizeof(int32_t), ps));
     }
   }
-  if (!do2) return MIA_OK;
-
-  for (int c = 0; c < n_chunks; ++c) {
-    const int64_t c0 = b0 + c * L.nc < b1 ? b0 + c * L.nc : b1;
-    const int64_t c1 = c0 + L.nc < b1 ? c0 + L.nc : b1;
-    float* dst = exch ? (float*)(base + L.bufs + L.chunk_bytes * c) : Xa;
-    const int64_t ldo = exch ? L.nc : (no_gather ? b1 - b0 : G);
-    const int64_t o0 = exch ? 0 : (no_gather ? c0 - b0 : c0);
-    if (c1 > c0 && !segmented && !tl_block) {
-      const int32_t* ccnt = cnt + (c0 - b0);
-      const int32_t* cidx = idx + (size_t)(c0 - b0) * L.cap;
-      const double* cw = w + (size_t)(c0 - b0) * L.cap;
-      int32_t* cfl = flags + (c0 - b0);
-      if (phase == 1 && tl_route) {
-        // declined points of the tile route: float32 records and per-point lists are built now (the step's index is still in
-        // its workspace, unsorted: the flagged points' lists are put into sorted-index order as on the lazy route)
-        if (c == 0) {
-          rc = mia_letkf_pack_obs_f32(Yb, d, k, P, rec, stream);
-          if (rc != MIA_OK) return rc;
-          if (tl_bucket) {      // (the buckets are no scan-based index: build one, unsorted like the lazy route's)
-            (void)count_arrays_clean_for_scan(ws);      // (cleared whole below; the scan counts in array 0)
-            rc = mia::index_build_impl(obs_xyz, P, n_coord, coord_group, gc_c, n_r, base + L.loc, L.loc_bytes, (hipStream_t)stream,
-                                       nullptr, nullptr, false, false, period);
-            if (rc != MIA_OK) return rc;
-          }
-        }
-        rc = mia::localize_lists_impl(grid_xyz, c0, c1, P, n_coord, coord_group, gc_c, n_r, gc_eps, L.cap, const_cast<int32_t*>(ccnt),
-                                      const_cast<int32_t*>(cidx), const_cast<double*>(cw), (int32_t*)(base + L.scratch),
-                                      base + L.loc, (hipStream_t)stream, nullptr, MIA_TAPER_GC, period);
-        if (rc != MIA_OK) return rc;
-        rc = mia::sort_flagged_lists(cfl, ccnt, const_cast<int32_t*>(cidx), const_cast<double*>(cw), c1 - c0, (int)L.cap,
-                                     base + L.loc, P, n_coord, (hipStream_t)stream);
-        if (rc != MIA_OK) return rc;
-        rc = mia_letkf_analysis_retry_f32(X, G, m, k, c0, c1, rec, P, ccnt, cidx, cw, L.cap, p_max_assumed, inf_factor,
-                                          gamma, dst, ldo, o0, cfl, stream);
-        if (rc != MIA_OK) return rc;
-      } else if (phase == 1) {
-        if (lazy) {      // (the lists of the declined points into sorted-index order, see above)
-          rc = mia::sort_flagged_lists(cfl, ccnt, const_cast<int32_t*>(cidx), const_cast<double*>(cw), c1 - c0, (int)L.cap,
-                                       base + L.loc, P, n_coord, (hipStream_t)stream);
-          if (rc != MIA_OK) return rc;
-        }
-        rc = mia_letkf_analysis_retry_f32(X, G, m, k, c0, c1, rec, P, ccnt, cidx, cw, L.cap, p_max_assumed, inf_factor,
-                                          gamma, dst, ldo, o0, cfl, stream);
-        if (rc != MIA_OK) return rc;
-      } else {
-        rc = MIA_ERR_UNSUPPORTED;
-        if (!eig_only) {
-          // a step in flight whose analysis is one plain launch: the launch carries its completion event itself
-          hipEvent_t kstop = nullptr;
-          if (carried) {          // (a timed step: the dispatch's own start / stop times, no marker packets either)
-            kstop = t_stop;
-            if (!kstop) {
-              rc = prep_event(&kstop);
-              if (rc != MIA_OK) return rc;
-            }
-            mia::launch_stop_event() = kstop;
-            mia::launch_start_event() = t_start;
-          }
-          const unsigned long long tiles_before = mia::tile_launch_count();
-          if (tl_route && tl_rbf)
-            rc = mia::lketkf_tile_launch(X, G, m, k, c0, c1 - c0, Yb, d, P, base + L.tl, L.ut, inf_factor, gamma, dst, ldo, o0,
-                                         cfl, ctr + 2, mia::option(MIA_OPT_CHEB_DMAX), tl_th, tl_tc, (hipStream_t)stream, 0, 0,
-                                         (tl_bucket && !tl_reuse) ? &tl_hk : nullptr);
-          else if (tl_route)
-            rc = mia::tile2_analysis_launch(X, G, m, k, c0, c1 - c0, base + L.hrec, P, base + L.tl, L.ut, inf_factor, dst, ldo, o0,
-                                            cfl, ctr + 2, mia::option(MIA_OPT_CHEB_DMAX), tl_th, tl_tc, (hipStream_t)stream, 0, 0,
-                                            (tl_bucket && !tl_reuse) ? &tl_hk : nullptr, tl_fused ? &tl_loc : nullptr);
-          else
-            rc = mia_letkf_analysis_matfun_f32(X, G, m, k, c0, c1, rec, P, ccnt, cidx, cw, L.cap, p_max_assumed,
-                                               inf_factor, gamma, dst, ldo, o0, cfl, ctr + 2, stream);
-          // (an unsorted index is only right for the kernel the rule above predicted; the tile route has no other kernel)
-          if ((lazy || tl_route) && (rc != MIA_OK || mia::tile_launch_count() == tiles_before)) {
-            mia::launch_stop_event() = nullptr;
-            mia::launch_start_event() = nullptr;
-            return rc != MIA_OK ? rc : MIA_ERR_UNSUPPORTED;
-          }
-          if (kstop) {
-            if (mia::launch_stop_event() == nullptr) {
-              *kdone_out = kstop;      // (taken by the tile kernel's launch)
-            } else if (t_start) {      // another kernel served the shape: ordinary markers around it (late start: after the fact)
-              MIA_HIP_TRY(hipEventRecord(t_start, s));
-              MIA_HIP_TRY(hipEventRecord(t_stop, s));
-            }
-            mia::launch_stop_event() = nullptr;
-            mia::launch_start_event() = nullptr;
-          }
-        }
-        if (rc == MIA_ERR_UNSUPPORTED)
-          rc = mia_letkf_analysis_packed_f32(X, G, m, k, c0, c1, rec, P, ccnt, cidx, cw, L.cap, p_max_assumed,
-                                             inf_factor, gamma, dst, ldo, o0, nullptr, cfl, stream);
-        if (rc != MIA_OK) return rc;
-      }
-    }
-    if (exch) {
-      float* gath = (float*)(base + L.gath + gath_stride * c);
-      if (segmented) {
-        if (c1 > c0) {
-          rc = mia::segment_wait_launch(done + (size_t)c * 64 * mia::kSlotStride, (int)(c1 - c0), ctr + 3, cs);
-          if (rc != MIA_OK) return rc;
-        }
-      } else if (!tl_block || c == 0) {      // (the tile route's one launch: the first piece's wait covers all of them)
-        MIA_HIP_TRY(hipEventRecord(comm->ev[c], s));
-        MIA_HIP_TRY(hipStreamWaitEvent(cs, comm->ev[c], 0));
-      }
-      rc = comm_allgather(comm, dst, gath, L.send_bytes, cs);
+  const mia::ZeroJob zj{{a.counters, p.exch ? p.ctr : nullptr, p.exch ? p.done : nullptr}, {8, p.exch ? 4 : 0, p.exch ? (int64_t)p.done_ints : 0}};
+  const mia::ZeroJob* zero = p.zero_in_kernel ? &zj : nullptr;
+  if (have_block && p.tl_reuse) {
+    if (!p.tl_rbf) {
+      rc = mia::split_pack_launch(a.Yb, a.d, a.k, a.P, base + L.hrec, ps);
       if (rc != MIA_OK) return rc;
-      // With steps in flight (MIA_STEP_NO_JOIN) and a placement stream, the copy of the gathered piece into the result
-      // leaves the exchange stream: the next step's all-gather need not wait for 2 x world x piece bytes of HBM traffic
-      hipStream_t xs = cs;
-      if (comm->place_stream && (step_flags & MIA_STEP_NO_JOIN)) {
-        xs = comm->place_stream;
-        MIA_HIP_TRY(hipEventRecord(comm->evp[c], cs));
-        MIA_HIP_TRY(hipStreamWaitEvent(xs, comm->evp[c], 0));
-      }
-      const int64_t off = (int64_t)c * L.nc;
-      int32_t* ctr_out = (phase == 0 && c == n_chunks - 1) ? counters : nullptr;
-      const bool vec = (L.nc % 4 == 0) && (G % 4 == 0) && (L.n % 4 == 0) && ((uintptr_t)Xa % 16 == 0);
-      if (vec) {
-        const int per = kPlaceThreads * kPlaceUnroll;
-        dim3 grid((unsigned)((L.nc / 4 + per - 1) / per), (unsigned)rows, (unsigned)world);
-        place_chunk_kernel<4><<<grid, kPlaceThreads, 0, xs>>>(gath, Xa, G, L.n, off, (int)L.nc, rows, L.send_bytes / sizeof(float),
-                                                    ctr_out, rank);
-      } else {
-        const int per = kPlaceThreads * kPlaceUnroll;
-        dim3 grid((unsigned)((L.nc + per - 1) / per), (unsigned)rows, (unsigned)world);
-        place_chunk_kernel<1><<<grid, kPlaceThreads, 0, xs>>>(gath, Xa, G, L.n, off, (int)L.nc, rows, L.send_bytes / sizeof(float),
-                                                    ctr_out, rank);
-      }
-      MIA_LAUNCH_CHECK();
     }
-  }
-
-  if (peer) {      // block analysed (stream s) -> exchange stream: wait, push, signal, wait (see "Direct exchange")
-    MIA_HIP_TRY(hipEventRecord(comm->ev[0], s));
-    MIA_HIP_TRY(hipStreamWaitEvent(cs, comm->ev[0], 0));
-    rc = peer_finish(comm, peer_slot, seq, G, b0, b1, rows, counters, cs);
+  } else if (have_block && p.tl_route) {
+    // bucket index: one kernel over the cell grid this workspace already holds (validated per observation); the first step on a
+    // workspace, or one sent back by error bit 8, runs the bounding-box kernel first
+    // (the split records ride in the bucket kernel -- small, and no LDS of its own -- rather than in the tile-list kernel, whose
+    //  occupancy the packing's 10 KB of LDS per workgroup would cap)
+    const mia::SplitPackJob sj{a.Yb, a.d, (unsigned char*)(base + L.hrec), a.k};
+    if (p.tl_bucket)
+      rc = mia::index_bucket_build_impl(a.obs_xyz, a.P, a.n_coord, a.coord_group, a.gc_c, a.n_r, base + L.loc, L.loc_bytes, ps, zero,
+                                        !(flags & MIA_STEP_WS_CLEAN) || (flags & MIA_STEP_FRESH_BOX) || p.cnt_must_clear,
+                                        p.tl_rbf ? nullptr : &sj, p.tl_counts, p.period);
+    else {
+      const bool arrays_clean = count_arrays_clean_for_scan(a.ws);      // (a scan-based build counts in array 0)
+      rc = mia::index_build_impl(a.obs_xyz, a.P, a.n_coord, a.coord_group, a.gc_c, a.n_r, base + L.loc, L.loc_bytes, ps, nullptr, zero,
+                                 (flags & MIA_STEP_WS_CLEAN) != 0 && arrays_clean, false, p.period);
+    }
+    if (rc != MIA_OK) return rc;
+    if (!p.tl_fused) {
+      rc = mia::tile_lists_launch(a.grid_xyz, p.b0, p.b1 - p.b0, a.P, a.n_coord, a.coord_group, a.gc_c, a.n_r, a.gc_eps, MIA_TAPER_GC, L.ut,
+                                  base + L.tl, p.ctr, base + L.loc, ps, (p.tl_bucket || p.tl_rbf) ? nullptr : &sj, p.tl_bucket, p.tl_counts,
+                                  p.period);
+      if (rc != MIA_OK) return rc;
+    }
+  } else if (have_block) {
+    // the record packing rides inside the first index kernel too (independent work, no launch of its own)
+    const mia::PackJob job{a.Yb, a.d, p.rec, a.k, (a.k + 1 + 3) / 4 * 4};
+    rc = mia::localize_impl(a.grid_xyz, p.b0, p.b1, a.obs_xyz, a.P, a.n_coord, a.coord_group, a.gc_c, a.n_r, a.gc_eps, L.cap, p.cnt, p.idx, p.w,
+                            p.ctr, base + L.loc, L.loc_bytes, ps, a.P > 0 ? &job : nullptr, true, zero, MIA_TAPER_GC,
+                            (flags & MIA_STEP_WS_CLEAN) != 0 && count_arrays_clean_for_scan(a.ws), !p.lazy, p.period);
     if (rc != MIA_OK) return rc;
   }
-  if (phase == 0 && t_stop && !carried) MIA_HIP_TRY(hipEventRecord(t_stop, s));
-  // (without the exchange route counters[4..7] stay zero: the rank's own [0..3] are the whole story)
-  if ((exch || peer) && !(step_flags & MIA_STEP_NO_JOIN)) {   // the caller's stream continues after the exchange
-    MIA_HIP_TRY(hipEventRecord(comm->ev[kMaxChunks + 1], cs));
-    MIA_HIP_TRY(hipStreamWaitEvent(s, comm->ev[kMaxChunks + 1], 0));
+  if (ps != p.s) {   // the analysis stream starts once the preparation stream has produced records and lists
+    rc = prep_event(&st->pe);
+    if (rc != MIA_OK) return rc;
+    MIA_HIP_TRY(hipEventRecord(st->pe, ps));
+  }
+  if (p.exch) MIA_HIP_TRY(hipEventRecord(a.comm->ev[mia::kMaxChunks], ps));
+  return MIA_OK;
+}
+
+// piece c of the block: grid points [c0, c1), written to dst (its send buffer on the exchange route, else the result) with leading
+// dimension ldo from column o0; the piece's slices of the per-point lists and flags
+struct StepPiece {
+  int c;
+  int64_t c0, c1, ldo, o0;
+  float* dst;
+  int32_t *cnt, *idx, *flags;
+  double* w;
+};
+static StepPiece step_piece(const mia_step_args_t& a, const StepPlan& p, int c) {
+  const StepLayout& L = p.L;
+  StepPiece q;
+  q.c = c;
+  q.c0 = p.b0 + c * L.nc < p.b1 ? p.b0 + c * L.nc : p.b1;
+  q.c1 = q.c0 + L.nc < p.b1 ? q.c0 + L.nc : p.b1;
+  q.dst = p.exch ? (float*)(p.base + L.bufs + L.chunk_bytes * c) : a.Xa;
+  q.ldo = p.exch ? L.nc : (p.no_gather ? p.b1 - p.b0 : a.G);
+  q.o0 = p.exch ? 0 : (p.no_gather ? q.c0 - p.b0 : q.c0);
+  q.cnt = p.cnt + (q.c0 - p.b0);
+  q.idx = p.idx + (size_t)(q.c0 - p.b0) * L.cap;
+  q.w = p.w + (size_t)(q.c0 - p.b0) * L.cap;
+  q.flags = a.flags + (q.c0 - p.b0);
+  return q;
+}
+
+// exchange of a piece: the exchange stream waits for the piece (its segment of a segmented launch, else an event on the analysis
+// stream -- ordered: false where an earlier piece's wait already covers this one), all-gather, placement into the result
+static int exchange_piece(const mia_step_args_t& a, const StepPlan& p, const StepPiece& q, bool segmented, bool ordered) {
+  const StepLayout& L = p.L;
+  mia_comm* comm = a.comm;
+  const hipStream_t cs = p.cs;
+  float* gath = (float*)(p.base + L.gath + p.gath_stride * q.c);
+  int rc = MIA_OK;
+  if (segmented) {
+    if (q.c1 > q.c0) {
+      rc = mia::segment_wait_launch(p.done + (size_t)q.c * 64 * mia::kSlotStride, (int)(q.c1 - q.c0), p.ctr + 3, cs);
+      if (rc != MIA_OK) return rc;
+    }
+  } else if (ordered) {
+    MIA_HIP_TRY(hipEventRecord(comm->ev[q.c], p.s));
+    MIA_HIP_TRY(hipStreamWaitEvent(cs, comm->ev[q.c], 0));
+  }
+  rc = mia::comm_allgather(comm, q.dst, gath, L.send_bytes, cs);
+  if (rc != MIA_OK) return rc;
+  // With steps in flight (MIA_STEP_NO_JOIN) and a placement stream, the copy of the gathered piece into the result
+  // leaves the exchange stream: the next step's all-gather need not wait for 2 x world x piece bytes of HBM traffic
+  hipStream_t xs = cs;
+  if (comm->place_stream && (p.flags & MIA_STEP_NO_JOIN)) {
+    xs = comm->place_stream;
+    MIA_HIP_TRY(hipEventRecord(comm->evp[q.c], cs));
+    MIA_HIP_TRY(hipStreamWaitEvent(xs, comm->evp[q.c], 0));
+  }
+  int32_t* ctr_out = (a.phase == 0 && q.c == p.n_chunks - 1) ? a.counters : nullptr;
+  return mia::place_chunk_launch(gath, a.Xa, a.G, L.n, (int64_t)q.c * L.nc, L.nc, p.rows, p.world, L.send_bytes / sizeof(float), ctr_out, p.rank, xs);
+}
+
+// the analysis of one piece as a launch of its own: tile kernels, matfun kernel, else the eigensolver entry
+static int analyse_piece(const mia_step_args_t& a, const StepPlan& p, StepState* st, const StepPiece& q) {
+  const StepLayout& L = p.L;
+  const hipEvent_t t_start = (hipEvent_t)a.time_start_event, t_stop = (hipEvent_t)a.time_stop_event;
+  int rc = MIA_ERR_UNSUPPORTED;
+  if (!p.eig_only) {
+    // a step in flight whose analysis is one plain launch: the launch carries its completion event itself
+    hipEvent_t kstop = nullptr;
+    if (p.carried) {          // (a timed step: the dispatch's own start / stop times, no marker packets either)
+      kstop = t_stop;
+      if (!kstop) {
+        rc = prep_event(&kstop);
+        if (rc != MIA_OK) return rc;
+      }
+      mia::launch_stop_event() = kstop;
+      mia::launch_start_event() = t_start;
+    }
+    const unsigned long long tiles_before = mia::tile_launch_count();
+    if (p.tl_route && p.tl_rbf)
+      rc = mia::lketkf_tile_launch(a.X, a.G, a.m, a.k, q.c0, q.c1 - q.c0, a.Yb, a.d, a.P, p.base + L.tl, L.ut, a.inf_factor, a.gamma, q.dst, q.ldo,
+                                   q.o0, q.flags, p.ctr + 2, mia::option(MIA_OPT_CHEB_DMAX), p.tl_th, p.tl_tc, p.s, 0, 0, p.hk);
+    else if (p.tl_route)
+      rc = mia::tile2_analysis_launch(a.X, a.G, a.m, a.k, q.c0, q.c1 - q.c0, p.base + L.hrec, a.P, p.base + L.tl, L.ut, a.inf_factor, q.dst, q.ldo,
+                                      q.o0, q.flags, p.ctr + 2, mia::option(MIA_OPT_CHEB_DMAX), p.tl_th, p.tl_tc, p.s, 0, 0, p.hk, p.loc);
+    else
+      rc = mia_letkf_analysis_matfun_f32(a.X, a.G, a.m, a.k, q.c0, q.c1, p.rec, a.P, q.cnt, q.idx, q.w, L.cap, a.p_max_assumed, a.inf_factor,
+                                         a.gamma, q.dst, q.ldo, q.o0, q.flags, p.ctr + 2, a.stream);
+    // (an unsorted index is only right for the kernel the rule of the plan predicted; the tile route has no other kernel)
+    if ((p.lazy || p.tl_route) && (rc != MIA_OK || mia::tile_launch_count() == tiles_before)) {
+      mia::launch_stop_event() = nullptr;
+      mia::launch_start_event() = nullptr;
+      return rc != MIA_OK ? rc : MIA_ERR_UNSUPPORTED;
+    }
+    if (kstop) {
+      if (mia::launch_stop_event() == nullptr) {
+        st->kdone = kstop;      // (taken by the tile kernel's launch)
+      } else if (t_start) {      // another kernel served the shape: ordinary markers around it (late start: after the fact)
+        MIA_HIP_TRY(hipEventRecord(t_start, p.s));
+        MIA_HIP_TRY(hipEventRecord(t_stop, p.s));
+      }
+      mia::launch_stop_event() = nullptr;
+      mia::launch_start_event() = nullptr;
+    }
+  }
+  if (rc == MIA_ERR_UNSUPPORTED)
+    rc = mia_letkf_analysis_packed_f32(a.X, a.G, a.m, a.k, q.c0, q.c1, p.rec, a.P, q.cnt, q.idx, q.w, L.cap, a.p_max_assumed, a.inf_factor,
+                                       a.gamma, q.dst, q.ldo, q.o0, nullptr, q.flags, a.stream);
+  return rc;
+}
+
+// analyse (phase 0, stage 2): the waits for the preparation, then the block in one launch over its pieces where a kernel can, else
+// piece by piece, each piece exchanged as it completes
+static int step_analyse(const mia_step_args_t& a, const StepPlan& p, StepState* st) {
+  const StepLayout& L = p.L;
+  const hipStream_t s = p.s;
+  const bool have_block = p.b1 > p.b0;
+  int rc = MIA_OK;
+  if (p.ps != s && !(p.flags & kStepPrepDone)) MIA_HIP_TRY(hipStreamWaitEvent(s, st->pe, 0));
+  // the side stream starts once the lists exist (and the slots it polls have been cleared)
+  if (p.exch) MIA_HIP_TRY(hipStreamWaitEvent(p.cs, a.comm->ev[mia::kMaxChunks], 0));
+  if (a.time_start_event && !p.carried) MIA_HIP_TRY(hipEventRecord((hipEvent_t)a.time_start_event, s));   // (after the wait for the lists: kernel time only)
+  float* bufs = (float*)(p.base + L.bufs);
+  const int64_t seg_stride = (int64_t)(L.chunk_bytes / sizeof(float));
+  // tile route with several pieces: ONE launch over the block, every tile writes into its piece's buffer; the pieces are
+  // exchanged once it has finished (the kernel is a fraction of one piece's all-gather: nothing to overlap inside it)
+  bool tl_block = false;
+  if (p.tl_route && p.n_chunks > 1 && have_block) {
+    rc = p.tl_rbf ? mia::lketkf_tile_launch(a.X, a.G, a.m, a.k, p.b0, p.b1 - p.b0, a.Yb, a.d, a.P, p.base + L.tl, L.ut, a.inf_factor, a.gamma, bufs,
+                                            L.nc, 0, a.flags, p.ctr + 2, mia::option(MIA_OPT_CHEB_DMAX), p.tl_th, p.tl_tc, s, (int)L.nc, seg_stride,
+                                            p.hk)
+                  : mia::tile2_analysis_launch(a.X, a.G, a.m, a.k, p.b0, p.b1 - p.b0, p.base + L.hrec, a.P, p.base + L.tl, L.ut, a.inf_factor, bufs,
+                                               L.nc, 0, a.flags, p.ctr + 2, mia::option(MIA_OPT_CHEB_DMAX), p.tl_th, p.tl_tc, s, (int)L.nc,
+                                               seg_stride, p.hk, p.loc);
+    if (rc != MIA_OK) return rc;
+    tl_block = true;
+  }
+  // one launch over the whole block whose segments are exchanged as they complete (no kernel boundary, no
+  // event between the pieces: a 1e5-point block in 4 launches costs 292 us instead of 245 us on MI355X)
+  bool segmented = false;
+  if (!tl_block && p.exch && p.n_chunks > 1 && !p.eig_only && have_block && p.signal_mode) {
+    rc = mia::cheb_analysis_launch(a.X, a.G, a.m, a.k, p.b0, p.b1 - p.b0, p.rec, p.cnt, p.idx, p.w, L.cap, p.pm_tl, a.inf_factor,
+                                   a.gamma > 0.0f ? 1 : 0, a.gamma, bufs, L.nc, 0, a.flags, p.ctr + 2, nullptr, nullptr, s, (int)L.nc, seg_stride,
+                                   p.done);
+    if (rc == MIA_OK) segmented = true;
+    else if (rc != MIA_ERR_UNSUPPORTED) return rc;
+  }
+  for (int c = 0; c < p.n_chunks; ++c) {
+    const StepPiece q = step_piece(a, p, c);
+    if (q.c1 > q.c0 && !segmented && !tl_block) {
+      rc = analyse_piece(a, p, st, q);
+      if (rc != MIA_OK) return rc;
+    }
+    if (p.exch) {      // (the tile route's one launch: the first piece's wait covers all of them)
+      rc = exchange_piece(a, p, q, segmented, !tl_block || c == 0);
+      if (rc != MIA_OK) return rc;
+    }
   }
   return MIA_OK;
 }
 
-// the body of the two step entries below (period: as the periodic entry takes it, nullptr = open)
-static int step_entry(const float* X, int64_t G, int m, int k, const float* Yb, const float* d, int64_t P, const double* grid_xyz,
-                      const double* obs_xyz, int n_coord, const int32_t* coord_group, const double* period, const double* gc_c, int n_r,
-                      double gc_eps, float inf_factor, float gamma, int method, int p_max_assumed, mia_comm_t* comm, int n_chunks,
-                      int phase, float* Xa, int32_t* flags, int32_t* counters, void* ws, size_t ws_bytes, void* stream,
-                      void* comm_stream, void* prep_stream, int step_flags) {
-  if (mia::check_period(period, period_coords(n_coord), &period) != MIA_OK) return MIA_ERR_ARG;
-  hipEvent_t pe = nullptr;
-  uint32_t seq = 0;
-  const hipEvent_t t0 = t_time_start, t1 = t_time_stop;
+// redo (phase 1): the points the step's kernel declined, piece by piece, with the eigensolver kernel over per-point lists
+static int step_redo(const mia_step_args_t& a, const StepPlan& p) {
+  const StepLayout& L = p.L;
+  const hipStream_t s = p.s;
+  int rc = MIA_OK;
+  for (int c = 0; c < p.n_chunks; ++c) {
+    const StepPiece q = step_piece(a, p, c);
+    if (q.c1 > q.c0) {
+      if (p.tl_route) {
+        // declined points of the tile route: float32 records and per-point lists are built now (the step's index is still in
+        // its workspace, unsorted: the flagged points' lists are put into sorted-index order as on the lazy route)
+        if (c == 0) {
+          rc = mia_letkf_pack_obs_f32(a.Yb, a.d, a.k, a.P, p.rec, a.stream);
+          if (rc != MIA_OK) return rc;
+          if (p.tl_bucket) {      // (the buckets are no scan-based index: build one, unsorted like the lazy route's)
+            (void)count_arrays_clean_for_scan(a.ws);      // (cleared whole below; the scan counts in array 0)
+            rc = mia::index_build_impl(a.obs_xyz, a.P, a.n_coord, a.coord_group, a.gc_c, a.n_r, p.base + L.loc, L.loc_bytes, s, nullptr, nullptr,
+                                       false, false, p.period);
+            if (rc != MIA_OK) return rc;
+          }
+        }
+        rc = mia::localize_lists_impl(a.grid_xyz, q.c0, q.c1, a.P, a.n_coord, a.coord_group, a.gc_c, a.n_r, a.gc_eps, L.cap, q.cnt, q.idx, q.w,
+                                      (int32_t*)(p.base + L.scratch), p.base + L.loc, s, nullptr, MIA_TAPER_GC, p.period);
+        if (rc != MIA_OK) return rc;
+      }
+      if (p.tl_route || p.lazy) {      // (the lists of the declined points into sorted-index order, see the plan)
+        rc = mia::sort_flagged_lists(q.flags, q.cnt, q.idx, q.w, q.c1 - q.c0, (int)L.cap, p.base + L.loc, a.P, a.n_coord, s);
+        if (rc != MIA_OK) return rc;
+      }
+      rc = mia_letkf_analysis_retry_f32(a.X, a.G, a.m, a.k, q.c0, q.c1, p.rec, a.P, q.cnt, q.idx, q.w, L.cap, a.p_max_assumed, a.inf_factor,
+                                        a.gamma, q.dst, q.ldo, q.o0, q.flags, a.stream);
+      if (rc != MIA_OK) return rc;
+    }
+    if (p.exch) {
+      rc = exchange_piece(a, p, q, false, true);
+      if (rc != MIA_OK) return rc;
+    }
+  }
+  return MIA_OK;
+}
+
+static int step_impl(const mia_step_args_t& a, StepState* st) {
+  const bool do1 = st->stage != 2, do2 = st->stage != 1;
+  if (st->stage == 2) st->kdone = nullptr;
+  StepPlan p;
+  int rc = step_plan(a, *st, &p);
+  if (rc != MIA_OK) return rc;
+  rc = step_decide(a, a.phase == 0 && do1, st, &p);
+  if (rc != MIA_OK) return rc;
+  (void)hipGetLastError();
+  if (p.exch || p.peer) {
+    rc = mia::comm_events(a.comm);
+    if (rc != MIA_OK) return rc;
+  }
+  if (p.peer && do1) {      // "my buffer of this slot may be overwritten": told to every peer before anything else of the step
+    rc = mia::peer_begin(a.comm, p.peer_slot, p.ps, &st->seq);
+    if (rc != MIA_OK) return rc;
+  }
+  if (a.phase == 0 && do1) {
+    rc = step_prepare(a, p, st);
+    if (rc != MIA_OK) return rc;
+  }
+  if (!do2) return MIA_OK;
+  rc = a.phase == 0 ? step_analyse(a, p, st) : step_redo(a, p);
+  if (rc != MIA_OK) return rc;
+  if (p.peer) {      // block analysed (stream s) -> exchange stream: wait, push, signal, wait (see "Direct exchange", step_comm.hip)
+    MIA_HIP_TRY(hipEventRecord(a.comm->ev[0], p.s));
+    MIA_HIP_TRY(hipStreamWaitEvent(p.cs, a.comm->ev[0], 0));
+    rc = mia::peer_finish(a.comm, p.peer_slot, st->seq, a.G, p.b0, p.b1, p.rows, a.counters, p.cs);
+    if (rc != MIA_OK) return rc;
+  }
+  if (a.phase == 0 && a.time_stop_event && !p.carried) MIA_HIP_TRY(hipEventRecord((hipEvent_t)a.time_stop_event, p.s));
+  // (without the exchange route counters[4..7] stay zero: the rank's own [0..3] are the whole story)
+  if ((p.exch || p.peer) && !(p.flags & MIA_STEP_NO_JOIN)) {   // the caller's stream continues after the exchange
+    MIA_HIP_TRY(hipEventRecord(a.comm->ev[mia::kMaxChunks + 1], p.cs));
+    MIA_HIP_TRY(hipStreamWaitEvent(p.s, a.comm->ev[mia::kMaxChunks + 1], 0));
+  }
+  return MIA_OK;
+}
+
+// The positional entries fill one block, once, here at the ABI boundary (the header gives their parameters the same names
+// everywhere, so the block is filled by NAME: no second positional list to transpose).  The coordinate-group and radius tables are
+// copied into the block: their sizes are checked first.  The macro RETURNS from the entry -- MIA_ERR_NULL for a NULL coord_group or
+// gc_c, MIA_ERR_SIZE for n_coord or n_r outside the block's tables -- before it declares the block.  Checking these sizes ahead of
+// the copies changes which code a call with TWO faults reports: a NULL X together with n_coord 0 was MIA_ERR_NULL (pointers were
+// looked at first) and is MIA_ERR_SIZE now; every single fault reports what it always did (tests/golden/step_call_trace.txt).
+#define MIA_STEP_BLOCK_FROM_PARAMETERS(a)                                                                                      \
+  if (!coord_group || !gc_c) return MIA_ERR_NULL;                                                                              \
+  if (!step_tables_fit(n_coord, n_r)) return MIA_ERR_SIZE;                                                                     \
+  mia_step_args_t a;                                                                                                           \
+  memset(&a, 0, sizeof a);                                                                                                     \
+  a.X = X; a.G = G; a.m = m; a.k = k; a.Yb = Yb; a.d = d; a.P = P; a.grid_xyz = grid_xyz; a.obs_xyz = obs_xyz;                 \
+  a.n_coord = n_coord; a.n_r = n_r; a.gc_eps = gc_eps; a.inf_factor = inf_factor; a.gamma = gamma; a.method = method;          \
+  for (int c_ = 0; c_ < n_coord; ++c_) a.coord_group[c_] = coord_group[c_];                                                    \
+  for (int r_ = 0; r_ < n_r; ++r_) a.gc_c[r_] = gc_c[r_];                                                                      \
+  a.p_max_assumed = p_max_assumed; a.comm = comm; a.n_chunks = n_chunks; a.phase = phase; a.Xa = Xa; a.flags = flags;          \
+  a.counters = counters; a.ws = ws; a.ws_bytes = ws_bytes; a.stream = stream; a.comm_stream = comm_stream;                     \
+  a.prep_stream = prep_stream; a.step_flags = step_flags
+
+// the whole step at once on the caller's thread, timed by the one-shot hook if one was set (mia_letkf_step_timing_events)
+static int step_now(mia_step_args_t* a) {
+  a->time_start_event = (void*)t_time_start;
+  a->time_stop_event = (void*)t_time_stop;
   t_time_start = t_time_stop = nullptr;
-  return step_impl(X, G, m, k, Yb, d, P, grid_xyz, obs_xyz, n_coord, coord_group, gc_c, n_r, gc_eps, inf_factor, gamma, method,
-                   p_max_assumed, comm, n_chunks, phase, Xa, flags, counters, ws, ws_bytes, stream, comm_stream, prep_stream,
-                   step_flags, 0, &pe, &seq, t0, t1, nullptr, nullptr, period);
+  StepState st;
+  st.flags = a->step_flags;
+  return step_impl(*a, &st);
 }
 
 extern "C" int mia_letkf_sharded_step_streams_f32(const float* X, int64_t G, int m, int k,
@@ -1194,9 +848,8 @@ extern "C" int mia_letkf_sharded_step_streams_f32(const float* X, int64_t G, int
                                                   float* Xa, int32_t* flags, int32_t* counters,
                                                   void* ws, size_t ws_bytes, void* stream, void* comm_stream,
                                                   void* prep_stream, int step_flags) {
-  return step_entry(X, G, m, k, Yb, d, P, grid_xyz, obs_xyz, n_coord, coord_group, nullptr, gc_c, n_r, gc_eps, inf_factor, gamma,
-                    method, p_max_assumed, comm, n_chunks, phase, Xa, flags, counters, ws, ws_bytes, stream, comm_stream, prep_stream,
-                    step_flags);
+  MIA_STEP_BLOCK_FROM_PARAMETERS(a);      // (may return MIA_ERR_NULL / MIA_ERR_SIZE)
+  return step_now(&a);
 }
 
 extern "C" int mia_letkf_sharded_step_periodic_f32(const float* X, int64_t G, int m, int k, const float* Yb, const float* d, int64_t P,
@@ -1206,9 +859,9 @@ extern "C" int mia_letkf_sharded_step_periodic_f32(const float* X, int64_t G, in
                                                    float* Xa, int32_t* flags, int32_t* counters, void* ws, size_t ws_bytes, void* stream,
                                                    void* comm_stream, void* prep_stream, int step_flags) {
   if (!period) return MIA_ERR_NULL;
-  return step_entry(X, G, m, k, Yb, d, P, grid_xyz, obs_xyz, n_coord, coord_group, period, gc_c, n_r, gc_eps, inf_factor, gamma,
-                    method, p_max_assumed, comm, n_chunks, phase, Xa, flags, counters, ws, ws_bytes, stream, comm_stream, prep_stream,
-                    step_flags);
+  MIA_STEP_BLOCK_FROM_PARAMETERS(a);      // (may return MIA_ERR_NULL / MIA_ERR_SIZE)
+  for (int c = 0; c < n_coord; ++c) a.period[c] = period[c];
+  return step_now(&a);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1223,14 +876,8 @@ extern "C" int mia_letkf_sharded_step_periodic_f32(const float* X, int64_t G, in
 // them: that is what the read-back event is for).
 namespace {
 struct StepJob {
-  const float* X; int64_t G; int m, k; const float* Yb; const float* d; int64_t P; const double* grid; const double* obs;
-  int n_coord; int32_t cg[MIA_MAX_COORD]; double rc_[MIA_MAX_RADII]; int n_r; double per[MIA_MAX_COORD] = {0.0, 0.0, 0.0}; bool cyclic = false; double eps; float inf, gamma; int method, hint;
-  mia_comm_t* comm; int n_chunks, phase; float* Xa; int32_t* flags; int32_t* counters; void* ws; size_t ws_bytes;
-  void *stream, *comm_stream, *prep_stream; int step_flags;
-  int32_t* host8; void *after, *on; void** done_event; void *t0, *t1;
-  hipEvent_t pe = nullptr; uint32_t seq = 0;
-  hipEvent_t kdone = nullptr;      // completion event carried by the analysis launch itself (stage 2), if any
-  StepDecision dec;                // what stage 1 decided about the workspace's lists and count arrays, for stage 2
+  mia_step_args_t a;               // the step, as the caller handed it in
+  StepState st;                    // what stage 1 leaves for stage 2
   int opts[MIA_OPT_COUNT_];        // the route options as they stood when the caller submitted the step
   long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};      // host time stamps (ns): submitted, A begins, A done, B has it, its preparation seen done,
                                                    // analysis enqueued, read-back enqueued (mia_debug_step_trace)
@@ -1239,9 +886,8 @@ struct StepJob {
   bool done = false;
   int run(int stage) {
     struct Scope { Scope(const int* o) { mia::option_override(o); } ~Scope() { mia::option_override(nullptr); } } scope(opts);
-    return step_impl(X, G, m, k, Yb, d, P, grid, obs, n_coord, cg, rc_, n_r, eps, inf, gamma, method, hint, comm, n_chunks, phase,
-                     Xa, flags, counters, ws, ws_bytes, stream, comm_stream, prep_stream, step_flags, stage, &pe, &seq,
-                     (hipEvent_t)t0, (hipEvent_t)t1, stage == 2 ? &kdone : nullptr, &dec, cyclic ? per : nullptr);
+    st.stage = stage;
+    return step_impl(a, &st);
   }
 };
 struct LaunchThreads {
@@ -1333,21 +979,21 @@ struct LaunchThreads {
       // from the end of one to the start of the next, 6-7 without): 0.093 -> 0.088 ms per step once the chip has room for
       // the preparation beside the analysis kernel (it made no difference while the three-wave kernel filled it).  The
       // preparation runs two steps ahead, so the wait is short; query + yield rather than a spinning synchronise.
-      if (rc == MIA_OK && j->pe && (j->step_flags & MIA_STEP_NO_JOIN) && mia::option(MIA_OPT_STEP_HOSTWAIT) != 0) {
+      if (rc == MIA_OK && j->st.pe && (j->st.flags & MIA_STEP_NO_JOIN) && mia::option(MIA_OPT_STEP_HOSTWAIT) != 0) {
         hipError_t q;
-        while ((q = hipEventQuery(j->pe)) == hipErrorNotReady) relax();      // (a microsecond between two queries: the runtime's locks are
+        while ((q = hipEventQuery(j->st.pe)) == hipErrorNotReady) relax();      // (a microsecond between two queries: the runtime's locks are
                                                                              //  the caller's and the other launch thread's too)
-        if (q == hipSuccess) j->step_flags |= kStepPrepDone;
+        if (q == hipSuccess) j->st.flags |= kStepPrepDone;
         else (void)hipGetLastError();         // (leave the ordering to the stream wait)
       }
       const auto tb0 = std::chrono::steady_clock::now();
       j->ts[4] = now_ns();
       if (rc == MIA_OK) rc = j->run(2);
       j->ts[5] = now_ns();
-      if (rc == MIA_OK && j->host8) {
+      if (rc == MIA_OK && j->a.host8) {
         // (the read-back waits for the kernel's own completion event when the launch carried one: no marker on the stream)
-        if (j->kdone && j->after == j->stream) rc = readback_after_event(j->counters, j->host8, j->kdone, j->on, j->done_event);
-        else rc = mia_letkf_step_readback(j->counters, j->host8, j->after, j->on, j->done_event);
+        if (j->st.kdone && j->a.after_stream == j->a.stream) rc = readback_after_event(j->a.counters, j->a.host8, j->st.kdone, j->a.on_stream, j->a.done_event);
+        else rc = mia_letkf_step_readback(j->a.counters, j->a.host8, j->a.after_stream, j->a.on_stream, j->a.done_event);
       }
       j->rc = rc;
       ns_b += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tb0).count();
@@ -1372,27 +1018,15 @@ LaunchThreads g_launcher;
 }  // namespace
 
 static thread_local long long t_submit_entry = 0;      // (diagnostics: when the argument-block submission was entered, mia_debug_step_trace)
-static int step_submit(const float* X, int64_t G, int m, int k, const float* Yb, const float* d, int64_t P,
-                       const double* grid_xyz, const double* obs_xyz, int n_coord, const int32_t* coord_group,
-                       const double* gc_c, int n_r, double gc_eps, float inf_factor, float gamma, int method,
-                       int p_max_assumed, mia_comm_t* comm, int n_chunks, int phase, float* Xa, int32_t* flags,
-                       int32_t* counters, void* ws, size_t ws_bytes, void* stream, void* comm_stream,
-                       void* prep_stream, int step_flags, int32_t* host8, void* after_stream, void* on_stream,
-                       void** done_event, void* time_start_event, void* time_stop_event, void** job_out, const double* period) {
-  if (!job_out || !coord_group || !gc_c) return MIA_ERR_NULL;
-  if (n_coord < 1 || n_coord > MIA_MAX_COORD || n_r < 1 || n_r > MIA_MAX_RADII) return MIA_ERR_SIZE;
-  if (mia::check_period(period, n_coord, &period) != MIA_OK) return MIA_ERR_ARG;
+// hands a checked block to the launch threads: the one copy of the block a submitted step costs
+static int step_submit(const mia_step_args_t& a, void** job_out) {
+  if (!job_out) return MIA_ERR_NULL;
+  if (!step_tables_fit(a.n_coord, a.n_r)) return MIA_ERR_SIZE;
+  const double* period = nullptr;
+  if (step_period(a, &period) != MIA_OK) return MIA_ERR_ARG;
   StepJob* j = new StepJob();
-  j->cyclic = period != nullptr;
-  for (int c = 0; c < n_coord; ++c) j->per[c] = period ? period[c] : 0.0;
-  j->X = X; j->G = G; j->m = m; j->k = k; j->Yb = Yb; j->d = d; j->P = P; j->grid = grid_xyz; j->obs = obs_xyz;
-  j->n_coord = n_coord; j->n_r = n_r; j->eps = gc_eps; j->inf = inf_factor; j->gamma = gamma; j->method = method;
-  for (int c = 0; c < n_coord; ++c) j->cg[c] = coord_group[c];
-  for (int r = 0; r < n_r; ++r) j->rc_[r] = gc_c[r];
-  j->hint = p_max_assumed; j->comm = comm; j->n_chunks = n_chunks; j->phase = phase; j->Xa = Xa; j->flags = flags;
-  j->counters = counters; j->ws = ws; j->ws_bytes = ws_bytes; j->stream = stream; j->comm_stream = comm_stream;
-  j->prep_stream = prep_stream; j->step_flags = step_flags; j->host8 = host8; j->after = after_stream; j->on = on_stream;
-  j->done_event = done_event; j->t0 = time_start_event; j->t1 = time_stop_event;
+  j->a = a;
+  j->st.flags = a.step_flags;
   mia::option_snapshot(j->opts);
   j->ts[0] = LaunchThreads::now_ns();
   j->ts[7] = t_submit_entry;            // (diagnostics: entry of the argument-block submission; 0 through the plain entry)
@@ -1422,9 +1056,11 @@ extern "C" int mia_letkf_step_submit(const float* X, int64_t G, int m, int k, co
                                      int32_t* counters, void* ws, size_t ws_bytes, void* stream, void* comm_stream,
                                      void* prep_stream, int step_flags, int32_t* host8, void* after_stream, void* on_stream,
                                      void** done_event, void* time_start_event, void* time_stop_event, void** job_out) {
-  return step_submit(X, G, m, k, Yb, d, P, grid_xyz, obs_xyz, n_coord, coord_group, gc_c, n_r, gc_eps, inf_factor, gamma, method,
-                     p_max_assumed, comm, n_chunks, phase, Xa, flags, counters, ws, ws_bytes, stream, comm_stream, prep_stream,
-                     step_flags, host8, after_stream, on_stream, done_event, time_start_event, time_stop_event, job_out, nullptr);
+  if (!job_out) return MIA_ERR_NULL;
+  MIA_STEP_BLOCK_FROM_PARAMETERS(a);      // (may return MIA_ERR_NULL / MIA_ERR_SIZE)
+  a.host8 = host8; a.after_stream = after_stream; a.on_stream = on_stream; a.done_event = done_event;
+  a.time_start_event = time_start_event; a.time_stop_event = time_stop_event;
+  return step_submit(a, job_out);
 }
 
 extern "C" int mia_letkf_step_submit_args(const mia_step_args_t* a, void** job_out) {
@@ -1440,10 +1076,7 @@ extern "C" int mia_letkf_step_submit_args(const mia_step_args_t* a, void** job_o
       if (rc != MIA_OK) return rc;
     }
   }
-  return step_submit(a->X, a->G, a->m, a->k, a->Yb, a->d, a->P, a->grid_xyz, a->obs_xyz, a->n_coord, a->coord_group, a->gc_c,
-                     a->n_r, a->gc_eps, a->inf_factor, a->gamma, a->method, a->p_max_assumed, a->comm, a->n_chunks, a->phase,
-                     a->Xa, a->flags, a->counters, a->ws, a->ws_bytes, a->stream, a->comm_stream, a->prep_stream, a->step_flags,
-                     a->host8, a->after_stream, a->on_stream, a->done_event, a->time_start_event, a->time_stop_event, job_out, a->period);
+  return step_submit(*a, job_out);
 }
 
 // One step taken at once on the caller's thread through the argument block: what mia_letkf_step_drain + the step call +
@@ -1451,7 +1084,7 @@ extern "C" int mia_letkf_step_submit_args(const mia_step_args_t* a, void** job_o
 extern "C" int mia_letkf_step_run_args(const mia_step_args_t* a, int32_t* out8) {
   if (!a || !a->done_event || !a->host8) return MIA_ERR_NULL;
   const double* period = nullptr;
-  if (mia::check_period(a->period, period_coords(a->n_coord), &period) != MIA_OK) return MIA_ERR_ARG;
+  if (step_period(*a, &period) != MIA_OK) return MIA_ERR_ARG;
   int rc = mia_letkf_step_drain();       // (a synchronous step must not overtake queued ones)
   if (rc != MIA_OK) return rc;
   if (a->in_event) {
@@ -1459,12 +1092,9 @@ extern "C" int mia_letkf_step_run_args(const mia_step_args_t* a, int32_t* out8) 
     if (rc != MIA_OK) return rc;
   }
   if ((a->time_start_event == nullptr) != (a->time_stop_event == nullptr)) return MIA_ERR_NULL;
-  hipEvent_t pe = nullptr;
-  uint32_t seq = 0;
-  rc = step_impl(a->X, a->G, a->m, a->k, a->Yb, a->d, a->P, a->grid_xyz, a->obs_xyz, a->n_coord, a->coord_group, a->gc_c, a->n_r, a->gc_eps,
-                 a->inf_factor, a->gamma, a->method, a->p_max_assumed, a->comm, a->n_chunks, a->phase, a->Xa, a->flags, a->counters, a->ws,
-                 a->ws_bytes, a->stream, a->comm_stream, a->prep_stream, a->step_flags & ~MIA_STEP_NO_JOIN, 0, &pe, &seq,
-                 (hipEvent_t)a->time_start_event, (hipEvent_t)a->time_stop_event, nullptr, nullptr, period);
+  StepState st;
+  st.flags = a->step_flags & ~MIA_STEP_NO_JOIN;
+  rc = step_impl(*a, &st);
   if (rc != MIA_OK) return rc;
   rc = mia_letkf_step_readback(a->counters, a->host8, a->after_stream, a->on_stream, a->done_event);
   if (rc != MIA_OK || !out8) return rc;

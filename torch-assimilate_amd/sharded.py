@@ -665,6 +665,23 @@ class ShardedLetkf:
         self._submitted = n_sub + 1
         return h
 
+    def _slot_step_args(self, slot, G, m, k, P, nc, flags):
+        """A step argument block (mia_step_args_t) with what a pipeline slot keeps from step to step: sizes, coordinate groups, periods,
+        radii, the slot's flags / counters / workspace / read-back buffers.  Made when a slot's key changes, not per step."""
+        import ctypes as C
+        a = _cabi.StepArgs()
+        a.G, a.m, a.k, a.P, a.n_coord, a.n_r = G, m, k, P, nc, len(self.radii)
+        for i_ in range(nc):
+            a.coord_group[i_] = slot["cg"][i_]
+            a.period[i_] = slot["per"][i_]
+        for i_ in range(len(self.radii)):
+            a.gc_c[i_] = slot["rc"][i_]
+        a.flags, a.counters, a.ws, a.ws_bytes = flags.data_ptr(), slot["counters"].data_ptr(), slot["ws"].data_ptr(), slot["ws"].numel()
+        a.host8 = slot["host"].data_ptr()
+        a.done_event = C.pointer(slot["event"])
+        a.phase = 0
+        return a
+
     def _native_submit(self, X, grid_xyz, obs_xyz, Yb, d, G, g0, g1, pipelined, geometry_id=None):
         import ctypes as C
         import torch.distributed as dist
@@ -836,21 +853,11 @@ class ShardedLetkf:
             # stream for the caller's stream (inputs and `out`'s memory are ready) is part of the same call
             a = slot.get("args")
             if a is None or slot.get("args_key") != key:
-                a = slot["args"] = _cabi.StepArgs()
+                a = slot["args"] = self._slot_step_args(slot, G, m, k, P, nc, flags)
                 slot["args_key"] = key
                 if "in_event" not in slot:
                     slot["in_event"] = C.c_void_p()
-                a.G, a.m, a.k, a.P, a.n_coord, a.n_r = G, m, k, P, nc, len(self.radii)
-                for i_ in range(nc):
-                    a.coord_group[i_] = slot["cg"][i_]
-                    a.period[i_] = slot["per"][i_]
-                for i_ in range(len(self.radii)):
-                    a.gc_c[i_] = slot["rc"][i_]
-                a.flags, a.counters, a.ws, a.ws_bytes = flags.data_ptr(), slot["counters"].data_ptr(), slot["ws"].data_ptr(), slot["ws"].numel()
-                a.host8 = slot["host"].data_ptr()
-                a.done_event = C.pointer(slot["event"])
                 a.in_event = C.pointer(slot["in_event"])
-                a.phase = 0
                 slot["job"] = C.c_void_p()
                 slot["job_ref"] = C.byref(slot["job"])
                 slot["args_ref"] = C.byref(a)
@@ -888,17 +895,8 @@ class ShardedLetkf:
                 and geometry_id is None and g0 == 0 and g1 == G and ev is not None):
             f = self._fast_serial
             if (f is None or f["st"] is not st or f["slot"] is not slot or slot.get("serial_key") != key or f["device"] != X.device):
-                a = _cabi.StepArgs()
-                a.G, a.m, a.k, a.P, a.n_coord, a.n_r = G, m, k, P, nc, len(self.radii)
-                for i_ in range(nc):
-                    a.coord_group[i_] = slot["cg"][i_]
-                    a.period[i_] = slot["per"][i_]
-                for i_ in range(len(self.radii)):
-                    a.gc_c[i_] = slot["rc"][i_]
-                a.flags, a.counters, a.ws, a.ws_bytes = flags.data_ptr(), slot["counters"].data_ptr(), slot["ws"].data_ptr(), slot["ws"].numel()
-                a.host8 = slot["host"].data_ptr()
-                a.done_event = C.pointer(slot["event"])
-                a.phase, a.n_chunks, a.comm = 0, 1, None
+                a = self._slot_step_args(slot, G, m, k, P, nc, flags)
+                a.n_chunks, a.comm = 1, None
                 a.comm_stream = side
                 slot["serial_key"] = key
                 self._fast_serial = dict(st=st, lib=lib, slot=slot, args=a, args_ref=C.byref(a), out8=(C.c_int32 * 8)(), G=G, m=m, k=k, P=P,
