@@ -395,6 +395,25 @@ int mia_letkf_analysis_retry_f64(const double* X, int64_t ldx, int m, int k, int
                                  double* Xa, int64_t ldo, int64_t o0, int32_t* flags, void* stream);
 int mia_letkf_matfun_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P);
 
+/* The same analysis in FLOAT64 on tiles for DENSE local networks, p_max > k (csrc/letkf_dense64.hip): observations at every
+ * grid point with a radius of a few grid lengths, any 2-D mesh.  The primal form of the route above: the matrix functions
+ * 1 / sqrt(1 + t) and 1 / (1 + t) of C_g = Yw^T diag(rho_g) Yw (k x k, what core/etkf.py:57-77 decomposes) are applied to the
+ * centred state row by one Chebyshev recurrence whose product C_g u = Yw^T (rho_g o (Yw u)) streams the union of the tile's
+ * lists through the wavefront sixteen slots at a time; C_g is never formed, every product is a v_mfma_f64_16x16x4_f64.
+ * Argument list, validation order, flags, decline counter, truncation target and degree cap as
+ * mia_letkf_analysis_matfun_f64; declined points are redone by mia_letkf_analysis_retry_f64.  Shapes: 2 <= k <= 64,
+ * k < p_max <= the slots of the record image in LDS (256, fewer where 256 records of k + 1 doubles do not fit: 224 at
+ * k = 64), any m; everything else -- p_max <= k included, which is mia_letkf_analysis_matfun_f64's -- returns
+ * MIA_ERR_UNSUPPORTED before any launch, as do gamma > 0, the option "tile" = 0 and a coefficient table that cannot be had.
+ * mia_letkf_dense_f64_cover: 1 when the shape is inside the route, 0 when not (host only, no device work). */
+int mia_letkf_analysis_dense_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
+                                 const double* rec, int64_t P,
+                                 const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w,
+                                 int p_cap, int p_max, double inf_factor, double gamma,
+                                 double* Xa, int64_t ldo, int64_t o0, int32_t* flags, int32_t* retry_count,
+                                 void* stream);
+int mia_letkf_dense_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P);
+
 /* Kernelised variant: KETKFModule with RBFKernel(gamma) (core/ketkf.py:65-94,
  * kernels/rbf.py:75-81,110-111), same localisation and transform (LKETKF,
  * interface/lketkf.py:77). */

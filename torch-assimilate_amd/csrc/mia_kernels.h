@@ -64,6 +64,17 @@ int tile64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g
                            double inf_factor, double* Xa, int64_t ldo, int64_t o0, int32_t* flags, int32_t* retry_count,
                            hipStream_t stream);
 
+// letkf_dense64.hip: the float64 analysis on tiles for dense local networks (primal form, 2 <= k <= 64, k < p_max <= the
+// slots of the LDS record image, any number of state rows): the union streams through the wave block by block, C_g is never
+// formed.  dense64_route_covers: shape test (host only; false for p_max <= k, which is letkf_tile64.hip's);
+// dense64_analysis_launch: MIA_ERR_UNSUPPORTED outside it, with the option tile = 0, and when its coefficient table cannot
+// be had.
+bool dense64_route_covers(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t ng);
+int dense64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t ng, const double* rec,
+                            const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                            double inf_factor, double* Xa, int64_t ldo, int64_t o0, int32_t* flags, int32_t* retry_count,
+                            hipStream_t stream);
+
 // Completion event for the next tile-kernel launch of this thread (set by the step driver around the analysis call of a
 // step in flight): the launch then carries the event in its own dispatch packet (hipExtLaunchKernel) instead of the caller
 // recording a marker packet behind it -- one packet less between two kernels of the analysis queue.  Cleared by the launch

@@ -557,6 +557,17 @@ class LetkfEngine:
     # Chebyshev recurrence -- so there is no hand-over; the attribute stays for experiments
     MATFUN_MAX_ROWS = 1 << 30
 
+    # method="auto" hands a float64 shape with p_max > k to the dense tile route only while DENSE64_AUTO_DEN * p_max <=
+    # DENSE64_AUTO_NUM * k (p_max <= 2.4 k).  Measured on MI355X (tools/time_dense64.py, profiles/dense64_time.json):
+    # 1e5 points, against the Jacobi kernel: k 20 p 31 9.3x, k 40 p 77 16.6x (8 state rows 3.1x), k 64 p 153 7.6x, but the
+    # 316 x 316 mesh at k 40 p 101 only 1.12x (unions of 16 consecutive points near 250 slots: tiles run in parts) while
+    # the 1-D network at k 40 p 173 gains 2.6x.  The gain is therefore no function of the shape alone; "auto" stays below the
+    # smallest p_max / k at which a measured case missed the factor 2, and method="dense64" names the route everywhere
+    # the kernel covers.  State rows: a further row costs 2.8 ms on the dense route and 0.9 ms on the Jacobi kernel (k 40 p 77),
+    # so the factor falls below 2 near 13 rows; "auto" hands over up to the 8 rows that were measured
+    DENSE64_AUTO_NUM, DENSE64_AUTO_DEN = 12, 5
+    DENSE64_AUTO_MAX_ROWS = 8
+
     def analysis(self, X: torch.Tensor, Yb: Optional[torch.Tensor], d: Optional[torch.Tensor],
                  nbrs: NeighbourLists, inf_factor: float = 1.0, return_weights: bool = False,
                  rbf_gamma: Optional[float] = None, out: Optional[torch.Tensor] = None, out_offset: int = 0,
@@ -571,7 +582,10 @@ class LetkfEngine:
         return the weights); "matfun" = eigensolver-free Chebyshev matrix-function route (float32, few
         state rows, no weights), with the eigensolver redoing the grid points it declines; "matfun64" =
         the same route in float64 on tiles of sixteen points (2 <= k <= 64, p_max <= k, plain ETKF core,
-        no weights); "auto" picks matfun / matfun64 by the state's dtype when it applies.  With ``defer_retry`` the (8-byte, synchronising) read of the decline
+        no weights); "dense64" = its primal form for dense local networks (2 <= k <= 64, k < p_max <= 256 slots, same
+        conditions); "auto" picks matfun / matfun64 / dense64 by the state's dtype and the shape when one applies
+        (dense64 only while p_max <= 2.4 k and m <= 8, see DENSE64_AUTO_NUM).
+        With ``defer_retry`` the (8-byte, synchronising) read of the decline
         counter is left to the caller: the return value gains a trailing callable that must be invoked.
         ``retry`` (1 int32, zeroed by the caller) / ``flags`` (n int32): caller-owned counter and flag
         buffers, e.g. one counter shared by the launches of several sub-ranges.
@@ -591,8 +605,8 @@ class LetkfEngine:
             self._keep_rec = rec      # (a record buffer packed during HIP-graph capture must outlive the capture)
         if rec.dtype != dtype or rec.shape[1] != (k + 1 + 3) // 4 * 4:
             raise ValueError("packed records do not match the state's dtype / ensemble size")
-        if method not in ("auto", "eig", "matfun", "matfun64"):
-            raise ValueError("method must be 'auto', 'eig', 'matfun' or 'matfun64'")
+        if method not in ("auto", "eig", "matfun", "matfun64", "dense64"):
+            raise ValueError("method must be 'auto', 'eig', 'matfun', 'matfun64' or 'dense64'")
         P = rec.shape[0]
         n = nbrs.g1 - nbrs.g0
         if out is None:
@@ -652,21 +666,29 @@ class LetkfEngine:
         can_matfun = dtype == torch.float32 and not return_weights and n > 0
         if method == "matfun" and not can_matfun:
             raise ValueError("the matfun route needs float32 and cannot return the weights")
-        # float64 on tiles (csrc/letkf_tile64.hip): plain ETKF core, no weights.  "auto" falls back to the Jacobi kernel
-        # where the shape is outside the route; "matfun64" names the route and raises there instead.
+        # float64 on tiles (csrc/letkf_tile64.hip: p_max <= k; csrc/letkf_dense64.hip: p_max > k): plain ETKF core, no weights.
+        # "auto" tries the two in this order (the dense one up to p_max = 2.4 k) and falls back to the Jacobi kernel elsewhere; "matfun64"
+        # and "dense64" name one route and raise there instead.
         can_matfun64 = dtype == torch.float64 and not return_weights and rbf_gamma is None
-        if method == "matfun64" and not can_matfun64:
-            raise ValueError("the matfun64 route needs float64, the plain ETKF core and cannot return the weights")
+        if method in ("matfun64", "dense64") and not can_matfun64:
+            raise ValueError("the %s route needs float64, the plain ETKF core and cannot return the weights" % method)
         use_matfun = can_matfun and (method == "matfun" or (method == "auto" and m <= self.MATFUN_MAX_ROWS))
         finish = None
-        if can_matfun64 and n > 0 and method in ("auto", "matfun64"):
+        if can_matfun64 and n > 0 and method in ("auto", "matfun64", "dense64"):
             if retry is None:
                 retry = torch.zeros(1, dtype=torch.int32, device=self.device)
-            rc = self.lib.mia_letkf_analysis_matfun_f64(*args, _ptr(flags), _ptr(retry), self._stream())
-            if rc == -3 and method == "auto":      # shape outside the tile kernel (or tile = 0): the Jacobi kernel below
+            rc, name = -3, "mia_letkf_analysis_matfun_f64"
+            if method != "dense64":
+                rc = self.lib.mia_letkf_analysis_matfun_f64(*args, _ptr(flags), _ptr(retry), self._stream())
+            dense_ok = method == "dense64" or (self.DENSE64_AUTO_DEN * nbrs.p_max <= self.DENSE64_AUTO_NUM * k and
+                                               m <= self.DENSE64_AUTO_MAX_ROWS)
+            if rc == -3 and method != "matfun64" and dense_ok:
+                name = "mia_letkf_analysis_dense_f64"
+                rc = self.lib.mia_letkf_analysis_dense_f64(*args, _ptr(flags), _ptr(retry), self._stream())
+            if rc == -3 and method == "auto":      # shape outside both tile kernels (or tile = 0): the Jacobi kernel below
                 pass
             else:
-                _cabi.check(rc, "mia_letkf_analysis_matfun_f64")
+                _cabi.check(rc, name)
                 use_matfun = True
 
                 def finish():
