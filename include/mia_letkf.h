@@ -395,6 +395,35 @@ int mia_letkf_analysis_retry_f64(const double* X, int64_t ldx, int m, int k, int
                                  double* Xa, int64_t ldo, int64_t o0, int32_t* flags, void* stream);
 int mia_letkf_matfun_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P);
 
+/* The WEIGHTS in FLOAT64 on the same tiles (csrc/letkf_tile64w.hip): what LETKF.estimate_weights returns
+ * (interface/letkf.py:127-146: W[g][i][j] = w_mean_i + W_pert_ij of ETKFModule, core/etkf.py:57-103, under
+ * wrapper_localization) in the drop-in classes' default working precision, without an eigensolver.  The frame of
+ * mia_letkf_analysis_matfun_f64 -- union, Gram matrix, Gershgorin bound, table row, degree and decline of every point are
+ * its own, bit for bit -- with one pass of the Chebyshev recurrence per MEMBER c < k on column c of the records, which
+ * yields row c of the sixteen points' weights; every product is a v_mfma_f64_16x16x4_f64.
+ * mia_letkf_weights_matfun_f64: argument list of mia_letkf_weights_matfun_f32 in double.  W [g1-g0][k][k] and flags are
+ * required; the route reads no state and writes no analysis, so X and Xa may be NULL (ldx / ldo are checked only for the
+ * pointer that is given; m must be >= 1 all the same).  Shapes: 2 <= k <= 64, p_max <= k, gamma <= 0; everything else
+ * returns MIA_ERR_UNSUPPORTED before any launch, as do the option "tile" = 0 and a coefficient table that cannot be had
+ * (stream being captured); validation order as mia_letkf_analysis_matfun_f64.  Declined points (degree above the cap 127):
+ * MIA_FLAG_RETRY, counted in *retry_count (device int32, zeroed by the caller), W untouched; a point without observations
+ * gets sqrt(inf_factor) I exactly (etkf.py:91-95); the Chebyshev degree of a written point is in bits 8-15 of its flag.
+ * mia_letkf_weights_retry_f64: the Jacobi kernel (mia_letkf_analysis_packed_f64 with W_opt) restricted to the flagged
+ * points; argument list of mia_letkf_weights_retry_f32 in double, X and Xa required (a one-row zero state serves).
+ * mia_letkf_weights_f64_cover: 1 when the shape is inside the route, 0 when not (host only, no device work). */
+int mia_letkf_weights_matfun_f64(const double* X /* may be NULL */, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
+                                 const double* rec, int64_t P,
+                                 const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w,
+                                 int p_cap, int p_max, double inf_factor, double gamma,
+                                 double* Xa /* may be NULL */, int64_t ldo, int64_t o0, double* W /* [g1-g0][k][k] */,
+                                 int32_t* flags, int32_t* retry_count, void* stream);
+int mia_letkf_weights_retry_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
+                                const double* rec, int64_t P,
+                                const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w,
+                                int p_cap, int p_max, double inf_factor, double gamma,
+                                double* Xa, int64_t ldo, int64_t o0, double* W, int32_t* flags, void* stream);
+int mia_letkf_weights_f64_cover(int k, int p_max, int64_t n_points, int64_t P);
+
 /* The same analysis in FLOAT64 on tiles for DENSE local networks, p_max > k (csrc/letkf_dense64.hip): observations at every
  * grid point with a radius of a few grid lengths, any 2-D mesh.  The primal form of the route above: the matrix functions
  * 1 / sqrt(1 + t) and 1 / (1 + t) of C_g = Yw^T diag(rho_g) Yw (k x k, what core/etkf.py:57-77 decomposes) are applied to the

@@ -64,6 +64,15 @@ int tile64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g
                            double inf_factor, double* Xa, int64_t ldo, int64_t o0, int32_t* flags, int32_t* retry_count,
                            hipStream_t stream);
 
+// letkf_tile64w.hip: the float64 WEIGHTS [ng][k][k] on the same frame (what LETKF.estimate_weights returns,
+// interface/letkf.py:127-146): one pass of the recurrence per member instead of per state row, no state and no analysis.
+// weights64_route_covers: shape test (host only; 2 <= k <= 64, p_max <= k); weights64_launch: MIA_ERR_UNSUPPORTED outside
+// it, with the option tile = 0, and when the float64 coefficient table cannot be had.
+bool weights64_route_covers(int k, int p_max, int64_t ng);
+int weights64_launch(int k, int64_t ng, const double* rec, const int32_t* nbr_cnt, const int32_t* nbr_idx,
+                     const double* nbr_w, int p_cap, int p_max, double inf_factor, double* W, int32_t* flags,
+                     int32_t* retry_count, hipStream_t stream);
+
 // letkf_dense64.hip: the float64 analysis on tiles for dense local networks (primal form, 2 <= k <= 64, k < p_max <= the
 // slots of the LDS record image, any number of state rows): the union streams through the wave block by block, C_g is never
 // formed.  dense64_route_covers: shape test (host only; false for p_max <= k, which is letkf_tile64.hip's);

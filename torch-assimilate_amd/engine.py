@@ -584,7 +584,8 @@ class LetkfEngine:
         the same route in float64 on tiles of sixteen points (2 <= k <= 64, p_max <= k, plain ETKF core,
         no weights); "dense64" = its primal form for dense local networks (2 <= k <= 64, k < p_max <= 256 slots, same
         conditions); "auto" picks matfun / matfun64 / dense64 by the state's dtype and the shape when one applies
-        (dense64 only while p_max <= 2.4 k and m <= 8, see DENSE64_AUTO_NUM).
+        (dense64 only while p_max <= 2.4 k and m <= 8, see DENSE64_AUTO_NUM).  Float64 weights without an eigensolver
+        are :meth:`weights64`'s (weights only, no analysis); ``return_weights=True`` here stays on the Jacobi kernel in float64.
         With ``defer_retry`` the (8-byte, synchronising) read of the decline
         counter is left to the caller: the return value gains a trailing callable that must be invoked.
         ``retry`` (1 int32, zeroed by the caller) / ``flags`` (n int32): caller-owned counter and flag
@@ -725,6 +726,70 @@ class LetkfEngine:
             res.append(flags)
         if defer_retry:
             res.append(finish if finish is not None else (lambda: 0))
+        return res[0] if len(res) == 1 else tuple(res)
+
+    # LETKF.estimate_weights_arrays hands float64 weights to weights64 by default only from this ensemble size on.  Measured on
+    # MI355X (tools/time_weights64.py, profiles/weights64_time.json), 1e5 points, against the Jacobi kernel with W:
+    # counter read included: k 40 p 20 3.25x (14.29 / 4.39 ms), k 64 p 31 6.15x (103.0 / 16.7 ms), but k 20 p 10 only 1.64x
+    # (3.38 / 2.06 ms; spreads below 1 % in all three).  The default therefore starts at the smallest measured k that passed the
+    # factor 2; weights64 itself stays available everywhere the kernel covers
+    WEIGHTS64_AUTO_MIN_K = 40
+
+    def weights64(self, Yb: Optional[torch.Tensor], d: Optional[torch.Tensor], nbrs: NeighbourLists, inf_factor: float = 1.0,
+                  rec: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, return_flags: bool = False,
+                  defer_retry: bool = False, rbf_gamma: Optional[float] = None):
+        """The float64 weights W (n, k, k), W[g, i, j] = w_mean_i + W_pert_ij (LETKF.estimate_weights, letkf.py:127-146), of the
+        shard described by ``nbrs`` on the matrix cores (mia_letkf_weights_matfun_f64, csrc/letkf_tile64w.hip): float64 Yb (k, P)
+        and d (P,) [or their packed records ``rec``], 2 <= k <= 64, p_max <= k, plain ETKF core.  Returns W [, flags (n,)]
+        [, finish] -- or None where the entry answers MIA_ERR_UNSUPPORTED (any other shape, float32 input, ``rbf_gamma``,
+        option tile = 0): the caller then takes ``analysis(..., return_weights=True)``.  Points the kernel declines are redone
+        by the Jacobi kernel (mia_letkf_weights_retry_f64) behind the 8-byte read of the decline counter; with ``defer_retry``
+        that read is left to the caller, who must invoke the trailing callable (it returns the number of points redone)."""
+        if rec is None:
+            if Yb.dim() != 2 or Yb.dtype != torch.float64:
+                return None
+            rec = self.pack_obs(Yb, d, torch.float64)
+        if rec.dtype != torch.float64 or rec.dim() != 2 or rec.shape[1] < 3:
+            return None
+        kp = rec.shape[1]
+        k = int(Yb.shape[0]) if Yb is not None else (int(out.shape[-1]) if out is not None else None)
+        if k is None:
+            raise ValueError("weights64 from packed records alone needs out= (n, k, k) for the ensemble size")
+        if kp != (k + 1 + 3) // 4 * 4:
+            raise ValueError("packed records do not match the ensemble size")
+        n = nbrs.g1 - nbrs.g0
+        if out is None:
+            out = torch.empty((n, k, k), dtype=torch.float64, device=self.device)
+        elif out.shape != (n, k, k) or out.dtype != torch.float64 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float64 tensor (n, k, k)")
+        W = out
+        flags = torch.empty(n, dtype=torch.int32, device=self.device)
+        retry = torch.zeros(1, dtype=torch.int32, device=self.device)
+        gamma = float(rbf_gamma) if rbf_gamma is not None else 0.0
+
+        def args(X, Xa):      # (a closure over rec, the lists and W: a deferred retry finds them alive)
+            return (_ptr(X), nbrs.g1, 1, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0], _ptr(nbrs.cnt), _ptr(nbrs.idx),
+                    _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max, float(inf_factor), gamma, _ptr(Xa), n, 0, _ptr(W), _ptr(flags))
+        rc = self.lib.mia_letkf_weights_matfun_f64(*args(None, None), _ptr(retry), self._stream())
+        if rc == -3:
+            return None
+        _cabi.check(rc, "mia_letkf_weights_matfun_f64")
+
+        def finish():
+            n_retry = int(retry.item())          # host sync (8 bytes)
+            if n_retry:
+                # the Jacobi kernel computes an analysis next to the weights: a one-row zero state and its output, from the workspace
+                x0 = self._workspace("weights64_x0", 8 * k * max(nbrs.g1, 1)).view(torch.float64)[:k * nbrs.g1].zero_()
+                xa = self._workspace("weights64_xa", 8 * k * max(n, 1)).view(torch.float64)
+                _cabi.check(self.lib.mia_letkf_weights_retry_f64(*args(x0, xa), self._stream()), "mia_letkf_weights_retry_f64")
+            return n_retry
+        if not defer_retry:
+            finish()
+        res = [W]
+        if return_flags:
+            res.append(flags)
+        if defer_retry:
+            res.append(finish)
         return res[0] if len(res) == 1 else tuple(res)
 
     # ------------------------------------------------------------------- IEnKS

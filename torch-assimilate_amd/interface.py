@@ -246,6 +246,9 @@ class LETKF(ETKF):
         W = self._weights_on_tiles(x, yb, d, nb, grid_coords, obs_coords)
         if W is not None:
             return W
+        W = self._weights_on_tiles64(yb, d, nb)
+        if W is not None:
+            return W
         _, W = self.engine.analysis(x, yb, d, nb, self.inf_factor, return_weights=True, **self._kernel_args())
         return W
 
@@ -286,6 +289,18 @@ class LETKF(ETKF):
                 nb = lists()
             eng.weights_retry(x, yb, d, nb, self.inf_factor, xa, W, flags)
         return W
+
+    def _weights_on_tiles64(self, yb, d, nb):
+        """The float64 weights on the matrix cores (engine.weights64, csrc/letkf_tile64w.hip) where that route applies: the
+        default dtype, the plain ETKF core, WEIGHTS64_AUTO_MIN_K <= k <= 64 and p_max <= k (below that ensemble size the
+        measured gain over the Jacobi kernel misses the factor 2: LetkfEngine.WEIGHTS64_AUTO_MIN_K) -- from the per-point
+        lists, so with every localisation (host ``dist_func`` and PeriodicMetric included).  Declined points are redone with weights by the Jacobi
+        kernel inside the engine call.  None: the caller takes ``engine.analysis(return_weights=True)``."""
+        ka = self._kernel_args()
+        if (yb.dtype != torch.float64 or ka.get("rbf_gamma") is not None or ka.get("kernel_program") is not None
+                or nb.g1 - nb.g0 <= 0 or yb.shape[0] < self.engine.WEIGHTS64_AUTO_MIN_K):
+            return None
+        return self.engine.weights64(yb, d, nb, self.inf_factor)
 
     def _analysis_by_step_driver(self, x, yb, d, grid_coords, obs_coords, g0, g1):
         """The whole analysis as ONE call of the native step driver (sharded.ShardedLetkf on one rank: observation index, the
