@@ -443,6 +443,28 @@ int mia_letkf_analysis_dense_f64(const double* X, int64_t ldx, int m, int k, int
                                  void* stream);
 int mia_letkf_dense_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P);
 
+/* The analysis of mia_letkf_analysis_matfun_f64 for ensembles ABOVE 64 members (csrc/letkf_wide64.hip): the same mathematics,
+ * input, prologue, coefficient table (target exp(-26), margin 2, degree cap 127), flags and decline counter, with the
+ * sixteen-slot row blocks of a tile's union split over the two (up to 96 slots) or four (up to 128) wavefronts of a
+ * workgroup that share one record image; per recurrence step the waves exchange the right-hand side through LDS.  Every sum
+ * over the union is one chain of v_mfma_f64_16x16x4_f64 in ascending slot order, so a point's bits do not depend on its
+ * tile, the shard boundary or the number of wavefronts.  Argument list and validation order as
+ * mia_letkf_analysis_matfun_f64; declined points are redone by mia_letkf_analysis_retry_f64.  Shapes: 2 <= k <= 128
+ * (k <= 64 is accepted so that the route can be compared with mia_letkf_analysis_matfun_f64, which keeps its own answers:
+ * k > 64 stays MIA_ERR_UNSUPPORTED there), 0 <= p_max <= k, any m; every such shape fits the LDS (k = 128 with p_max = 128:
+ * 153 744 bytes of the 162 816 a workgroup may ask for), so the capacity ends at k = 128.  Everything else returns
+ * MIA_ERR_UNSUPPORTED before any launch, as do gamma > 0, the option "tile" = 0 and a coefficient table that cannot be had
+ * (stream being captured).
+ * mia_letkf_wide_f64_cover: 1 when the shape is inside the route (2 <= k <= 128, 0 <= p_max <= k, k * ld * 8 < 2^31 for
+ * both leading dimensions, the LDS of the chosen instantiation), 0 when not (host only, no device work). */
+int mia_letkf_analysis_wide_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
+                                const double* rec, int64_t P,
+                                const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w,
+                                int p_cap, int p_max, double inf_factor, double gamma,
+                                double* Xa, int64_t ldo, int64_t o0, int32_t* flags, int32_t* retry_count,
+                                void* stream);
+int mia_letkf_wide_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P);
+
 /* Kernelised variant: KETKFModule with RBFKernel(gamma) (core/ketkf.py:65-94,
  * kernels/rbf.py:75-81,110-111), same localisation and transform (LKETKF,
  * interface/lketkf.py:77). */

@@ -568,6 +568,16 @@ class LetkfEngine:
     DENSE64_AUTO_NUM, DENSE64_AUTO_DEN = 12, 5
     DENSE64_AUTO_MAX_ROWS = 8
 
+    # method="auto" hands a float64 shape with more than 64 members and p_max <= k to the wide tile route (csrc/letkf_wide64.hip)
+    # from WIDE64_AUTO_MIN_K members on and up to WIDE64_AUTO_MAX_ROWS state rows.  Measured on MI355X (tools/time_wide64.py,
+    # profiles/wide64_time.json), 1e5 points, against the Jacobi kernel: k 80 p 63 181.2x (319.0 / 1.76 ms),
+    # 8 state rows 44.1x (378.7 / 8.59 ms), k 128 p 62 92.1x (310.4 / 3.37 ms); k 96 p 81 and k 128 p 97 (4.33 / 3.96 ms) have no Jacobi
+    # time at all: that kernel answers MIA_ERR_UNSUPPORTED there.  Every measured case passes the factor 2, so the rule is the
+    # route's own range (matfun64 has k <= 64) and the rows that were measured; method="wide64" names the route everywhere
+    # the kernel covers
+    WIDE64_AUTO_MIN_K = 65
+    WIDE64_AUTO_MAX_ROWS = 8
+
     def analysis(self, X: torch.Tensor, Yb: Optional[torch.Tensor], d: Optional[torch.Tensor],
                  nbrs: NeighbourLists, inf_factor: float = 1.0, return_weights: bool = False,
                  rbf_gamma: Optional[float] = None, out: Optional[torch.Tensor] = None, out_offset: int = 0,
@@ -583,8 +593,15 @@ class LetkfEngine:
         state rows, no weights), with the eigensolver redoing the grid points it declines; "matfun64" =
         the same route in float64 on tiles of sixteen points (2 <= k <= 64, p_max <= k, plain ETKF core,
         no weights); "dense64" = its primal form for dense local networks (2 <= k <= 64, k < p_max <= 256 slots, same
-        conditions); "auto" picks matfun / matfun64 / dense64 by the state's dtype and the shape when one applies
-        (dense64 only while p_max <= 2.4 k and m <= 8, see DENSE64_AUTO_NUM).  Float64 weights without an eigensolver
+        conditions); "wide64" = matfun64's analysis with a tile's union split over two or four wavefronts (2 <= k <= 128,
+        p_max <= k, same conditions; what ensembles of 65 .. 128 members run); "auto" picks matfun / matfun64 / dense64 /
+        wide64 by the state's dtype and the shape when one applies (dense64 only while p_max <= 2.4 k and m <= 8, see
+        DENSE64_AUTO_NUM; wide64 only from WIDE64_AUTO_MIN_K members and up to WIDE64_AUTO_MAX_ROWS state rows -- below
+        65 members matfun64 has taken the shape already).  Points the float64 tile routes decline (Chebyshev degree above 127:
+        observations several times stronger than the background spread) are redone by the Jacobi kernel, which holds a point's
+        matrices in LDS; where it cannot (about 70 local observations and more: e.g. k = 96 with p_max 81, k = 128 with p_max 97,
+        shapes that raised altogether before the wide route) that redo raises MiaError AFTER the other points have been
+        written -- data-dependent; the flags name the declined points (MIA_FLAG_RETRY).  Float64 weights without an eigensolver
         are :meth:`weights64`'s (weights only, no analysis); ``return_weights=True`` here stays on the Jacobi kernel in float64.
         With ``defer_retry`` the (8-byte, synchronising) read of the decline
         counter is left to the caller: the return value gains a trailing callable that must be invoked.
@@ -606,8 +623,8 @@ class LetkfEngine:
             self._keep_rec = rec      # (a record buffer packed during HIP-graph capture must outlive the capture)
         if rec.dtype != dtype or rec.shape[1] != (k + 1 + 3) // 4 * 4:
             raise ValueError("packed records do not match the state's dtype / ensemble size")
-        if method not in ("auto", "eig", "matfun", "matfun64", "dense64"):
-            raise ValueError("method must be 'auto', 'eig', 'matfun', 'matfun64' or 'dense64'")
+        if method not in ("auto", "eig", "matfun", "matfun64", "dense64", "wide64"):
+            raise ValueError("method must be 'auto', 'eig', 'matfun', 'matfun64', 'dense64' or 'wide64'")
         P = rec.shape[0]
         n = nbrs.g1 - nbrs.g0
         if out is None:
@@ -667,26 +684,32 @@ class LetkfEngine:
         can_matfun = dtype == torch.float32 and not return_weights and n > 0
         if method == "matfun" and not can_matfun:
             raise ValueError("the matfun route needs float32 and cannot return the weights")
-        # float64 on tiles (csrc/letkf_tile64.hip: p_max <= k; csrc/letkf_dense64.hip: p_max > k): plain ETKF core, no weights.
-        # "auto" tries the two in this order (the dense one up to p_max = 2.4 k) and falls back to the Jacobi kernel elsewhere; "matfun64"
-        # and "dense64" name one route and raise there instead.
+        # float64 on tiles (csrc/letkf_tile64.hip: p_max <= k <= 64; csrc/letkf_dense64.hip: p_max > k; csrc/letkf_wide64.hip:
+        # p_max <= k <= 128): plain ETKF core, no weights.  "auto" tries the three in this order (the dense one up to
+        # p_max = 2.4 k, the wide one under WIDE64_AUTO_*) and falls back to the Jacobi kernel elsewhere; "matfun64", "dense64"
+        # and "wide64" name one route and raise there instead.
+        tile64_methods = ("matfun64", "dense64", "wide64")
         can_matfun64 = dtype == torch.float64 and not return_weights and rbf_gamma is None
-        if method in ("matfun64", "dense64") and not can_matfun64:
+        if method in tile64_methods and not can_matfun64:
             raise ValueError("the %s route needs float64, the plain ETKF core and cannot return the weights" % method)
         use_matfun = can_matfun and (method == "matfun" or (method == "auto" and m <= self.MATFUN_MAX_ROWS))
         finish = None
-        if can_matfun64 and n > 0 and method in ("auto", "matfun64", "dense64"):
+        if can_matfun64 and n > 0 and method in ("auto",) + tile64_methods:
             if retry is None:
                 retry = torch.zeros(1, dtype=torch.int32, device=self.device)
             rc, name = -3, "mia_letkf_analysis_matfun_f64"
-            if method != "dense64":
+            if method in ("auto", "matfun64"):
                 rc = self.lib.mia_letkf_analysis_matfun_f64(*args, _ptr(flags), _ptr(retry), self._stream())
-            dense_ok = method == "dense64" or (self.DENSE64_AUTO_DEN * nbrs.p_max <= self.DENSE64_AUTO_NUM * k and
+            dense_ok = method == "dense64" or (method == "auto" and self.DENSE64_AUTO_DEN * nbrs.p_max <= self.DENSE64_AUTO_NUM * k and
                                                m <= self.DENSE64_AUTO_MAX_ROWS)
-            if rc == -3 and method != "matfun64" and dense_ok:
+            if rc == -3 and dense_ok:
                 name = "mia_letkf_analysis_dense_f64"
                 rc = self.lib.mia_letkf_analysis_dense_f64(*args, _ptr(flags), _ptr(retry), self._stream())
-            if rc == -3 and method == "auto":      # shape outside both tile kernels (or tile = 0): the Jacobi kernel below
+            wide_ok = method == "wide64" or (method == "auto" and k >= self.WIDE64_AUTO_MIN_K and m <= self.WIDE64_AUTO_MAX_ROWS)
+            if rc == -3 and wide_ok:
+                name = "mia_letkf_analysis_wide_f64"
+                rc = self.lib.mia_letkf_analysis_wide_f64(*args, _ptr(flags), _ptr(retry), self._stream())
+            if rc == -3 and method == "auto":      # shape outside the tile kernels (or tile = 0): the Jacobi kernel below
                 pass
             else:
                 _cabi.check(rc, name)

@@ -57,7 +57,8 @@ class ETKF:
         # the reference's working precision: float64 unless the caller says otherwise (interface/base.py:68,73).  The local
         # analysis then runs on a float64 tile kernel (per-point lists, every product on the matrix cores): csrc/letkf_tile64.hip
         # while no point sees more observations than there are members, csrc/letkf_dense64.hip for dense networks (k < p_max <= 2.4 k, m <= 8,
-        # LetkfEngine.DENSE64_AUTO_NUM); on the Jacobi kernel everywhere else.  An explicit dtype=torch.float32 chooses the
+        # LetkfEngine.DENSE64_AUTO_NUM), csrc/letkf_wide64.hip for ensembles of 65 .. 128 members (p_max <= k, m <= 8,
+        # LetkfEngine.WIDE64_AUTO_*); on the Jacobi kernel everywhere else.  An explicit dtype=torch.float32 chooses the
         # float32 tile kernels and the step driver -- the benchmarked hot path
         self._dtype = torch.float64
         self.dtype = dtype
@@ -354,7 +355,7 @@ class LETKF(ETKF):
         applies: float32, a built-in distance, a shape the kernels take (mia_letkf_tiles_cover).  Declined points are redone by
         the eigensolver kernel from the per-point lists.  Returns (Xa, flags) or None: the caller takes the per-point route
         (float64, the default dtype: ``engine.analysis(method="auto")`` forms the tiles' unions itself from the per-point lists of
-        any metric and runs letkf_tile64_kernel, or letkf_dense64_kernel where k < p_max <= 2.4 k; no explicit ``dtype=torch.float32`` is
+        any metric and runs letkf_tile64_kernel, or letkf_dense64_kernel where k < p_max <= 2.4 k, or letkf_wide64_kernel for 65 .. 128 members with p_max <= k; no explicit ``dtype=torch.float32`` is
         needed to reach a tile kernel)."""
         eng = self.engine
         ka = self._kernel_args()
