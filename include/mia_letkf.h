@@ -465,6 +465,30 @@ int mia_letkf_analysis_wide_f64(const double* X, int64_t ldx, int m, int k, int6
                                 void* stream);
 int mia_letkf_wide_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P);
 
+/* The float64 RBF-kernelised analysis on tiles (csrc/lketkf_tile64.hip): KETKFModule._estimate_weights (core/ketkf.py:65-94)
+ * with RBFKernel(gamma) / GaussKernel (kernels/rbf.py:75-81,110-111) under wrapper_localization (interface/wrapper.py:86-98)
+ * and the transform of interface/base.py:257-278, sixteen grid points per workgroup of four wavefronts, without an
+ * eigensolver.  Input, flags (degree in bits 8-15) and decline counter as mia_letkf_analysis_matfun_f64: float64 packed
+ * records [P][kp] and per-point lists with their float64 sqrt(rho).  The pair statistic sum_s (y_as - y_bs)^2 rho_sg of a tile
+ * is one product on v_mfma_f64_16x16x4_f64 in ascending slot order, the matrix functions of Kc = C K C come from the
+ * Chebyshev recurrence with the float64 primal table (target exp(-26), margin 2, degree cap 127) under the row-sum bound of
+ * K; every sum over members runs in ascending order, so a point's bits do not depend on its tile or the shard boundary.
+ * Argument list and validation order as mia_letkf_analysis_matfun_f64, and gamma > 0 is REQUIRED (MIA_ERR_SIZE otherwise).
+ * Points that see a non-finite record or whose degree exceeds the cap are declined (MIA_FLAG_RETRY, counted in
+ * *retry_count, Xa untouched) and redone by mia_letkf_analysis_retry_f64 with the same gamma; a list longer than p_max gives
+ * MIA_FLAG_OVERFLOW and NaN output; a point without local observations gets mean + sqrt(inf) x'.  Shapes: 2 <= k <= 40,
+ * 0 <= p_max <= 64 (no p_max <= k condition), any m.  Everything else returns MIA_ERR_UNSUPPORTED before any launch, as do
+ * the option "tile" = 0 and a coefficient table that cannot be had (stream being captured).
+ * mia_lketkf_rbf_f64_cover: 1 when the shape is inside the route (the LDS of the chosen instantiation included), 0 when not
+ * (host only, no device work). */
+int mia_lketkf_rbf_analysis_matfun_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
+                                       const double* rec, int64_t P,
+                                       const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w,
+                                       int p_cap, int p_max, double inf_factor, double gamma,
+                                       double* Xa, int64_t ldo, int64_t o0, int32_t* flags, int32_t* retry_count,
+                                       void* stream);
+int mia_lketkf_rbf_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P);
+
 /* Kernelised variant: KETKFModule with RBFKernel(gamma) (core/ketkf.py:65-94,
  * kernels/rbf.py:75-81,110-111), same localisation and transform (LKETKF,
  * interface/lketkf.py:77). */

@@ -95,6 +95,17 @@ int wide64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g
                            double inf_factor, double* Xa, int64_t ldo, int64_t o0, int32_t* flags, int32_t* retry_count,
                            hipStream_t stream);
 
+// lketkf_tile64.hip: the float64 RBF-kernelised analysis on tiles (2 <= k <= 40, lists of at most 64 observations, any number
+// of state rows; no p_max <= k condition): one workgroup of four wavefronts per tile, the pair statistic on the matrix
+// cores, a point's k x k matrix in LDS.  rbf64_route_covers: shape test (host only, the LDS of the chosen instantiation
+// included); rbf64_analysis_launch: MIA_ERR_UNSUPPORTED outside it, without gamma > 0, with the option tile = 0, and when the
+// float64 coefficient table cannot be had.
+bool rbf64_route_covers(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t ng);
+int rbf64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t ng, const double* rec,
+                          const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                          double inf_factor, double gamma, double* Xa, int64_t ldo, int64_t o0, int32_t* flags,
+                          int32_t* retry_count, hipStream_t stream);
+
 // Completion event for the next tile-kernel launch of this thread (set by the step driver around the analysis call of a
 // step in flight): the launch then carries the event in its own dispatch packet (hipExtLaunchKernel) instead of the caller
 // recording a marker packet behind it -- one packet less between two kernels of the analysis queue.  Cleared by the launch

@@ -578,6 +578,27 @@ class LetkfEngine:
     WIDE64_AUTO_MIN_K = 65
     WIDE64_AUTO_MAX_ROWS = 8
 
+    # method="auto" hands a float64 analysis with rbf_gamma to the RBF tile route (csrc/lketkf_tile64.hip) only for
+    # k >= RBF64_AUTO_MIN_K and either ONE state row with p_max <= RBF64_AUTO_MAX_P or up to RBF64_AUTO_MAX_ROWS state rows with
+    # p_max <= RBF64_AUTO_MAX_P_ROWS (and k <= 40: the kernel's cover).  Measured on MI355X (tools/time_rbf64.py,
+    # profiles/rbf64_time.json), 1e5 points, gamma 0.5, against the Jacobi kernel, median ms:
+    #   1-D networks, p_max <= 20:  k 40 m 1 31.6x (59.78 / 1.892), m 8 6.3x (66.28 / 10.54); k 20 m 1 23.5x, m 8 6.2x;
+    #                               k 8 (p 12) m 1 11.5x (2.34 / 0.204), m 8 3.7x (3.35 / 0.896)
+    #   1-D dense network, p_max 57 (unions of 72 slots, tiles in two parts): m 1 8.5x (44.14 / 5.177), m 8 2.5x (50.59 / 20.36)
+    #   316 x 316 mesh, p_max 21 (unions of 52 slots, 3.2 parts per tile): m 1 8.4x (60.01 / 7.147), m 8 1.6x (66.65 / 40.52): MISSES
+    #   316 x 316 mesh, p_max 57 (unions of 191 slots, 15.7 parts per tile): m 1 0.93x (61.30 / 65.95): SLOWER
+    # Every part of a tile repeats the whole pair product and recurrence for sixteen columns, so the gain follows the number
+    # of parts, which is the network's and no function of (m, k, p_max): at p_max 57 the 1-D network gains 8.5x and the mesh
+    # loses.  "auto" therefore stays below the smallest p_max at which a measured case missed the factor 2: 57 with one state
+    # row (the largest that passed beneath it: 21), 21 with more rows (the largest that passed beneath it: 20, at the 8 rows that
+    # were measured; between 1 and 8 rows nothing was measured).  The 1-D dense network thereby forgoes its 8.5x unless
+    # method="rbf64" names the route, which stays available everywhere the kernel covers.  NOT measured: a mesh with p_max <= 20
+    # at 8 state rows -- by the mesh at p_max 21 it would gain less than 2x (and more than 1x); the rule is blind to it
+    RBF64_AUTO_MIN_K = 8
+    RBF64_AUTO_MAX_ROWS = 8
+    RBF64_AUTO_MAX_P = 21
+    RBF64_AUTO_MAX_P_ROWS = 20
+
     def analysis(self, X: torch.Tensor, Yb: Optional[torch.Tensor], d: Optional[torch.Tensor],
                  nbrs: NeighbourLists, inf_factor: float = 1.0, return_weights: bool = False,
                  rbf_gamma: Optional[float] = None, out: Optional[torch.Tensor] = None, out_offset: int = 0,
@@ -594,14 +615,19 @@ class LetkfEngine:
         the same route in float64 on tiles of sixteen points (2 <= k <= 64, p_max <= k, plain ETKF core,
         no weights); "dense64" = its primal form for dense local networks (2 <= k <= 64, k < p_max <= 256 slots, same
         conditions); "wide64" = matfun64's analysis with a tile's union split over two or four wavefronts (2 <= k <= 128,
-        p_max <= k, same conditions; what ensembles of 65 .. 128 members run); "auto" picks matfun / matfun64 / dense64 /
-        wide64 by the state's dtype and the shape when one applies (dense64 only while p_max <= 2.4 k and m <= 8, see
+        p_max <= k, same conditions; what ensembles of 65 .. 128 members run); "rbf64" = the RBF-kernelised core in float64 on
+        tiles (``rbf_gamma`` given, 2 <= k <= 40, lists of at most 64 observations -- no p_max <= k condition --, no
+        ``kernel_program``, no weights; csrc/lketkf_tile64.hip); "auto" picks matfun / matfun64 / dense64 / wide64 / rbf64 by
+        the state's dtype, the core and the shape when one applies (dense64 only while p_max <= 2.4 k and m <= 8, see
         DENSE64_AUTO_NUM; wide64 only from WIDE64_AUTO_MIN_K members and up to WIDE64_AUTO_MAX_ROWS state rows -- below
-        65 members matfun64 has taken the shape already).  Points the float64 tile routes decline (Chebyshev degree above 127:
+        65 members matfun64 has taken the shape already; rbf64 from RBF64_AUTO_MIN_K members, with one state row while
+        p_max <= RBF64_AUTO_MAX_P and with up to RBF64_AUTO_MAX_ROWS state rows while p_max <= RBF64_AUTO_MAX_P_ROWS: beyond that
+        its gain depends on the network -- a 2-D mesh with 57 local observations runs slower than on the Jacobi kernel).  Points the float64 tile routes decline (Chebyshev degree above 127:
         observations several times stronger than the background spread) are redone by the Jacobi kernel, which holds a point's
         matrices in LDS; where it cannot (about 70 local observations and more: e.g. k = 96 with p_max 81, k = 128 with p_max 97,
         shapes that raised altogether before the wide route) that redo raises MiaError AFTER the other points have been
-        written -- data-dependent; the flags name the declined points (MIA_FLAG_RETRY).  Float64 weights without an eigensolver
+        written -- data-dependent; the flags name the declined points (MIA_FLAG_RETRY).  Points rbf64 declines (a non-finite
+        record in their list, degree above 127) are redone the same way.  Float64 weights without an eigensolver
         are :meth:`weights64`'s (weights only, no analysis); ``return_weights=True`` here stays on the Jacobi kernel in float64.
         With ``defer_retry`` the (8-byte, synchronising) read of the decline
         counter is left to the caller: the return value gains a trailing callable that must be invoked.
@@ -623,8 +649,12 @@ class LetkfEngine:
             self._keep_rec = rec      # (a record buffer packed during HIP-graph capture must outlive the capture)
         if rec.dtype != dtype or rec.shape[1] != (k + 1 + 3) // 4 * 4:
             raise ValueError("packed records do not match the state's dtype / ensemble size")
-        if method not in ("auto", "eig", "matfun", "matfun64", "dense64", "wide64"):
-            raise ValueError("method must be 'auto', 'eig', 'matfun', 'matfun64', 'dense64' or 'wide64'")
+        if method not in ("auto", "eig", "matfun", "matfun64", "dense64", "wide64", "rbf64"):
+            raise ValueError("method must be 'auto', 'eig', 'matfun', 'matfun64', 'dense64', 'wide64' or 'rbf64'")
+        # float64 RBF-kernelised filter on tiles (csrc/lketkf_tile64.hip): 2 <= k <= 40, lists of at most 64 observations, no weights
+        can_rbf64 = dtype == torch.float64 and not return_weights and rbf_gamma is not None and kernel_program is None
+        if method == "rbf64" and not can_rbf64:
+            raise ValueError("the rbf64 route needs float64, rbf_gamma, no kernel_program and cannot return the weights")
         P = rec.shape[0]
         n = nbrs.g1 - nbrs.g0
         if out is None:
@@ -713,6 +743,24 @@ class LetkfEngine:
                 pass
             else:
                 _cabi.check(rc, name)
+                use_matfun = True
+
+                def finish():
+                    n_retry = int(retry.item())          # host sync (8 bytes)
+                    if n_retry:
+                        _cabi.check(self.lib.mia_letkf_analysis_retry_f64(*args, _ptr(flags), self._stream()),
+                                    "mia_letkf_analysis_retry_f64")
+                    return n_retry
+        elif can_rbf64 and n > 0 and (method == "rbf64" or (method == "auto" and k >= self.RBF64_AUTO_MIN_K and (
+                (m == 1 and nbrs.p_max <= self.RBF64_AUTO_MAX_P) or
+                (m <= self.RBF64_AUTO_MAX_ROWS and nbrs.p_max <= self.RBF64_AUTO_MAX_P_ROWS)))):
+            if retry is None:
+                retry = torch.zeros(1, dtype=torch.int32, device=self.device)
+            rc = self.lib.mia_lketkf_rbf_analysis_matfun_f64(*args, _ptr(flags), _ptr(retry), self._stream())
+            if rc == -3 and method == "auto":      # shape outside the kernel (or tile = 0): the Jacobi kernel below
+                pass
+            else:
+                _cabi.check(rc, "mia_lketkf_rbf_analysis_matfun_f64")
                 use_matfun = True
 
                 def finish():

@@ -355,8 +355,9 @@ class LETKF(ETKF):
         applies: float32, a built-in distance, a shape the kernels take (mia_letkf_tiles_cover).  Declined points are redone by
         the eigensolver kernel from the per-point lists.  Returns (Xa, flags) or None: the caller takes the per-point route
         (float64, the default dtype: ``engine.analysis(method="auto")`` forms the tiles' unions itself from the per-point lists of
-        any metric and runs letkf_tile64_kernel, or letkf_dense64_kernel where k < p_max <= 2.4 k, or letkf_wide64_kernel for 65 .. 128 members with p_max <= k; no explicit ``dtype=torch.float32`` is
-        needed to reach a tile kernel)."""
+        any metric and runs letkf_tile64_kernel, or letkf_dense64_kernel where k < p_max <= 2.4 k, or letkf_wide64_kernel for 65 .. 128 members with p_max <= k; with an RBF / Gauss kernel
+        it runs lketkf_tile64_kernel for RBF64_AUTO_MIN_K <= k <= 40 with one state row and p_max <= RBF64_AUTO_MAX_P, or up to
+        RBF64_AUTO_MAX_ROWS state rows and p_max <= RBF64_AUTO_MAX_P_ROWS; no explicit ``dtype=torch.float32`` is needed to reach a tile kernel)."""
         eng = self.engine
         ka = self._kernel_args()
         gamma = ka.get("rbf_gamma")
@@ -454,7 +455,10 @@ class KETKF(ETKF):
 
 
 class LKETKF(LETKF):
-    """Localised kernelised ETKF (interface/lketkf.py:37-115; estimate_weights is LETKF's, :77)."""
+    """Localised kernelised ETKF (interface/lketkf.py:37-115; estimate_weights is LETKF's, :77).  In the default dtype (float64)
+    ``analyse_arrays`` with an RBFKernel / GaussKernel runs lketkf_tile64_kernel (csrc/lketkf_tile64.hip) from the per-point lists of
+    any localisation -- built-in metrics, PeriodicMetric, a host ``dist_func`` -- under ``LetkfEngine.RBF64_AUTO_*``; with a
+    ``weight_save_path``, for ``estimate_weights`` and for every other kernel the Jacobi kernel computes it, as before."""
 
     def __init__(self, kernel, localization: Optional[GaspariCohn] = None, inf_factor: float = 1.0,
                  smoother: bool = False, gpu: bool = True, pre_transform=None, post_transform=None,
