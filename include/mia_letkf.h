@@ -93,6 +93,11 @@ const char* mia_status_string(int status);
  *   "tile_fused"       1  step driver, tile route over the bucket index, unions of at most 32 slots, no
  *                         geometry epoch declared: every analysis wavefront localises its own tile first (csrc/letkf_tile2f.hip -- the
  *                         list kernel's code, bit-identical results; no list kernel, no tile lists in memory) / 0: lists first
+ *   "apply64"         -1  the one three-valued option: the float64 ensemble transforms (mia_apply_weights_f64,
+ *                         mia_apply_local_weights_f64) on tiles of sixteen grid points (csrc/apply_local64.hip) -1: for the
+ *                         covered shapes where the measurement of profiles/apply64_time.json says the tile kernel wins / 1: for
+ *                         every covered shape / 0: never (the one-point kernels).  "tile" = 0 also keeps the one-point kernels.
+ *                         Any negative value sets -1, any positive value 1; mia_get_option returns -1, 0 or 1
  * Scope: process-wide defaults, read when a call ENQUEUES its work -- for steps handed to the launch threads
  * (mia_letkf_step_submit) at submission: a step runs with the routes that were in force when it was submitted, whatever is
  * set afterwards.  What differs per runner of one process travels in the call's own arguments (method, step_flags:
@@ -104,6 +109,10 @@ int mia_get_option(const char* name, int* value);
  * arguments included, e.g. "letkf_tile2f_kernel<2, 3, 1, false, 4>"), NUL-terminated into buf[n]; "" before the first launch.
  * Diagnostics only (bench lines and tools label their figures with the kernel that ran): not a route switch. */
 int mia_last_analysis_kernel(char* buf, int n);
+/* The same for the ensemble transform: the kernel mia_apply_weights_f64 / mia_apply_local_weights_f64 launched last (tile
+ * kernel or fallback, e.g. "apply_local64_tile_kernel<3>", "apply_local_weights_kernel<double>"); "" before the first such
+ * launch.  A slot of its own: it never changes what mia_last_analysis_kernel returns.  Diagnostics only. */
+int mia_last_transform_kernel(char* buf, int n);
 
 /* ------------------------------------------------------------------------------------
  * Gaspari-Cohn taper of normalised distances r = dist / c (unit-testable stage).
@@ -578,6 +587,12 @@ int mia_apply_weights_f32(const float* X, int64_t ldx, int m, int k, int64_t g0,
                           const float* W, float* Xa, int64_t ldo, int64_t o0, void* stream);
 int mia_apply_weights_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
                           const double* W, double* Xa, int64_t ldo, int64_t o0, void* stream);
+/* The float64 transform with one weight matrix on the matrix cores (csrc/apply_local64.hip, replaces the einsum of
+ * interface/base.py:257-278 for 2-D weights): mia_apply_weights_f64 takes apply_global64_tile_kernel -- sixteen grid points
+ * as the columns of v_mfma_f64_16x16x4_f64 products, no LDS -- where this returns 1 and the option "apply64" allows, and the
+ * one-point-per-thread kernel otherwise.  1 for 2 <= k <= 128, m >= 1, n_points >= 1 and (k + 3) * ld * 8 < 2^32 for both
+ * leading dimensions (32-bit lane offsets); 0 when not.  Host only, no device work. */
+int mia_apply_f64_cover(int m, int k, int64_t ldx, int64_t ldo, int64_t n_points);
 
 /* Ensemble transform with PER-GRID-POINT weights: _apply_weights with weights of dims (grid, ensemble, ensemble_new)
  * (base.py:257-278; what update_state does with the result of estimate_weights, filter.py:157-164, and what the
@@ -586,6 +601,13 @@ int mia_apply_local_weights_f32(const float* X, int64_t ldx, int m, int k, int64
                                 const float* W, float* Xa, int64_t ldo, int64_t o0, void* stream);
 int mia_apply_local_weights_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
                                 const double* W, double* Xa, int64_t ldo, int64_t o0, void* stream);
+/* The float64 per-point transform on tiles (csrc/apply_local64.hip, replaces the einsum of interface/base.py:257-278 for
+ * 3-D weights): mia_apply_local_weights_f64 takes apply_local64_tile_kernel -- a workgroup per sixteen points, eight state
+ * rows per pass through an LDS image of 1024 * round_up(k, 4) + 64 bytes, W_g straight from memory as the A operand of
+ * v_mfma_f64_16x16x4_f64 -- where this returns 1 and the option "apply64" allows, and the one-point-per-wavefront kernel
+ * otherwise.  1 for 2 <= k <= 128, m >= 1, n_points >= 1 and (k + 3) * ld * 8 < 2^32 for both leading dimensions; the image
+ * of every such k fits what a workgroup may ask for (131 136 bytes at k = 128).  Host only, no device work. */
+int mia_apply_local_f64_cover(int m, int k, int64_t ldx, int64_t ldo, int64_t n_points);
 
 /* ------------------------------------------------------------------------------------
  * Localised IEnKS: one Gauss-Newton update of the ensemble weights per grid point,

@@ -23,6 +23,7 @@ _PROTOS = {
     "mia_set_option": ([C.c_char_p, i32], i32),
     "mia_get_option": ([C.c_char_p, C.POINTER(C.c_int)], i32),
     "mia_last_analysis_kernel": ([C.c_char_p, i32], i32),
+    "mia_last_transform_kernel": ([C.c_char_p, i32], i32),
     "mia_gaspari_cohn_f64": ([vp, i64, vp, vp], i32),
     "mia_gaspari_cohn_f32": ([vp, i64, vp, vp], i32),
     "mia_gaspari_cohn_inf_f64": ([vp, i64, vp, vp], i32),
@@ -110,6 +111,8 @@ _PROTOS = {
     "mia_ketkf_weights_f64": ([vp, vp, i32, i64, f64, C.POINTER(KernelOp), i32, vp, vp, vp, sz, vp], i32),
     "mia_apply_weights_f32": ([vp, i64, i32, i32, i64, i64, vp, vp, i64, i64, vp], i32),
     "mia_apply_weights_f64": ([vp, i64, i32, i32, i64, i64, vp, vp, i64, i64, vp], i32),
+    "mia_apply_f64_cover": ([i32, i32, i64, i64, i64], i32),
+    "mia_apply_local_f64_cover": ([i32, i32, i64, i64, i64], i32),
     "mia_apply_local_weights_f32": ([vp, i64, i32, i32, i64, i64, vp, vp, i64, i64, vp], i32),
     "mia_apply_local_weights_f64": ([vp, i64, i32, i32, i64, i64, vp, vp, i64, i64, vp], i32),
     "mia_lienks_update_f32": ([vp, i64, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp], i32),
@@ -258,6 +261,14 @@ def last_analysis_kernel() -> str:
     """mia_last_analysis_kernel: the analysis kernel launched last, as rocprofv3 names it ('' before the first launch)."""
     buf = C.create_string_buffer(160)
     check(lib().mia_last_analysis_kernel(buf, 160), "mia_last_analysis_kernel")
+    return buf.value.decode()
+
+
+def last_transform_kernel() -> str:
+    """mia_last_transform_kernel: the kernel the float64 ensemble transform launched last (tile kernel or fallback), as rocprofv3
+    names it ('' before the first launch)."""
+    buf = C.create_string_buffer(160)
+    check(lib().mia_last_transform_kernel(buf, 160), "mia_last_transform_kernel")
     return buf.value.decode()
 
 

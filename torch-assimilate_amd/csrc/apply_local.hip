@@ -4,7 +4,7 @@
 //     xa[v][j][g] = mean_vg + sum_i (x[v][i][g] - mean_vg) W[g][i][j]          mean_vg = (1 / k) sum_i x[v][i][g]
 //
 // HBM-bound work: 4 k^2 bytes of W per point once + 8 k bytes per state row and point.  The round-1 kernel (ienks.hip, kept for
-// float64 and ensembles beyond 96 members) gave a wavefront one grid point: its loads of x and stores of xa are one float per
+// ensembles beyond 96 members; float64 has its own tile kernels, apply_local64.hip) gave a wavefront one grid point: its loads of x and stores of xa are one float per
 // 64-byte sector (lanes walk the member axis, ldx floats apart) and W is read again for every state row -- 0.11 ms per row and
 // 1e5 points, five times the analysis kernel's own row loop.  Here a workgroup of four wavefronts owns a TILE of sixteen
 // consecutive grid points:

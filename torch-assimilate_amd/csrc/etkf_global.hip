@@ -417,5 +417,17 @@ extern "C" int mia_apply_weights_f32(const float* X, int64_t ldx, int m, int k, 
 extern "C" int mia_apply_weights_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
                                      const double* W, double* Xa, int64_t ldo, int64_t o0, void* stream) {
   (void)hipGetLastError();  // drop stale per-thread error state left by other users of the runtime
-  return apply_weights_impl<double>(X, ldx, m, k, g0, g1, W, Xa, ldo, o0, (hipStream_t)stream);
+  // grid points as the columns of a float64 matrix-instruction product (apply_local64.hip) where the shape and the option
+  // apply64 allow: the same checks first
+  if (g1 > g0 && g0 >= 0 && m >= 1 && k >= 2 && X && W && Xa && ldx >= g1 && ldo >= o0 + (g1 - g0) && m <= 65535) {
+    const int rc = apply_global64_tile_launch(X, ldx, m, k, g0, g1 - g0, W, Xa, ldo, o0, (hipStream_t)stream);
+    if (rc != MIA_ERR_UNSUPPORTED) return rc;
+  }
+  const int rc = apply_weights_impl<double>(X, ldx, m, k, g0, g1, W, Xa, ldo, o0, (hipStream_t)stream);
+  if (rc == MIA_OK && g1 > g0) {      // the instantiation apply_weights_impl<double> chose
+    const bool small = (size_t)k * 256 * sizeof(double) <= 64 * 1024;
+    const bool wlds = ((size_t)k * k + (size_t)k * (small ? 256 : 64)) * sizeof(double) <= kMaxDynamicLds;
+    note_transform_kernel("apply_weights_kernel<double, %d, %s>", small ? 256 : 64, (small || wlds) ? "true" : "false");
+  }
+  return rc;
 }

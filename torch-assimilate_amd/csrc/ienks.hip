@@ -457,5 +457,12 @@ extern "C" int mia_apply_local_weights_f32(const float* X, int64_t ldx, int m, i
 extern "C" int mia_apply_local_weights_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
                                            const double* W, double* Xa, int64_t ldo, int64_t o0, void* stream) {
   (void)hipGetLastError();
-  return apply_local_weights_impl<double>(X, ldx, m, k, g0, g1, W, Xa, ldo, o0, (hipStream_t)stream);
+  // tiles of sixteen points (apply_local64.hip) where the shape and the option apply64 allow: the same argument checks first
+  if (g1 > g0 && g0 >= 0 && m >= 1 && k >= 2 && X && W && Xa && ldx >= g1 && ldo >= o0 + (g1 - g0)) {
+    const int rc = apply_local64_tile_launch(X, ldx, m, k, g0, g1 - g0, W, Xa, ldo, o0, (hipStream_t)stream);
+    if (rc != MIA_ERR_UNSUPPORTED) return rc;
+  }
+  const int rc = apply_local_weights_impl<double>(X, ldx, m, k, g0, g1, W, Xa, ldo, o0, (hipStream_t)stream);
+  if (rc == MIA_OK && g1 > g0) note_transform_kernel("apply_local_weights_kernel<double>");
+  return rc;
 }

@@ -32,6 +32,21 @@ int apply_local_tile_launch(const float* X, int64_t ldx, int m, int k, int64_t g
 int apply_global_tile_launch(const float* X, int64_t ldx, int m, int k, int64_t g0, int64_t ng, const float* W, float* Xa,
                              int64_t ldo, int64_t o0, hipStream_t stream);
 
+// apply_local64.hip: both transforms in float64 on the same frame (v_mfma_f64_16x16x4_f64, 2 <= k <= 128, any m).
+// apply_*64_covers: shape test (host only; the 32-bit lane offsets and, per point, the LDS of the instantiation);
+// apply_*64_tile_launch: MIA_ERR_UNSUPPORTED outside it, with the option tile = 0, with apply64 = 0, and with apply64 = -1
+// where the round-1 kernel is kept by default (the caller then runs apply_local_weights_kernel / apply_weights_kernel)
+bool apply_local64_covers(int m, int k, int64_t ldx, int64_t ldo, int64_t ng);
+bool apply_global64_covers(int m, int k, int64_t ldx, int64_t ldo, int64_t ng);
+size_t apply_local64_lds_bytes(int k);
+int apply_local64_tile_launch(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t ng, const double* W, double* Xa,
+                              int64_t ldo, int64_t o0, hipStream_t stream);
+int apply_global64_tile_launch(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t ng, const double* W, double* Xa,
+                               int64_t ldo, int64_t o0, hipStream_t stream);
+// The transform kernel an entry point has just put on a stream, under the name rocprofv3 records for it: read back by
+// mia_last_transform_kernel.  A slot of its own: mia_last_analysis_kernel keeps naming the analysis.  printf-style.
+void note_transform_kernel(const char* fmt, ...);
+
 // Chebyshev coefficient tables of the matfun kernels (letkf_cheb.hip, cheb_coef_table): geometric grid of scaled
 // spectral bounds T = L / reg, 32 per octave over 2^-24 .. 2^8; entry i holds {degree, bits of 2 / T} and 64 (phi, psi)
 // coefficient pairs, zero beyond the degree.

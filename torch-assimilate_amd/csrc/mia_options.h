@@ -26,6 +26,10 @@ int option(int id);
 // snapshot of all options (MIA_OPT_COUNT_ ints) / run this thread under a snapshot (nullptr: the process-wide values again)
 void option_snapshot(int* out);
 void option_override(const int* snapshot);
+// "apply64", the one THREE-valued option (kept beside the on/off table above, whose setter folds every value to 0 / 1):
+// the float64 transforms on tiles (apply_local64.hip) -1: where the measurement says they win (default) / 1: every covered
+// shape / 0: never.  Process-wide; the step driver never reaches the float64 transforms, so it is in no snapshot.
+int option_apply64();
 }
 
 // Timing / accuracy experiments of tools/ (phase skipping, tolerances, alternative launch shapes) read the environment --
