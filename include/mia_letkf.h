@@ -558,6 +558,34 @@ int mia_lketkf_kernel_analysis_packed_f64(const double* X, int64_t ldx, int m, i
                                           double* Xa, int64_t ldo, int64_t o0, double* W_opt, int32_t* flags_opt,
                                           void* stream);
 
+/* The float64 kernel-expression analysis on tiles (csrc/lketkf_tile64.hip, instantiated in csrc/lketkf_kern64.hip): the frame of
+ * mia_lketkf_rbf_analysis_matfun_f64 -- input, union by rank, canonical summation order, tiles in parts, flags with the degree
+ * in bits 8-15, decline counter, prior branch, cover 2 <= k <= 40, 0 <= p_max <= 64, any m -- with K(Yb, Yb) and K(Yb, d) from a
+ * kernel expression: the pair statistics the program pushes (x.y, |x - y|_2^2 with B = rho; |x - y|_1 with B = sqrt(rho)) are
+ * one chain of v_mfma_f64_16x16x4_f64 each, the program is evaluated per element with the float64 library exp / pow, and the
+ * spectral bound is the largest ABSOLUTE row sum of K.  The Chebyshev recurrence cannot clamp negative eigenvalues of C K C as
+ * the reference does (core/utils.py:58-59): the entry is right only for a kernel that is positive semidefinite by
+ * construction, and the CALLER vouches for that (kernels.py, kernel_is_psd).  A program that holds MIA_KOP_TANH or MIA_KOP_SIN
+ * answers MIA_ERR_UNSUPPORTED.  Validation in the order of mia_lketkf_rbf_analysis_matfun_f64, with the program check
+ * (the codes of mia_lketkf_kernel_analysis_packed_f64) in place of the gamma check.  Declined points (MIA_FLAG_RETRY: a
+ * non-finite record, degree above 127) are redone by mia_lketkf_kernel_analysis_retry_f64 -- the Jacobi kernel of
+ * mia_lketkf_kernel_analysis_packed_f64 restricted to the flagged points -- with the same program.
+ * mia_lketkf_kernel_f64_cover: the answer of mia_lketkf_rbf_f64_cover (host only, no device work). */
+int mia_lketkf_kernel_analysis_matfun_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
+                                          const double* rec, int64_t P,
+                                          const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w,
+                                          int p_cap, int p_max, double inf_factor,
+                                          const mia_kernel_op_t* prog /* host */, int n_ops,
+                                          double* Xa, int64_t ldo, int64_t o0, int32_t* flags, int32_t* retry_count,
+                                          void* stream);
+int mia_lketkf_kernel_analysis_retry_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
+                                         const double* rec, int64_t P,
+                                         const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w,
+                                         int p_cap, int p_max, double inf_factor,
+                                         const mia_kernel_op_t* prog /* host */, int n_ops,
+                                         double* Xa, int64_t ldo, int64_t o0, int32_t* flags, void* stream);
+int mia_lketkf_kernel_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P);
+
 /* ------------------------------------------------------------------------------------
  * Global (unlocalised) ETKF: one (k, P) solve, ETKF.estimate_weights
  * (interface/etkf.py:99-120) -> weights [k][k]; and the global ensemble transform

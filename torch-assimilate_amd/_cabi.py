@@ -67,6 +67,11 @@ _PROTOS = {
     "mia_lketkf_rbf_analysis_matfun_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
                                             vp, i64, i64, vp, vp, vp], i32),
     "mia_lketkf_rbf_f64_cover": ([i32, i32, i32, i64, i64, i64, i64], i32),
+    "mia_lketkf_kernel_analysis_matfun_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64,
+                                               C.POINTER(KernelOp), i32, vp, i64, i64, vp, vp, vp], i32),
+    "mia_lketkf_kernel_analysis_retry_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64,
+                                              C.POINTER(KernelOp), i32, vp, i64, i64, vp, vp], i32),
+    "mia_lketkf_kernel_f64_cover": ([i32, i32, i32, i64, i64, i64, i64], i32),
     "mia_letkf_weights_matfun_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
                                       vp, i64, i64, vp, vp, vp, vp], i32),
     "mia_letkf_weights_retry_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,

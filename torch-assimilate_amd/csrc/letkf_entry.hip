@@ -374,6 +374,43 @@ extern "C" int mia_lketkf_rbf_f64_cover(int m, int k, int p_max, int64_t ldx, in
   if (P < 0) return 0;
   return rbf64_route_covers(m, k, p_max, ldx, ldo, n_points) ? 1 : 0;
 }
+// the float64 kernel-expression filter on tiles (lketkf_kern64.hip): validation in the order of mia_lketkf_rbf_analysis_matfun_f64,
+// the program check in place of the gamma check, then the one kernel of the route
+extern "C" int mia_lketkf_kernel_analysis_matfun_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
+                                                     const double* rec, int64_t P, const int32_t* nbr_cnt,
+                                                     const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                                                     double inf_factor, const mia_kernel_op_t* prog, int n_ops, double* Xa,
+                                                     int64_t ldo, int64_t o0, int32_t* flags, int32_t* retry_count, void* stream) {
+  (void)hipGetLastError();
+  if (g1 < g0 || g0 < 0 || m < 1 || k < 2 || P < 0 || p_cap < 1 || p_max < 0) return MIA_ERR_SIZE;
+  if (!(inf_factor > 0.0)) return MIA_ERR_SIZE;
+  const int rc = kernel_program_check(prog, n_ops);
+  if (rc != MIA_OK) return rc;
+  const int64_t ng = g1 - g0;
+  if (ng == 0) return MIA_OK;
+  if (!X || !Xa || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
+  if (ldx < g1 || ldo < o0 + ng) return MIA_ERR_SIZE;
+  if (p_max > p_cap) p_max = p_cap;
+  if (P > 0 && !rec) return MIA_ERR_NULL;
+  return kern64_analysis_launch(X, ldx, m, k, g0, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, prog, n_ops, Xa, ldo,
+                                o0, flags, retry_count, (hipStream_t)stream);
+}
+extern "C" int mia_lketkf_kernel_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P) {
+  if (P < 0) return 0;
+  return rbf64_route_covers(m, k, p_max, ldx, ldo, n_points) ? 1 : 0;
+}
+extern "C" int mia_lketkf_kernel_analysis_retry_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
+                                                    const double* rec, int64_t P, const int32_t* nbr_cnt,
+                                                    const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                                                    double inf_factor, const mia_kernel_op_t* prog, int n_ops, double* Xa,
+                                                    int64_t ldo, int64_t o0, int32_t* flags, void* stream) {
+  (void)hipGetLastError();
+  if (!flags) return MIA_ERR_NULL;
+  const int rc = kernel_program_check(prog, n_ops);
+  if (rc != MIA_OK) return rc;
+  return analysis_packed_impl<double>(X, ldx, m, k, g0, g1, rec, P, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor,
+                                      2, 0.0, Xa, ldo, o0, nullptr, flags, (hipStream_t)stream, 1, prog, n_ops);
+}
 extern "C" int mia_letkf_analysis_retry_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
                                             const double* rec, int64_t P, const int32_t* nbr_cnt,
                                             const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,

@@ -67,6 +67,19 @@ __device__ inline T kprog_pair(const KernelProgram<T>& kp, const T* Yt, int kpad
   return kprog_eval(kp, dt, sq, l1, same);
 }
 
+// Chain-rule factor of the clamp c(l) = max(l, 0) in the divided differences of the first-order correction below:
+// (c(lp) - c(lq)) / (lp - lq), in [0, 1] and free of cancellation (1 for two positive eigenvalues, 0 for two that are clamped,
+// l+ / (l+ - l-) for a pair on both sides of the kink).  The correction's closed forms are the divided differences of functions
+// of c + reg; for an INDEFINITE kernel (tanh, periodic: eigenvalues of C K C near -1) they overstate every term that couples a
+// clamped mode, which left such filters at 3e-9 of the reference instead of the 1e-12 of the definite ones.
+template <typename T>
+__device__ inline T clamp_dd(T lp, T lq) {
+  const T cp = lp > T(0) ? lp : T(0), cq = lq > T(0) ? lq : T(0);
+  if (lp > T(0) && lq > T(0)) return T(1);
+  if (!(lp > T(0)) && !(lq > T(0))) return T(0);
+  return (cp - cq) / (lp - lq);
+}
+
 template <typename T, int NT, typename TI = T>
 __global__ __launch_bounds__(NT) void letkf_wave_kernel(WaveParams<T, TI> P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -274,8 +287,10 @@ __global__ __launch_bounds__(NT) void letkf_wave_kernel(WaveParams<T, TI> P) {
     if (!conv) flag |= MIA_FLAG_NOCONV;
     // ---- per-mode values (clamp >= 0 then + reg: core/utils.py:58-59).  u = sqrt(l + reg)
     const T ar = t_sqrt(reg);
+    const bool kexpr = P.kernel_mode == 2;      // a kernel expression may be indefinite: the clamp's factor joins the correction
     for (int r = tid; r < n; r += NT) {
       T lam = S[r * lda + r];
+      if (kexpr) cs[r] = lam;                   // (the rotation buffer is free after the eigensolve: the eigenvalue as found)
       lam = lam > T(0) ? lam : T(0);
       const T le = lam + reg;
       const T u = t_sqrt(le);
@@ -295,7 +310,8 @@ __global__ __launch_bounds__(NT) void letkf_wave_kernel(WaveParams<T, TI> P) {
     // mean term: (D + E + reg)^-1 a  ~=  gM o (a - E (gM o a))        [F_pq = -gM_p gM_q]
     for (int r = tid; r < n; r += NT) {
       T acc = T(0);
-      for (int b = 0; b < n; ++b) if (b != r) acc += sym(S, lda, r, b) * gM[b] * sb[b];
+      if (kexpr) { for (int b = 0; b < n; ++b) if (b != r) acc += sym(S, lda, r, b) * clamp_dd(cs[r], cs[b]) * gM[b] * sb[b]; }
+      else for (int b = 0; b < n; ++b) if (b != r) acc += sym(S, lda, r, b) * gM[b] * sb[b];
       av[r] = gM[r] * (sb[r] - acc);
     }
     __syncthreads();
@@ -309,6 +325,7 @@ __global__ __launch_bounds__(NT) void letkf_wave_kernel(WaveParams<T, TI> P) {
           T F;
           if (P.dual) F = cdual * (ar + ua + ub) / ((ua + ub) * ua * ub * (ar + ua) * (ar + ub));
           else F = -t_sqrt(km1) / (ua * ub * (ua + ub));
+          if (kexpr) F *= clamp_dd(cs[a], cs[b]);
           if (b >= ntrue) F = T(0);
           S[a * lda + b] *= F;
         }

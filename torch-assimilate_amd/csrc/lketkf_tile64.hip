@@ -41,7 +41,24 @@
 // points that see the record are DECLINED (MIA_FLAG_RETRY, counted, Xa untouched), as are points whose degree exceeds the
 // table's cap, and redone by letkf_wave_kernel<double>.  A point without local observations gets the prior branch, whatever
 // its degree would be, and does not count towards the tile's largest degree.
+//
+// Kernel expressions (template parameter ST != 0; instantiated in lketkf_kern64.hip, which includes this file).  Every other
+// reference kernel and every +, *, ** composition is a function of three pair statistics (mia_kernel_prog.h), and each of them
+// is the same product with other operands:
+//     x.y        A = y_as y_bs,       B = rho
+//     |x - y|^2  A = (y_as - y_bs)^2, B = rho
+//     |x - y|_1  A = |y_as - y_bs|,   B = sqrt(rho)     (letkf_wave.hip takes the statistics of the sqrt(rho)-scaled block)
+// ST is the set of statistics an instantiation forms (kStatDot | kStatSq | kStatL1), one accumulator chain each over the same
+// 4 UT unconditional steps.  The accumulators are then copied into ordinary registers by unconditional additions BEFORE the
+// interpreter's first (wave-uniform) branch -- DESIGN 4.2 -- and lane (lr, h) evaluates the program (kprog_eval) on its four
+// (pair h + 4 r, point lr) results.  `same` (DiagKernel) belongs to the RESULT row: it is true exactly for the pairs T(a, a),
+// read from the pair table, and false for the k observation pairs (diag.py:65-66).  Everything after K is in LDS is the RBF
+// form's, with one difference: a dot-product kernel has negative entries, so the spectral bound is the largest ABSOLUTE row
+// sum (||C K C|| <= ||K||_2 <= ||K||_inf for a symmetric K); the signed row sums still centre.  The recurrence is right only for a
+// positive semidefinite K -- the reference clamps negative eigenvalues, a polynomial cannot --: the caller vouches for that
+// (kernels.py, kernel_is_psd).
 #include "mia_cheb_table64.h"
+#include "mia_kernel_prog.h"
 
 namespace mia {
 
@@ -54,7 +71,11 @@ struct Rbf64Params {
   double* Xa; int64_t ldo, o0; int32_t* flags; int32_t* retry_count;
   int dmax;
   const Tab64Hdr* tab_hdr; const double2* tab_c;
+  KernelProgram<double> prog;                                // (ST != 0 only)
 };
+
+// pair statistics an instantiation forms for a kernel expression; 0 = none: the RBF form, exp(ngamma Dist)
+constexpr int kStatDot = 1, kStatSq = 2, kStatL1 = 4;
 
 constexpr int kRbf64MaxK = 40;
 
@@ -66,8 +87,9 @@ __host__ __device__ static inline size_t rbf64_region(int ut, int k, int kp) {
   return a > b ? a : b;
 }
 
-// UT: 16-slot blocks of the union an instantiation holds; NR = ceil(k / 16): rows of a point's matrix a thread owns
-template <int UT, int NR>
+// UT: 16-slot blocks of the union an instantiation holds; NR = ceil(k / 16): rows of a point's matrix a thread owns;
+// ST: statistics set of a kernel expression (0: RBF)
+template <int UT, int NR, int ST>
 __global__ __launch_bounds__(256, 2) void lketkf_tile64_kernel(Rbf64Params P) {
   constexpr int UMAX = 16 * UT, NU = 4 * UT, DS = UMAX + 1;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -112,7 +134,7 @@ __global__ __launch_bounds__(256, 2) void lketkf_tile64_kernel(Rbf64Params P) {
   //      (unconditional loads inside the row's storage; entries beyond the count become index -1)
   const int nl = pm < P.p_cap ? pm : P.p_cap;
   int eidx[NU];
-  double ew[NU];
+  double ew[ST == 0 ? NU : 1];   // (a kernel expression reads sqrt(rho) again where it fills Dl: the interpreter needs the registers)
   int lcnt;
   unsigned long long badmask;
   {
@@ -125,7 +147,7 @@ __global__ __launch_bounds__(256, 2) void lketkf_tile64_kernel(Rbf64Params P) {
       const int pos = sub + 4 * u;
       const int e = pos < nl ? pos : 0;
       eidx[u] = ib[e];
-      ew[u] = wb[e];
+      if constexpr (ST == 0) ew[u] = wb[e];
     }
     const bool pbad = lp < npts && (lcnt > pm || lcnt > P.p_cap || lcnt > UMAX);   // loud failure, never truncate
     if (pbad && wave == 0) {
@@ -219,13 +241,20 @@ __global__ __launch_bounds__(256, 2) void lketkf_tile64_kernel(Rbf64Params P) {
       __syncthreads();
       continue;
     }
+    if constexpr (ST == 0) {
 #pragma unroll
-    for (int u = 0; u < NU; ++u)
-      if (es[u] >= 0) Dl[lp * DS + es[u]] = ew[u];             // (the four wavefronts write the same value)
+      for (int u = 0; u < NU; ++u)
+        if (es[u] >= 0) Dl[lp * DS + es[u]] = ew[u];           // (the four wavefronts write the same value)
+    } else {
+      const double* wb = P.w + (p0 + (lp < npts ? lp : 0)) * P.p_cap;
+#pragma unroll
+      for (int u = 0; u < NU; ++u)
+        if (es[u] >= 0) Dl[lp * DS + es[u]] = wb[sub + 4 * u];   // (es >= 0: entry sub + 4 u lies inside the point's list)
+    }
     __syncthreads();
 
     // ---- Dist on the matrix cores, exp, K to LDS: the pair blocks round-robin over the wavefronts
-    {
+    if constexpr (ST == 0) {
       double rho[UT][4];      // B operand: rho of (slot 16 t + 4 q + h, point lr)
 #pragma unroll
       for (int t = 0; t < UT; ++t)
@@ -250,6 +279,45 @@ __global__ __launch_bounds__(256, 2) void lketkf_tile64_kernel(Rbf64Params P) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) Kt[(16 * blk + h + 4 * r) * 16 + lr] = exp(P.ngamma * acc[r]);
       }
+    } else {
+      // a kernel expression: one chain per statistic of the set.  sqrt(rho) is read from LDS at every step: 4 UT values of rho
+      // (and of sqrt(rho)) held in registers beside three accumulators and the interpreter's pow spill to scratch at UT >= 3
+#pragma clang loop unroll(disable)
+      for (int blk = wave; blk < NPB; blk += 4) {
+        const int pa = PA[16 * blk + lr];
+        const int ca = pa & 255, cb = pa >> 8;
+        d4t ad = {0., 0., 0., 0.}, as = {0., 0., 0., 0.}, al = {0., 0., 0., 0.};
+#pragma unroll
+        for (int t = 0; t < UT; ++t)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const int slot = 16 * t + 4 * q + h;
+            const double* yr = Yw + slot * KS;
+            const double ya = yr[ca], yb = yr[cb], df = ya - yb;
+            const double dv = Dl[lr * DS + slot], rh = dv * dv;
+            if constexpr ((ST & kStatDot) != 0) ad = MIA_MFMA64(ya * yb, rh, ad);
+            if constexpr ((ST & kStatSq) != 0) as = MIA_MFMA64(df * df, rh, as);
+            if constexpr ((ST & kStatL1) != 0) al = MIA_MFMA64(fabs(df), dv, al);
+          }
+        // the accumulators' first vector reads: unconditional, ahead of the interpreter's branches (x + 0.0 is not folded)
+        double sd[4], ss[4], sl[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          sd[r] = (ST & kStatDot) ? ad[r] + 0.0 : 0.0;
+          ss[r] = (ST & kStatSq) ? as[r] + 0.0 : 0.0;
+          sl[r] = (ST & kStatL1) ? al[r] + 0.0 : 0.0;
+        }
+#pragma clang loop unroll(disable)
+        for (int r = 0; r < 4; ++r) {
+          const int row = 16 * blk + h + 4 * r;               // the RESULT row's pair decides `same`, not the operand row's
+          const int pr = PA[row];
+          const bool same = row < NT && (pr & 255) == (pr >> 8);
+          const double vd = r == 0 ? sd[0] : (r == 1 ? sd[1] : (r == 2 ? sd[2] : sd[3]));
+          const double vs = r == 0 ? ss[0] : (r == 1 ? ss[1] : (r == 2 ? ss[2] : ss[3]));
+          const double vl = r == 0 ? sl[0] : (r == 1 ? sl[1] : (r == 2 ? sl[2] : sl[3]));
+          Kt[row * 16 + lr] = kprog_eval<double>(P.prog, vd, vs, vl, same);
+        }
+      }
     }
     __syncthreads();          // K complete; the record image is dead from here on
 
@@ -261,24 +329,31 @@ __global__ __launch_bounds__(256, 2) void lketkf_tile64_kernel(Rbf64Params P) {
       rok[i] = r0 + 16 * i < k;
       ra[i] = rok[i] ? r0 + 16 * i : 0;
     }
+    //      (a kernel expression: the absolute row sums beside them, parked in V1 until the recurrence's first barrier)
     {
-      double rs[NR];
+      double rs[NR], rab[NR];
       int ix[NR];
 #pragma unroll
-      for (int i = 0; i < NR; ++i) { rs[i] = 0.0; ix[i] = ra[i]; }
+      for (int i = 0; i < NR; ++i) { rs[i] = 0.0; rab[i] = 0.0; ix[i] = ra[i]; }
       for (int b = 0; b < k; ++b) {
 #pragma unroll
         for (int i = 0; i < NR; ++i) {
-          rs[i] += Kt[ix[i] * 16 + p];
+          const double kv = Kt[ix[i] * 16 + p];
+          rs[i] += kv;
+          if constexpr (ST != 0) rab[i] += fabs(kv);
           ix[i] += b < ra[i] ? k - b - 1 : 1;
         }
       }
 #pragma unroll
       for (int i = 0; i < NR; ++i)
-        if (rok[i]) Rs[ra[i] * 16 + p] = rs[i];
+        if (rok[i]) {
+          Rs[ra[i] * 16 + p] = rs[i];
+          if constexpr (ST != 0) V1[ra[i] * 16 + p] = rab[i];
+        }
     }
     __syncthreads();
-    // ---- spectral bound (largest row sum), degree and interval from the table; the centred kernel vector
+    // ---- spectral bound (largest row sum; of |K| for a kernel expression), degree and interval from the table; the centred
+    //      kernel vector
     const bool colact = colok && p >= lo && p < hi;
     const bool noobs = pcnt[p] == 0;
     double alpha;
@@ -288,7 +363,8 @@ __global__ __launch_bounds__(256, 2) void lketkf_tile64_kernel(Rbf64Params P) {
       double L = 0.0, rsum = 0.0, kosum = 0.0;
       for (int b = 0; b < k; ++b) {
         const double v = Rs[b * 16 + p];
-        L = (v > L || v != v) ? v : L;
+        const double bv = ST != 0 ? V1[b * 16 + p] : v;
+        L = (bv > L || bv != bv) ? bv : L;
         rsum += v;
         kosum += Kt[(NT + b) * 16 + p];
       }
@@ -411,28 +487,28 @@ static size_t rbf64_lds_bytes(int ut, int k) {
   return align_up(((size_t)npb * 256 + rbf64_region(ut, k, kp)) * sizeof(double) + ((size_t)16 * ut + 16 * (size_t)npb + 48) * sizeof(int), 16);
 }
 
-template <int UT, int NR>
+template <int UT, int NR, int ST>
 static int rbf64_launch_t(const Rbf64Params& tp, hipStream_t stream) {
   const size_t lds = rbf64_lds_bytes(UT, tp.k);
   if (lds > kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
-  auto kern = lketkf_tile64_kernel<UT, NR>;
+  auto kern = lketkf_tile64_kernel<UT, NR, ST>;
   if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int64_t ntile = (tp.ng + 15) >> 4;
   const int64_t gx = ntile < 65536 ? ntile : 65536;
   const int64_t gy = (ntile + gx - 1) / gx;
   if (gy > 65535) return MIA_ERR_UNSUPPORTED;
   kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(256), lds, stream>>>(tp);
-  note_analysis_kernel("lketkf_tile64_kernel<%d, %d>", UT, NR);
+  note_analysis_kernel("lketkf_tile64_kernel<%d, %d, %d>", UT, NR, ST);     // (ST: 0 RBF; 1 dot, 2 sq, 7 dot + sq + l1)
   MIA_LAUNCH_CHECK();
   return MIA_OK;
 }
 
-template <int UT>
+template <int UT, int ST>
 static int rbf64_launch_u(const Rbf64Params& tp, hipStream_t stream) {
   switch ((tp.k + 15) >> 4) {
-    case 1: return rbf64_launch_t<UT, 1>(tp, stream);
-    case 2: return rbf64_launch_t<UT, 2>(tp, stream);
-    case 3: return rbf64_launch_t<UT, 3>(tp, stream);
+    case 1: return rbf64_launch_t<UT, 1, ST>(tp, stream);
+    case 2: return rbf64_launch_t<UT, 2, ST>(tp, stream);
+    case 3: return rbf64_launch_t<UT, 3, ST>(tp, stream);
   }
   return MIA_ERR_UNSUPPORTED;
 }
@@ -443,6 +519,42 @@ static int rbf64_ut(int p_max) {
   return ut < 1 ? 1 : (ut > 4 ? 4 : ut);
 }
 
+template <int ST>
+static int rbf64_launch_s(const Rbf64Params& tp, hipStream_t stream) {
+  switch (rbf64_ut(tp.p_max)) {
+    case 1: return rbf64_launch_u<1, ST>(tp, stream);
+    case 2: return rbf64_launch_u<2, ST>(tp, stream);
+    case 3: return rbf64_launch_u<3, ST>(tp, stream);
+    case 4: return rbf64_launch_u<4, ST>(tp, stream);
+  }
+  return MIA_ERR_UNSUPPORTED;
+}
+
+// the parameter block of both forms (ngamma and prog are the caller's)
+static Rbf64Params rbf64_params(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t ng, const double* rec,
+                                const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                                double inf_factor, double* Xa, int64_t ldo, int64_t o0, int32_t* flags, int32_t* retry_count,
+                                const CoefTable64* tab) {
+  Rbf64Params tp;
+  tp.X = X; tp.ldx = ldx; tp.m = m; tp.k = k; tp.kp = (k + 1 + 3) & ~3;
+  tp.g0 = g0; tp.ng = ng; tp.rec = rec;
+  tp.cnt = nbr_cnt; tp.idx = nbr_idx; tp.w = nbr_w; tp.p_cap = p_cap; tp.p_max = p_max;
+  const double rg = (double)(k - 1) / inf_factor, km = (double)(k - 1);
+  tp.reg = rg;
+  tp.inv_reg = 1.0 / rg;
+  tp.f0 = sqrt(km / rg);
+  tp.inv_k = 1.0 / (double)k;
+  tp.cs_phi = sqrt(km) / sqrt(rg);
+  tp.cs_psi = 1.0 / rg;
+  tp.ngamma = 0.0;
+  tp.Xa = Xa; tp.ldo = ldo; tp.o0 = o0; tp.flags = flags; tp.retry_count = retry_count;
+  tp.dmax = kTab64Deg - 1;
+  tp.tab_hdr = tab->hdr; tp.tab_c = tab->c;
+  tp.prog.n = 0;
+  return tp;
+}
+
+#ifndef MIA_KERN64_TU
 // RBF kernel, float64, 2 <= k <= 40 members, lists of at most 64 observations (no p_max <= k condition: the matrix is k x k)
 bool rbf64_route_covers(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t ng) {
   if (m < 1 || k < 2 || k > kRbf64MaxK || p_max < 0 || p_max > 64 || ldx < 1 || ldo < 1 || ng < 0) return false;
@@ -458,28 +570,40 @@ int rbf64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g0
   if (!rbf64_route_covers(m, k, p_max, ldx, ldo, ng)) return MIA_ERR_UNSUPPORTED;
   const CoefTable64* tab = cheb_coef_table64(stream, kTab64Primal);
   if (!tab) return MIA_ERR_UNSUPPORTED;
-  Rbf64Params tp;
-  tp.X = X; tp.ldx = ldx; tp.m = m; tp.k = k; tp.kp = (k + 1 + 3) & ~3;
-  tp.g0 = g0; tp.ng = ng; tp.rec = rec;
-  tp.cnt = nbr_cnt; tp.idx = nbr_idx; tp.w = nbr_w; tp.p_cap = p_cap; tp.p_max = p_max;
-  const double rg = (double)(k - 1) / inf_factor, km = (double)(k - 1);
-  tp.reg = rg;
-  tp.inv_reg = 1.0 / rg;
-  tp.f0 = sqrt(km / rg);
-  tp.inv_k = 1.0 / (double)k;
-  tp.cs_phi = sqrt(km) / sqrt(rg);
-  tp.cs_psi = 1.0 / rg;
+  Rbf64Params tp = rbf64_params(X, ldx, m, k, g0, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, Xa, ldo, o0, flags,
+                                retry_count, tab);
   tp.ngamma = -gamma;
-  tp.Xa = Xa; tp.ldo = ldo; tp.o0 = o0; tp.flags = flags; tp.retry_count = retry_count;
-  tp.dmax = kTab64Deg - 1;
-  tp.tab_hdr = tab->hdr; tp.tab_c = tab->c;
-  switch (rbf64_ut(p_max)) {
-    case 1: return rbf64_launch_u<1>(tp, stream);
-    case 2: return rbf64_launch_u<2>(tp, stream);
-    case 3: return rbf64_launch_u<3>(tp, stream);
-    case 4: return rbf64_launch_u<4>(tp, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
+  return rbf64_launch_s<0>(tp, stream);
 }
+#else
+// (this translation unit = lketkf_kern64.hip: the kernel-expression instantiations, compiled beside the RBF ones)
+// The cover is the RBF form's (same LDS layout).  A program's statistics are rounded up to one of three compiled sets:
+// {dot}, {sq}, {dot, sq, l1}; tanh and sin make no positive semidefinite kernel the package knows: MIA_ERR_UNSUPPORTED.
+int kern64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t ng, const double* rec,
+                           const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                           double inf_factor, const mia_kernel_op_t* prog, int n_ops, double* Xa, int64_t ldo, int64_t o0,
+                           int32_t* flags, int32_t* retry_count, hipStream_t stream) {
+  if (!option(MIA_OPT_TILE) || !flags || !retry_count) return MIA_ERR_UNSUPPORTED;
+  if (kernel_program_check(prog, n_ops) != MIA_OK) return MIA_ERR_UNSUPPORTED;
+  if (!rbf64_route_covers(m, k, p_max, ldx, ldo, ng)) return MIA_ERR_UNSUPPORTED;
+  int need = 0;
+  for (int i = 0; i < n_ops; ++i) {
+    const int op = prog[i].op;
+    if (op == MIA_KOP_TANH || op == MIA_KOP_SIN) return MIA_ERR_UNSUPPORTED;
+    if (op == MIA_KOP_DOT) need |= kStatDot;
+    if (op == MIA_KOP_SQDIST) need |= kStatSq;
+    if (op == MIA_KOP_L1DIST) need |= kStatL1;
+  }
+  const CoefTable64* tab = cheb_coef_table64(stream, kTab64Primal);
+  if (!tab) return MIA_ERR_UNSUPPORTED;
+  Rbf64Params tp = rbf64_params(X, ldx, m, k, g0, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, Xa, ldo, o0, flags,
+                                retry_count, tab);
+  tp.prog.n = n_ops;
+  for (int i = 0; i < n_ops; ++i) { tp.prog.op[i] = (unsigned char)prog[i].op; tp.prog.val[i] = prog[i].value; }
+  if (need == kStatDot) return rbf64_launch_s<kStatDot>(tp, stream);
+  if (need == kStatSq || need == 0) return rbf64_launch_s<kStatSq>(tp, stream);      // (a constant kernel needs none)
+  return rbf64_launch_s<kStatDot | kStatSq | kStatL1>(tp, stream);
+}
+#endif
 
 }  // namespace mia

@@ -121,6 +121,14 @@ int rbf64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g0
                           double inf_factor, double gamma, double* Xa, int64_t ldo, int64_t o0, int32_t* flags,
                           int32_t* retry_count, hipStream_t stream);
 
+// lketkf_kern64.hip (the ST != 0 instantiations of lketkf_tile64.hip): the same analysis with K from a kernel expression
+// (host array `prog`, checked here again); the cover is rbf64_route_covers.  MIA_ERR_UNSUPPORTED outside it, for a malformed
+// program or one with tanh / sin, with the option tile = 0, and when the float64 coefficient table cannot be had.
+int kern64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t ng, const double* rec,
+                           const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                           double inf_factor, const mia_kernel_op_t* prog, int n_ops, double* Xa, int64_t ldo, int64_t o0,
+                           int32_t* flags, int32_t* retry_count, hipStream_t stream);
+
 // Completion event for the next tile-kernel launch of this thread (set by the step driver around the analysis call of a
 // step in flight): the launch then carries the event in its own dispatch packet (hipExtLaunchKernel) instead of the caller
 // recording a marker packet behind it -- one packet less between two kernels of the analysis queue.  Cleared by the launch

@@ -599,12 +599,40 @@ class LetkfEngine:
     RBF64_AUTO_MAX_P = 21
     RBF64_AUTO_MAX_P_ROWS = 20
 
+    # method="auto" hands a float64 analysis with a positive semidefinite kernel_program (kernel_psd=True) to the kernel-expression
+    # tile route (csrc/lketkf_kern64.hip) only for ONE state row (KERN64_AUTO_MAX_ROWS), k >= KERN64_AUTO_MIN_K (<= 40: the cover)
+    # and p_max <= KERN64_AUTO_MAX_P.  The rule cannot see the kernel function, so a class passes only if every kernel measured in
+    # it gained 2x.  Measured on MI355X (tools/time_kern64.py, profiles/kern64_time.json), 1e5 points, inflation 1.1,
+    # against the Jacobi expression route, counter read and redo of declined points included, median ms, for
+    # rational (sq, degree 14) / ornuhl (l1, 12) / poly2 (dot, 63 mean, up to 126) / poly2 + ornuhl * scale (all three):
+    #   k 40 p 20  m 1: 15.1x (80.5 / 5.32)  20.2x (76.1 / 3.77)  6.6x (79.1 / 11.98)  5.9x (82.6 / 14.00)
+    #              m 8:  4.6x (88.4 / 19.05)  5.5x (84.0 / 15.21)  1.14x (87.2 / 76.7)  1.15x (90.6 / 78.6): the polynomials MISS
+    #   k 20 p 20  m 1:  8.6x (9.61 / 1.12)  10.4x (9.12 / 0.88)  2.28x (9.31 / 4.08)  2.19x (9.83 / 4.49)   (22 / 23 points redone)
+    #              m 8:  2.9x                 3.2x                 0.57x                0.59x: SLOWER
+    #   k 8  p 12  m 1:  5.1x (2.49 / 0.49)   5.7x (2.39 / 0.42)  1.65x (2.46 / 1.49)  1.71x (2.60 / 1.52): the polynomials MISS
+    #              m 8:  1.7x                 1.9x                 0.42x                0.47x: all MISS
+    #   316 x 316 mesh, k 40 p 21 (tiles in 3.2 parts)
+    #              m 1:  4.9x (83.9 / 17.0)   6.3x (77.4 / 12.4)  3.19x (86.9 / 27.3)  2.61x (88.0 / 33.7)
+    #              m 8:  1.45x                1.67x                0.60x                0.58x: all MISS
+    # A state row costs one Chebyshev recurrence of the point's degree, and a polynomial kernel's degree is 4-5 times an RBF's: with
+    # eight rows the recurrence outweighs the eigensolve it replaces.  So: one row (between 1 and 8 nothing was measured), from the
+    # smallest measured k at which all four kernels passed (20; 8 missed, between them nothing was measured), up to the largest
+    # measured p_max (21; beyond it nothing was measured -- the RBF form loses on a mesh at p_max 57).  The bounded kernels thereby
+    # forgo 3-5x at eight rows and 5x at k = 8 unless method="kern64" names the route, which stays available everywhere the
+    # kernel covers
+    KERN64_AUTO_MIN_K = 20
+    KERN64_AUTO_MAX_ROWS = 1
+    KERN64_AUTO_MAX_P = 21
+
+    def _kern64_auto(self, m: int, k: int, p_max: int) -> bool:
+        return k >= self.KERN64_AUTO_MIN_K and m <= self.KERN64_AUTO_MAX_ROWS and p_max <= self.KERN64_AUTO_MAX_P
+
     def analysis(self, X: torch.Tensor, Yb: Optional[torch.Tensor], d: Optional[torch.Tensor],
                  nbrs: NeighbourLists, inf_factor: float = 1.0, return_weights: bool = False,
                  rbf_gamma: Optional[float] = None, out: Optional[torch.Tensor] = None, out_offset: int = 0,
                  return_flags: bool = False, rec: Optional[torch.Tensor] = None, method: str = "auto",
                  defer_retry: bool = False, retry: Optional[torch.Tensor] = None,
-                 flags: Optional[torch.Tensor] = None, kernel_program=None):
+                 flags: Optional[torch.Tensor] = None, kernel_program=None, kernel_psd: bool = False):
         """X (m, k, G) prior ensemble (grid fastest), Yb (k, P), d (P,) [or their packed records
         ``rec`` from :meth:`pack_obs`]: analysis of the shard described by ``nbrs``.
         Returns Xa (m, k, n) [, W (n, k, k)] [, flags (n,)].
@@ -617,7 +645,9 @@ class LetkfEngine:
         conditions); "wide64" = matfun64's analysis with a tile's union split over two or four wavefronts (2 <= k <= 128,
         p_max <= k, same conditions; what ensembles of 65 .. 128 members run); "rbf64" = the RBF-kernelised core in float64 on
         tiles (``rbf_gamma`` given, 2 <= k <= 40, lists of at most 64 observations -- no p_max <= k condition --, no
-        ``kernel_program``, no weights; csrc/lketkf_tile64.hip); "auto" picks matfun / matfun64 / dense64 / wide64 / rbf64 by
+        ``kernel_program``, no weights; csrc/lketkf_tile64.hip); "kern64" = the same kernel with K from a ``kernel_program``
+        (float64, the cover of rbf64, ``kernel_psd=True``, no tanh / sin, no weights; csrc/lketkf_kern64.hip); "auto" picks
+        matfun / matfun64 / dense64 / wide64 / rbf64 / kern64 by
         the state's dtype, the core and the shape when one applies (dense64 only while p_max <= 2.4 k and m <= 8, see
         DENSE64_AUTO_NUM; wide64 only from WIDE64_AUTO_MIN_K members and up to WIDE64_AUTO_MAX_ROWS state rows -- below
         65 members matfun64 has taken the shape already; rbf64 from RBF64_AUTO_MIN_K members, with one state row while
@@ -627,14 +657,20 @@ class LetkfEngine:
         matrices in LDS; where it cannot (about 70 local observations and more: e.g. k = 96 with p_max 81, k = 128 with p_max 97,
         shapes that raised altogether before the wide route) that redo raises MiaError AFTER the other points have been
         written -- data-dependent; the flags name the declined points (MIA_FLAG_RETRY).  Points rbf64 declines (a non-finite
-        record in their list, degree above 127) are redone the same way.  Float64 weights without an eigensolver
+        record in their list, degree above 127) are redone the same way, as are kern64's (mia_lketkf_kernel_analysis_retry_f64,
+        the Jacobi kernel with the same program; polynomial kernels reach degree 127 much sooner than an RBF kernel).  Float64 weights without an eigensolver
         are :meth:`weights64`'s (weights only, no analysis); ``return_weights=True`` here stays on the Jacobi kernel in float64.
         With ``defer_retry`` the (8-byte, synchronising) read of the decline
         counter is left to the caller: the return value gains a trailing callable that must be invoked.
         ``retry`` (1 int32, zeroed by the caller) / ``flags`` (n int32): caller-owned counter and flag
         buffers, e.g. one counter shared by the launches of several sub-ranges.
         ``rbf_gamma`` selects the RBF-kernelised core (KETKFModule with RBFKernel), ``kernel_program``
-        ([(MIA_KOP_*, value), ...], see kernels.py) the kernel-expression route for every other reference kernel."""
+        ([(MIA_KOP_*, value), ...], see kernels.py) the kernel-expression route for every other reference kernel.
+        ``kernel_psd``: the program's kernel is positive semidefinite by construction (``kernels.kernel_is_psd``; a caller who
+        passes a raw program asserts it) -- the eigensolver-free kern64 route is right only then, because the reference clamps
+        negative eigenvalues of the centred kernel matrix and a polynomial cannot; "auto" takes kern64 for such a float64
+        program under KERN64_AUTO_* (one state row, KERN64_AUTO_MIN_K <= k, p_max <= KERN64_AUTO_MAX_P: with more rows or fewer
+        members a polynomial kernel gains less than 2x or loses) and runs every other program on the Jacobi kernel, as before."""
         if X.dim() == 2:
             X = X[None]
         X = X.to(self.device).contiguous()
@@ -649,12 +685,17 @@ class LetkfEngine:
             self._keep_rec = rec      # (a record buffer packed during HIP-graph capture must outlive the capture)
         if rec.dtype != dtype or rec.shape[1] != (k + 1 + 3) // 4 * 4:
             raise ValueError("packed records do not match the state's dtype / ensemble size")
-        if method not in ("auto", "eig", "matfun", "matfun64", "dense64", "wide64", "rbf64"):
-            raise ValueError("method must be 'auto', 'eig', 'matfun', 'matfun64', 'dense64', 'wide64' or 'rbf64'")
+        if method not in ("auto", "eig", "matfun", "matfun64", "dense64", "wide64", "rbf64", "kern64"):
+            raise ValueError("method must be 'auto', 'eig', 'matfun', 'matfun64', 'dense64', 'wide64', 'rbf64' or 'kern64'")
         # float64 RBF-kernelised filter on tiles (csrc/lketkf_tile64.hip): 2 <= k <= 40, lists of at most 64 observations, no weights
         can_rbf64 = dtype == torch.float64 and not return_weights and rbf_gamma is not None and kernel_program is None
         if method == "rbf64" and not can_rbf64:
             raise ValueError("the rbf64 route needs float64, rbf_gamma, no kernel_program and cannot return the weights")
+        # ... and the same kernel with K from a kernel expression (csrc/lketkf_kern64.hip): positive semidefinite kernels only
+        can_kern64 = (dtype == torch.float64 and not return_weights and kernel_program is not None and rbf_gamma is None
+                      and bool(kernel_psd))
+        if method == "kern64" and not can_kern64:
+            raise ValueError("the kern64 route needs float64, a kernel_program with kernel_psd=True and cannot return the weights")
         P = rec.shape[0]
         n = nbrs.g1 - nbrs.g0
         if out is None:
@@ -677,16 +718,35 @@ class LetkfEngine:
             prog = (_cabi.KernelOp * max(nops, 1))()
             for i, (op, val) in enumerate(kernel_program):
                 prog[i].op, prog[i].value = int(op), float(val)
-            fn = getattr(self.lib, "mia_lketkf_kernel_analysis_packed_" + sfx)
-            _cabi.check(fn(*args[:13], float(inf_factor), prog, nops, *args[15:], _ptr(W), _ptr(flags), self._stream()),
-                        "mia_lketkf_kernel_analysis_packed_" + sfx)
+            pargs = (*args[:13], float(inf_factor), prog, nops, *args[15:])
+            finish = None
+            if can_kern64 and n > 0 and (method == "kern64" or (method == "auto" and self._kern64_auto(m, k, nbrs.p_max))):
+                if retry is None:
+                    retry = torch.zeros(1, dtype=torch.int32, device=self.device)
+                rc = self.lib.mia_lketkf_kernel_analysis_matfun_f64(*pargs, _ptr(flags), _ptr(retry), self._stream())
+                if rc == -3 and method == "auto":      # shape outside the kernel, tanh / sin, tile = 0: the Jacobi kernel below
+                    pass
+                else:
+                    _cabi.check(rc, "mia_lketkf_kernel_analysis_matfun_f64")
+
+                    def finish(_alive=(X, rec, out, nbrs)):   # (pargs holds addresses: a deferred redo must find the arrays alive)
+                        n_retry = int(retry.item())          # host sync (8 bytes)
+                        if n_retry:
+                            _cabi.check(self.lib.mia_lketkf_kernel_analysis_retry_f64(*pargs, _ptr(flags), self._stream()),
+                                        "mia_lketkf_kernel_analysis_retry_f64")
+                        return n_retry
+            if finish is None:
+                fn = getattr(self.lib, "mia_lketkf_kernel_analysis_packed_" + sfx)
+                _cabi.check(fn(*pargs, _ptr(W), _ptr(flags), self._stream()), "mia_lketkf_kernel_analysis_packed_" + sfx)
+            elif not defer_retry:
+                finish()
             res = [out]
             if return_weights:
                 res.append(W)
             if return_flags:
                 res.append(flags)
             if defer_retry:
-                res.append(lambda: 0)
+                res.append(finish if finish is not None else (lambda: 0))
             return res[0] if len(res) == 1 else tuple(res)
         if (return_weights and dtype == torch.float32 and method != "eig" and n > 0):
             # weights without an eigensolver (dual route, order <= 32); -3 = shape outside that kernel

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from .engine import LetkfEngine, warn_if_noconv
-from .kernels import kernel_route
+from .kernels import kernel_is_psd, kernel_route
 from .localization import GaspariCohn
 
 logger = logging.getLogger(__name__)
@@ -96,7 +96,11 @@ class ETKF:
     def _kernel_args(self) -> dict:
         # (a per-observation lengthscale vector is meaningful for the global solve only: kernels.GaussKernel)
         gamma, prog = kernel_route(self._kernel, allow_feature_scale=not hasattr(self, "localization"))
-        return dict(rbf_gamma=gamma, kernel_program=prog)
+        if prog is None:
+            return dict(rbf_gamma=gamma, kernel_program=prog)
+        # (a kernel expression: whether it is positive semidefinite by construction decides between the float64 tile kernel and
+        #  the Jacobi kernel, LetkfEngine.analysis)
+        return dict(rbf_gamma=gamma, kernel_program=prog, kernel_psd=kernel_is_psd(self._kernel))
 
     def __str__(self):
         return "Global ETKF(inf_factor={0})".format(self.inf_factor)
@@ -357,7 +361,9 @@ class LETKF(ETKF):
         (float64, the default dtype: ``engine.analysis(method="auto")`` forms the tiles' unions itself from the per-point lists of
         any metric and runs letkf_tile64_kernel, or letkf_dense64_kernel where k < p_max <= 2.4 k, or letkf_wide64_kernel for 65 .. 128 members with p_max <= k; with an RBF / Gauss kernel
         it runs lketkf_tile64_kernel for RBF64_AUTO_MIN_K <= k <= 40 with one state row and p_max <= RBF64_AUTO_MAX_P, or up to
-        RBF64_AUTO_MAX_ROWS state rows and p_max <= RBF64_AUTO_MAX_P_ROWS; no explicit ``dtype=torch.float32`` is needed to reach a tile kernel)."""
+        RBF64_AUTO_MAX_ROWS state rows and p_max <= RBF64_AUTO_MAX_P_ROWS; with any other positive semidefinite kernel expression
+        (``kernels.kernel_is_psd``) it runs lketkf_tile64_kernel<UT, NR, ST> for KERN64_AUTO_MIN_K <= k <= 40 with one state row and
+        p_max <= KERN64_AUTO_MAX_P; no explicit ``dtype=torch.float32`` is needed to reach a tile kernel)."""
         eng = self.engine
         ka = self._kernel_args()
         gamma = ka.get("rbf_gamma")
@@ -457,8 +463,13 @@ class KETKF(ETKF):
 class LKETKF(LETKF):
     """Localised kernelised ETKF (interface/lketkf.py:37-115; estimate_weights is LETKF's, :77).  In the default dtype (float64)
     ``analyse_arrays`` with an RBFKernel / GaussKernel runs lketkf_tile64_kernel (csrc/lketkf_tile64.hip) from the per-point lists of
-    any localisation -- built-in metrics, PeriodicMetric, a host ``dist_func`` -- under ``LetkfEngine.RBF64_AUTO_*``; with a
-    ``weight_save_path``, for ``estimate_weights`` and for every other kernel the Jacobi kernel computes it, as before."""
+    any localisation -- built-in metrics, PeriodicMetric, a host ``dist_func`` -- under ``LetkfEngine.RBF64_AUTO_*``.  Every other
+    kernel or composition that is positive semidefinite by construction (``kernels.kernel_is_psd``: PolyKernel, RationalKernel,
+    OrnsteinUhlenbeckKernel, ScaleKernel, DiagKernel, their sums, products and integer powers) runs the same kernel with the pair
+    statistics its expression needs (csrc/lketkf_kern64.hip) under ``LetkfEngine.KERN64_AUTO_*`` (one state row, 20 <= k <= 40,
+    p_max <= 21).  With a ``weight_save_path``, for ``estimate_weights``, for TanhKernel, PeriodicKernel and whatever else is not
+    known to be positive semidefinite (the reference clamps negative eigenvalues; the eigensolver-free route cannot) the Jacobi
+    kernel computes it, as before."""
 
     def __init__(self, kernel, localization: Optional[GaspariCohn] = None, inf_factor: float = 1.0,
                  smoother: bool = False, gpu: bool = True, pre_transform=None, post_transform=None,

@@ -21,7 +21,7 @@ from typing import List, Optional, Tuple
 
 __all__ = ["BaseKernel", "AdditiveKernel", "MultiplicativeKernel", "PowerKernel", "LinearKernel", "GaussKernel",
            "RBFKernel", "PolyKernel", "TanhKernel", "PeriodicKernel", "RationalKernel",
-           "OrnsteinUhlenbeckKernel", "ScaleKernel", "DiagKernel", "kernel_route",
+           "OrnsteinUhlenbeckKernel", "ScaleKernel", "DiagKernel", "kernel_route", "kernel_is_psd",
            "KOP_DOT", "KOP_SQDIST", "KOP_L1DIST", "KOP_CONST", "KOP_DIAG", "KOP_ADD", "KOP_MUL", "KOP_POW",
            "KOP_EXP", "KOP_TANH", "KOP_SIN"]
 
@@ -69,6 +69,13 @@ class BaseKernel:
         """The kernel as [(opcode, value), ...] in reverse Polish form."""
         raise NotImplementedError
 
+    @property
+    def is_psd(self) -> bool:
+        """True where K(X, X) is positive semidefinite BY CONSTRUCTION for every sample set X -- what the eigensolver-free
+        float64 route needs (csrc/lketkf_tile64.hip: the reference clamps negative eigenvalues of the centred kernel matrix,
+        core/utils.py:58-59, and a polynomial in the matrix cannot).  Conservative: a kernel that does not say so is not."""
+        return False
+
 
 class CompKernel(BaseKernel):
     _op = None
@@ -95,21 +102,36 @@ class AdditiveKernel(CompKernel):
     """K1 + K2 (base_kernels.py:98-117)."""
     _op, _sym = KOP_ADD, "+"
 
+    @property
+    def is_psd(self) -> bool:          # (sums of positive semidefinite matrices)
+        return self.kernel_1.is_psd and self.kernel_2.is_psd
+
 
 class MultiplicativeKernel(CompKernel):
     """K1 * K2 (base_kernels.py:120-139)."""
     _op, _sym = KOP_MUL, "*"
+
+    @property
+    def is_psd(self) -> bool:          # (Schur product theorem)
+        return self.kernel_1.is_psd and self.kernel_2.is_psd
 
 
 class PowerKernel(CompKernel):
     """K1 ** K2 (base_kernels.py:142-161)."""
     _op, _sym = KOP_POW, "^"
 
+    @property
+    def is_psd(self) -> bool:          # (a positive integer power is a repeated Schur product; any other exponent is not known to be)
+        exp = self.kernel_2
+        return (self.kernel_1.is_psd and type(exp) is ScaleKernel and _f32(exp.scaling) >= 1.0
+                and _f32(exp.scaling) == int(_f32(exp.scaling)))
+
 
 class LinearKernel(BaseKernel):
     """K(x, y) = x y^T: the KETKF with this kernel is the ETKF (linear.py:41-67,
     tests/unit_tests/interface/test_lketkf.py:109-117) and is routed to the ETKF kernels."""
     gamma = None
+    is_psd = True                      # (a Gram matrix)
 
     def program(self) -> Program:
         return [(KOP_DOT, 0.0)]
@@ -142,6 +164,8 @@ class GaussKernel(BaseKernel):
     @property
     def gamma(self) -> float:
         return 0.5 / self.lengthscale ** 2
+
+    is_psd = True                      # (Gaussian: positive definite for every width)
 
     def program(self, allow_vector: bool = False) -> Program:
         if self.feature_scale is not None and not allow_vector:
@@ -182,6 +206,10 @@ class PolyKernel(BaseKernel):
     def __init__(self, degree: float = 2.0, const: float = 1.0):
         self.degree = _scalar(degree, "degree")
         self.const = _scalar(const, "const")
+
+    @property
+    def is_psd(self) -> bool:          # ((x.y + c)^p: Gram + constant >= 0, then a repeated Schur product)
+        return self.const >= 0.0 and self.degree >= 1.0 and self.degree == int(self.degree)
 
     def program(self) -> Program:
         return [(KOP_DOT, 0.0), (KOP_CONST, self.const), (KOP_ADD, 0.0), (KOP_CONST, self.degree), (KOP_POW, 0.0)]
@@ -237,6 +265,10 @@ class RationalKernel(BaseKernel):
         self.lengthscale = _scalar(lengthscale, "lengthscale")
         self.weighting = _scalar(weighting, "weighting")
 
+    @property
+    def is_psd(self) -> bool:          # (a scale mixture of Gaussians for every a > 0)
+        return self.weighting > 0.0
+
     def program(self) -> Program:
         return [(KOP_SQDIST, 0.0), (KOP_CONST, 1.0 / (2.0 * self.weighting * self.lengthscale ** 2)), (KOP_MUL, 0.0),
                 (KOP_CONST, 1.0), (KOP_ADD, 0.0), (KOP_CONST, -self.weighting), (KOP_POW, 0.0)]
@@ -254,6 +286,10 @@ class OrnsteinUhlenbeckKernel(BaseKernel):
     def __init__(self, lengthscale: float = 1.0):
         self.lengthscale = _scalar(lengthscale, "lengthscale")
 
+    @property
+    def is_psd(self) -> bool:          # (the Laplacian kernel: a product of one-dimensional exp(-|x - y| / l))
+        return self.lengthscale > 0.0
+
     def program(self) -> Program:
         return [(KOP_L1DIST, 0.0), (KOP_CONST, -1.0 / self.lengthscale), (KOP_MUL, 0.0), (KOP_EXP, 0.0)]
 
@@ -269,6 +305,10 @@ class ScaleKernel(BaseKernel):
 
     def __init__(self, scaling: float = 0.0):
         self.scaling = _scalar(scaling, "scaling")
+
+    @property
+    def is_psd(self) -> bool:          # (c 1 1^T)
+        return self.scaling >= 0.0
 
     def program(self) -> Program:
         return [(KOP_CONST, _f32(self.scaling))]
@@ -286,6 +326,10 @@ class DiagKernel(BaseKernel):
 
     def __init__(self, scaling: float = 0.0):
         self.scaling = _scalar(scaling, "scaling")
+
+    @property
+    def is_psd(self) -> bool:          # (c I)
+        return self.scaling >= 0.0
 
     def program(self) -> Program:
         return [(KOP_DIAG, _f32(self.scaling))]
@@ -330,3 +374,11 @@ def kernel_route(kernel, allow_feature_scale: bool = False) -> Tuple[Optional[fl
     prog = kernel.program()
     check_program(prog)
     return None, prog
+
+
+def kernel_is_psd(kernel) -> bool:
+    """Whether ``kernel`` is positive semidefinite by construction (``BaseKernel.is_psd``): the condition under which the
+    kernel-expression route may leave the Jacobi kernel for the eigensolver-free float64 tile kernel
+    (``LetkfEngine.analysis(kernel_psd=True)``).  TanhKernel, PeriodicKernel (as the reference defines it, on the 1-norm: C K C
+    has eigenvalues near -1 on the golden case) and anything that is no kernel of this module are not."""
+    return isinstance(kernel, BaseKernel) and bool(kernel.is_psd)
