@@ -670,6 +670,30 @@ int mia_lienks_update_f64(const double* W_in, int64_t w_stride, int k, int64_t g
                           const double* rec, int64_t P,
                           const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
                           double tau, double epsilon, double* W_out, int32_t* flags_opt, void* stream);
+/* tau = 1 in FLOAT64 without an eigensolver, on tiles of sixteen grid points (csrc/lienks_tile64.hip; replaces the two
+ * torch.svd of core/ienks.py:56-67 and 89-103 and the update of :108-126, per grid point under interface/lienks.py:75-118):
+ * Wp' = I + D phi(S) D^T, w_mean' = D psi(S) (d_l + D^T w_mean), S = D^T D -- the LETKF weights at inflation 1 with the
+ * innovations shifted by D^T w_mean -- on the frame of mia_letkf_weights_matfun_f64, every product a v_mfma_f64_16x16x4_f64.
+ * Bundle variant (epsilon > 0, D = Yl / eps, core/ienks.py:167-173): every iteration, the result depends on W_in through
+ * its row means alone.  Transform variant (epsilon <= 0, D = Wp^-1 Yl, core/ienks.py:69-75): only where
+ * max |W_in - w_mean 1^T - I| <= 1e-14 (the first iteration from the prior weights); any other point with observations is
+ * declined.  Argument list and validation order of mia_lienks_update_matfun_f32: sizes (w_stride 0 or k*k), empty shard ->
+ * MIA_OK, NULL pointers, then MIA_ERR_UNSUPPORTED for the option "tile" = 0 and outside 2 <= k <= 64, p_max <= k (nothing is
+ * dereferenced before that), and when the coefficient table cannot be had (stream being captured).  Declined points (another
+ * Wp, degree above the cap 127): MIA_FLAG_RETRY, counted in *retry_count (device int32, zeroed by the caller), untouched in
+ * W_out; a point without observations gets its W_in back bit for bit, flag 0 (ienks.py:135); the Chebyshev degree of a
+ * written point is in bits 8-15 of its flag.
+ * mia_lienks_update_retry_f64: the general kernel (mia_lienks_update_f64) restricted to the flagged points.
+ * mia_lienks_update_f64_cover: 1 when the shape is inside the route, 0 when not (host only, no device work). */
+int mia_lienks_update_matfun_f64(const double* W_in, int64_t w_stride, int k, int64_t g0, int64_t g1,
+                                 const double* rec, int64_t P,
+                                 const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                                 double epsilon, double* W_out, int32_t* flags, int32_t* retry_count, void* stream);
+int mia_lienks_update_retry_f64(const double* W_in, int64_t w_stride, int k, int64_t g0, int64_t g1,
+                                const double* rec, int64_t P,
+                                const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                                double tau, double epsilon, double* W_out, int32_t* flags, void* stream);
+int mia_lienks_update_f64_cover(int k, int p_max, int64_t n_points, int64_t P);
 
 /* ------------------------------------------------------------------------------------
  * Observation-space preparation, the step immediately upstream of the analysis

@@ -1,0 +1,549 @@
+// The localised IEnKS weight update with tau = 1 in FLOAT64, sixteen grid points per wavefront, every contraction on the matrix
+// cores (v_mfma_f64_16x16x4_f64), without an eigensolver: what IEnKSTransformModule / IEnKSBundleModule.forward
+// (core/ienks.py:108-141, 167-173) return on the localised block under LocalizedIEnKS*.inner_loop (interface/lienks.py:75-118)
+// in the reference's default working precision.  With tau = 1, reg = k - 1, D = Yl (transform variant, while Wp = I) or
+// D = Yl / eps (bundle variant) and S = D^T D:
+//
+//     Wp'     = sqrt(k-1) Pn^-1/2                       = I + D phi(S) D^T
+//     w_mean' = w_mean - Pn^-1 ((k-1) w_mean - D d_l)   = D psi(S) (d_l + D^T w_mean)
+//     W'      = w_mean' 1^T + Wp'
+//
+// i.e. the LETKF weights at inflation 1 with the innovations shifted by D^T w_mean (the float32 twin: letkf_cheb.hip:913-948).
+//
+// The frame is letkf_tile64w.hip's, statement for statement: per-point lists of any metric, union by rank extraction, record
+// image in LDS, G = Yw Yw^T, D^2, Gershgorin bound, table row -> alpha, degree and decline of every point, one pass of the
+// recurrence per MEMBER c < k on column c of the record image, row c of sixteen points' weights per pass.  (A copy, not a
+// template switch: the weights kernel's code objects stay what they were.)  Lane roles, canonical summation order and the
+// instruction discipline (every product step unconditional, no branch between a matrix instruction and the first vector read
+// of its result; builtins only) are described in letkf_tile64.hip.
+//
+// What differs from letkf_weights64_kernel:
+//
+//     w_mean_i = (sum_j W_in[i][j] - 1) / k    per point (or once, for ONE shared matrix: w_stride = 0).  Sixteen lanes share a
+//                                     row: lane lr adds columns lr, lr + 16, ... in that order, then a butterfly over the
+//                                     sixteen -- an order that depends on (i, j) alone, not on the point's place in its tile
+//     z[b][pt] = sum_i Yw[b][i] w_mean[pt][i]  the shift, slots x points in the result layout: one more accumulator chain beside
+//                                     G in the Gram loop (same A operands, w_mean as the B operand), unconditional
+//     e[b][pt] = (d_b s + z[b][pt]) D^2[b][pt] s = 1 (transform) or eps (bundle: only Yl is divided by eps, core/ienks.py:167-173).
+//                                     Kept in LDS, in the rows of Dl, which are dead once sqrt(rho) sits in registers: the lane
+//                                     that read Dl[pt][b] is the lane that writes and later reads e there, so no barrier and
+//                                     not one register more than the weights kernel in the member loop
+//     wm_c     = sum_b e_b psi_b      per point: the innovation differs per point, so it sits in the B operand and the A
+//                                     operand is all ones (every row of the result block is the sum, in the canonical order)
+//     sqrt(rho) enters Dl as sqrt(rho) / eps (bundle): bound, table row and degree are those of the scaled S
+//     W'[g][c][j] = wm_c + [c == j] + (Yw^T (D^2 o Phi))_j
+//
+// A point without observations gets its W_in back bit for bit, flag 0 (core/ienks.py:135), and takes no part in the tile.
+// Transform variant: a point whose Wp is not the identity (kPriorTol below) is declined like a point whose degree exceeds the
+// table's cap: MIA_FLAG_RETRY, counted, W_out untouched; the general kernel redoes them (mia_lienks_update_retry_f64).  A tile
+// that holds a non-finite record is done point by point, so that MIA_FLAG_NONFINITE stays with the points that use the record.
+#include "mia_cheb_table64.h"
+
+namespace mia {
+
+// A point of the transform variant is "at the prior" when max_ij |W_in[i][j] - w_mean_i - [i == j]| <= kPriorTol.  Only there
+// D = Wp^-1 Yl equals Yl.  An accepted deviation delta of Wp from I perturbs Wp^-1, and with it D, by at most k delta relative
+// (||Wp - I||_2 <= k max_ij |.|): 64 * 1e-14 = 6.4e-13 at the largest k of the route, two orders below the 1e-10 contract of
+// the float64 tile kernels.  Forming I + w_mean 1^T in float64 and taking the row means again leaves residues of
+// about 1e-16 (a few ulp of numbers near 1), two orders below the threshold: the prior and what update_state builds from it pass.
+constexpr double kPriorTol = 1e-14;
+
+struct Lienks64Params {
+  int k; int kp;
+  int64_t ng;
+  const double* Win; int64_t w_stride;     // [ng][k][k], or one [k][k] for all points when w_stride == 0
+  const double* rec;
+  const int32_t* cnt; const int32_t* idx; const double* w; int p_cap; int p_max;
+  int transform;                           // 1: transform variant (D = Yl while Wp = I), 0: bundle variant (D = Yl / eps)
+  double dscale, dshift;                   // 1 / eps and eps (bundle), 1 and 1 (transform)
+  double reg, inv_reg, f0, cs_phi, cs_psi;
+  double* W; int32_t* flags; int32_t* retry_count;
+  int dmax;
+  const Tab64Hdr* tab_hdr; const double2* tab_c;
+};
+
+// Row means of one point's incoming weights, w_mean_i = (sum_j W[i][j] - 1) / k (_split_weights, core/ienks.py:46-54), for
+// rows i = 4 iq + h: the sixteen lanes (lr) of lane group h share row i and all end up with its mean.  take: this lane keeps
+// the means in wmv (rows beyond k give 0).  dev: running maximum of |W[i][j] - w_mean_i - [i == j]| over the elements this
+// lane has seen (NaN where an element is not a number).
+template <int KT>
+__device__ __forceinline__ void lienks64_row_means(const double* win, int k, int lr, int h, bool take, double (&wmv)[4 * KT],
+                                                   double& dev) {
+  // (lane roles through opaque copies, as in the kernel's loops: the per-row predicates and offsets are invariant in the
+  //  caller's loop over points and would otherwise be hoisted in front of it, a hundred scalar registers at KT = 4)
+  asm volatile("" : "+v"(lr), "+v"(h));
+#pragma unroll
+  for (int iq = 0; iq < 4 * KT; ++iq) {
+    const int i = 4 * iq + h;
+    const bool rok = i < k;
+    const double* row = win + (rok ? i : 0) * k;
+    double wv[KT];
+    double s = 0.0;
+#pragma unroll
+    for (int jj = 0; jj < KT; ++jj) {
+      const int j = lr + 16 * jj;
+      const double v = row[j < k ? j : 0];
+      wv[jj] = v;
+      s += (rok && j < k) ? v : 0.0;
+    }
+    s += __shfl_xor(s, 1, 64);
+    s += __shfl_xor(s, 2, 64);
+    s += __shfl_xor(s, 4, 64);
+    s += __shfl_xor(s, 8, 64);
+    const double wm = (s - 1.0) / double(k);
+#pragma unroll
+    for (int jj = 0; jj < KT; ++jj) {
+      const int j = lr + 16 * jj;
+      const double e = fabs(wv[jj] - wm - (i == j ? 1.0 : 0.0));
+      if (rok && j < k) dev = (e > dev || e != e) ? e : dev;
+    }
+    wmv[iq] = take ? (rok ? wm : 0.0) : wmv[iq];
+  }
+}
+
+// UT: 16-slot blocks of the union the wavefront holds (G is UT x UT result blocks of 8 registers); KT = ceil(k / 16).
+// Instantiations and launch bounds are letkf_weights64_kernel's.
+template <int UT, int KT>
+__global__ __launch_bounds__(64, (UT <= 2 ? 2 : 1)) void lienks_update64_kernel(Lienks64Params P) {
+  constexpr int UMAX = 16 * UT, NU = 4 * UT, DS = UMAX + 1;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int lane = threadIdx.x;
+  const int k = P.k, kp = P.kp, pm = P.p_max;
+  const int KS = kp | 1;                                     // odd row pitch (in doubles) of the record image
+  double* Yw = reinterpret_cast<double*>(smem_raw);          // [UMAX][KS] union records, zero rows beyond the union
+  double* Dl = Yw + UMAX * KS;                               // [16][DS]   sqrt(rho) [/ eps] of (point, slot), 0 = not local; later e
+  int* ukey = reinterpret_cast<int*>(Dl + 16 * DS);          // [UMAX]     observation index of a slot, -1 = unused
+
+  // XCD-aware block -> tile map: blocks b, b + 8, ... share an XCD (and its L2) and take consecutive tiles, whose
+  // records overlap
+  const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+  const int64_t ntile = (P.ng + 15) >> 4;
+  if (bid >= ntile) return;
+  const int64_t q8 = ntile >> 3, r8 = ntile & 7, xcd = bid & 7;
+  const int64_t tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int64_t p0 = tile << 4;                              // first point of the tile (index into the launch's ng points)
+  const int npts = P.ng - p0 < 16 ? (int)(P.ng - p0) : 16;
+  const int lr = lane & 15, h = lane >> 4, lp = lane >> 2, sub = lane & 3;
+  const unsigned kk8 = (unsigned)(k * k) * 8u;               // bytes of one point's weights
+  const bool shared_w = P.w_stride == 0;
+
+  // ---- the tile's neighbour lists: lane (lp, sub) holds entries sub, sub + 4, ... of point lp (unconditional loads inside
+  //      the row's storage; entries beyond the count become index -1: the one validity test of everything that follows)
+  const int nl = pm < P.p_cap ? pm : P.p_cap;
+  int eidx[NU];
+  double ew[NU];
+  int lcnt;
+  unsigned long long skipmask;       // bit 4 p: point p takes no part in the tile (overflow, no observation, declined here)
+  {
+    const int64_t row = p0 + (lp < npts ? lp : 0);          // (lists, flags and weights count from the shard's g0)
+    lcnt = P.cnt[row];
+    const int32_t* ib = P.idx + row * P.p_cap;
+    const double* wb = P.w + row * P.p_cap;
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+      const int pos = sub + 4 * u;
+      const int e = pos < nl ? pos : 0;
+      eidx[u] = ib[e];
+      ew[u] = wb[e];
+    }
+    const bool pbad = lp < npts && (lcnt > pm || lcnt > P.p_cap || lcnt > UMAX);   // loud failure, never truncate
+    if (pbad) {
+      if (sub == 0) P.flags[p0 + lp] = MIA_FLAG_OVERFLOW;
+      const double nanv = __builtin_nan("");
+      double* wp = P.W + (p0 + lp) * (int64_t)(k * k);
+      for (int it = sub; it < k * k; it += 4) wp[it] = nanv;
+    }
+    if (lp >= npts || pbad) lcnt = 0;
+    // ---- no local observation: the weights go back as they came (core/ienks.py:135), the whole wavefront copying a point
+    const unsigned long long emask = __ballot(lp < npts && !pbad && lcnt == 0);
+    skipmask = __ballot(pbad) | emask;
+    for (int pt = 0; pt < npts; ++pt) {
+      if (!((emask >> (4 * pt)) & 1ull)) continue;
+      const double* win = P.Win + (p0 + pt) * P.w_stride;
+      double* wout = P.W + (p0 + pt) * (int64_t)(k * k);
+      for (int it = lane; it < k * k; it += 64) wout[it] = win[it];
+      if (lane == 0) P.flags[p0 + pt] = 0;
+    }
+    // ---- transform variant: D = Wp^-1 Yl is Yl only at the prior; any other point with observations is the general kernel's
+    if (P.transform) {
+      unsigned np = 0u;                                      // bit p: point p is not at the prior
+      const int nscan = shared_w ? 1 : npts;
+      for (int pt = 0; pt < nscan; ++pt) {
+        if (!shared_w && ((skipmask >> (4 * pt)) & 1ull)) continue;
+        double wtmp[4 * KT], dev = 0.0;
+#pragma unroll
+        for (int iq = 0; iq < 4 * KT; ++iq) wtmp[iq] = 0.0;
+        lienks64_row_means<KT>(P.Win + (p0 + pt) * P.w_stride, k, lr, h, false, wtmp, dev);
+        if (__any(!(dev <= kPriorTol))) np |= shared_w ? 0xffffu : (1u << pt);
+      }
+      const bool pnot = lp < npts && lcnt > 0 && ((np >> lp) & 1u);
+      if (pnot && sub == 0) {
+        P.flags[p0 + lp] = MIA_FLAG_RETRY;
+        atomicAdd(P.retry_count, 1);
+      }
+      if (pnot) lcnt = 0;
+      skipmask |= __ballot(pnot);
+    }
+    if (!__any(lcnt > 0)) return;                            // nothing left to update in this tile
+#pragma unroll
+    for (int u = 0; u < NU; ++u)
+      if (sub + 4 * u >= lcnt) eidx[u] = -1;
+  }
+
+  int lo = 0;
+#pragma clang loop unroll(disable)
+  while (lo < npts) {
+    // The loop body runs once per tile unless the tile had to be split.  The lane id goes through an opaque copy, so that
+    // the compiler does not hoist dozens of address / predicate registers out of a loop that does not loop.
+    int lanev = lane;
+    asm volatile("" : "+v"(lanev));
+    const int lr = lanev & 15, h = lanev >> 4, lp = lanev >> 2;
+    const bool colok = lr < npts && !((skipmask >> (4 * lr)) & 1ull);
+    // ---- union of the lists of points [lo, hi): slot = RANK of the observation index, found by repeated extraction of
+    //      the smallest remaining key (one DPP reduction per slot); shrink the range until the union fits
+    int n = 16, hi, U;
+    int es[NU];            // slot of this lane's entries
+    for (;;) {
+      hi = lo + n < npts ? lo + n : npts;
+      const bool act = lp >= lo && lp < hi;
+      unsigned key1[NU];   // index + 1 of an entry that takes part, 0 otherwise
+#pragma unroll
+      for (int u = 0; u < NU; ++u) {
+        es[u] = -1;
+        key1[u] = (act && eidx[u] >= 0) ? (unsigned)eidx[u] + 1u : 0u;
+      }
+      for (int i = lane; i < UMAX; i += 64) ukey[i] = -1;
+      __syncthreads();
+      U = 0;
+      unsigned last = 0u;
+#pragma clang loop unroll(disable)
+      for (;;) {
+        unsigned best = 0u;                       // ~(smallest key above `last`), 0 = none left
+#pragma unroll
+        for (int u = 0; u < NU; ++u) {
+          const unsigned cand = key1[u] > last ? ~key1[u] : 0u;
+          best = cand > best ? cand : best;
+        }
+        best = tile64_wave_max_u32(best);
+        if (best == 0u) break;
+        last = ~best;
+        if (U < UMAX) {
+#pragma unroll
+          for (int u = 0; u < NU; ++u)
+            if (key1[u] == last) es[u] = U;
+          if (lane == 0) ukey[U] = (int)(last - 1u);
+        }
+        ++U;
+        if (U > UMAX) break;
+      }
+      if (U > UMAX) { __syncthreads(); n >>= 1; continue; }     // (n = 1 always fits: a single list has at most UMAX entries)
+      __syncthreads();
+      // ---- the union's records, four rows per trip: lane group h takes row r0 + h, its sixteen lanes the columns
+      double fin = 0.0;       // stays 0 while every value is finite (inf * 0 = NaN)
+#pragma clang loop unroll_count(2)
+      for (int r0 = 0; r0 < UMAX; r0 += 4) {
+        const int r = r0 + h;
+        const int key = ukey[r];
+        const double* src = P.rec + (int64_t)(key < 0 ? 0 : key) * kp;
+        for (int c = lr; c < kp; c += 16) {
+          double v = 0.0;
+          if (key >= 0) v = src[c];
+          fin = fma(v, 0.0, fin);
+          Yw[r * KS + c] = v;
+        }
+      }
+      // A non-finite record would reach EVERY column of the tile through the shared Gram matrix (NaN * 0 = NaN), also the
+      // points that do not see that observation.  Such a tile is done point by point: the union is then the point's
+      // own list and the damage stays where the reference has it.
+      if (__any(fin != fin) && hi - lo > 1) { __syncthreads(); n = 1; continue; }
+      break;
+    }
+    for (int i = lane; i < 16 * DS; i += 64) Dl[i] = 0.0;
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < NU; ++u)
+      if (es[u] >= 0) Dl[lp * DS + es[u]] = ew[u] * P.dscale;
+    __syncthreads();
+    const bool colact = colok && lr >= lo && lr < hi;
+    // ---- w_mean of the points of this pass: wmv[4 tm + q] = w_mean[point lr][member 16 tm + 4 q + h], the B operand of the
+    //      shift (0 for points that take no part).  Closed before the first matrix instruction of the pass.
+    double wmv[4 * KT];
+#pragma unroll
+    for (int iq = 0; iq < 4 * KT; ++iq) wmv[iq] = 0.0;
+    {
+      const int nscan = shared_w ? 1 : hi;
+      for (int pt = shared_w ? 0 : lo; pt < nscan; ++pt) {
+        if (!shared_w && ((skipmask >> (4 * pt)) & 1ull)) continue;
+        double dev = 0.0;
+        lienks64_row_means<KT>(P.Win + (p0 + pt) * P.w_stride, k, lr, h, shared_w || lr == pt, wmv, dev);
+      }
+    }
+    d4t d2[UT];             // D^2 of column lr, slots 16 t + h + 4 r
+    // ---- G = Yw Yw^T: G[t1][t2][r] = Gram[16 t1 + h + 4 r][16 t2 + lr]; beside it the shift z = Yw w_mean,
+    //      zs[t][r] = z[16 t + h + 4 r][point lr], on the same A operands
+    d4t G[UT][UT], zs[UT];
+#pragma unroll
+    for (int t1 = 0; t1 < UT; ++t1) {
+      zs[t1] = d4t{0., 0., 0., 0.};
+#pragma unroll
+      for (int t2 = 0; t2 < UT; ++t2) G[t1][t2] = d4t{0., 0., 0., 0.};
+    }
+#pragma unroll
+    for (int tm = 0; tm < KT; ++tm)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int mem = 16 * tm + 4 * q + h;
+        const bool ok = tm < KT - 1 || mem < k;            // (innovation / pad columns are not members; only the last block is ragged)
+        const int col = ok ? mem : 0;
+        double av[UT];
+#pragma unroll
+        for (int t = 0; t < UT; ++t) {
+          const double v = Yw[(16 * t + lr) * KS + col];
+          av[t] = ok ? v : 0.0;
+        }
+        const double wb = ok ? wmv[4 * tm + q] : 0.0;
+#pragma unroll
+        for (int t2 = 0; t2 < UT; ++t2)
+#pragma unroll
+          for (int t1 = 0; t1 < UT; ++t1) G[t1][t2] = MIA_MFMA64(av[t1], av[t2], G[t1][t2]);
+#pragma unroll
+        for (int t = 0; t < UT; ++t) zs[t] = MIA_MFMA64(av[t], wb, zs[t]);
+      }
+    // the shifted innovation of (slot, point), d_b s + z: read off the accumulators before any branch
+    d4t ev[UT];
+#pragma unroll
+    for (int t = 0; t < UT; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) ev[t][r] = Yw[(16 * t + h + 4 * r) * KS + k] * P.dshift + zs[t][r];
+    // ---- Gershgorin bound of every point: L_g = max_a w_a sum_b |G_ab| w_b, then degree / interval from the table
+    double alpha;
+    int deg, tab_idx, pflag = 0;
+    bool decl;
+    {
+      d4t dreg[UT], R[UT];
+#pragma unroll
+      for (int t = 0; t < UT; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) dreg[t][r] = Dl[lr * DS + 16 * t + h + 4 * r];
+        R[t] = d4t{0., 0., 0., 0.};
+      }
+#pragma unroll
+      for (int tk = 0; tk < UT; ++tk)
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+          for (int t = 0; t < UT; ++t) R[t] = MIA_MFMA64(fabs(G[tk][t][q]), dreg[tk][q], R[t]);
+      double L = 0.0;
+#pragma unroll
+      for (int t = 0; t < UT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const double v = dreg[t][r] * R[t][r];
+          L = (v > L || v != v) ? v : L;
+          d2[t][r] = dreg[t][r] * dreg[t][r];
+          // e = (d s + z) D^2 over sqrt(rho) in LDS: this lane alone reads and writes the element
+          Dl[lr * DS + 16 * t + h + 4 * r] = ev[t][r] * d2[t][r];
+        }
+      L = tile64_max_h(L);
+      L = fmax(L, 1e-300 * P.reg) * (1.0 + 1e-12);
+      if (!(L == L) || !(fabs(L) < 1e300)) { pflag |= MIA_FLAG_NONFINITE; L = P.reg; }
+      tab_idx = (int)ceil(double(kTabPerOctave) * log2(L * P.inv_reg)) + kTabIdx0;
+      tab_idx = tab_idx < 0 ? 0 : (tab_idx > kTabN - 1 ? kTabN - 1 : tab_idx);      // (the last entries decline: T = 2^8)
+      const Tab64Hdr hd = P.tab_hdr[tab_idx];
+      deg = hd.deg;
+      decl = colact && (deg > P.dmax || deg > kTab64Deg - 1);
+      alpha = (deg > kTab64Deg - 1) ? 0.0 : hd.two_over_T * P.inv_reg;             // (a declined column carries bounded junk)
+      if (decl && h == 0) {
+        P.flags[p0 + lr] = MIA_FLAG_RETRY;
+        atomicAdd(P.retry_count, 1);
+      }
+    }
+    const int degmax = (int)tile64_wave_max_u32((colact && !decl) ? (unsigned)deg : 0u);
+    const double2* ctab = P.tab_c + (size_t)tab_idx * kTab64Deg;
+    auto coef = [&](int j) -> double2 {                              // (zero beyond a point's own degree)
+      const double2 c = ctab[j < kTab64Deg ? j : kTab64Deg - 1];
+      return double2{c.x * P.cs_phi, c.y * P.cs_psi};
+    };
+
+    for (int c = 0; c < k; ++c) {
+      // (lane roles through opaque copies once more: what is invariant in this loop -- addresses, predicates -- would
+      //  otherwise be hoisted in front of it and spilled there)
+      int hv = h, lrv = lr;
+      asm volatile("" : "+v"(hv), "+v"(lrv));
+      // ---- Z = Yw e_c: column c of the record image, in the result layout as it lies
+      d4t va[UT], vb[UT], aphi[UT], apsi[UT], y[UT];
+#pragma unroll
+      for (int t = 0; t < UT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) va[t][r] = Yw[(16 * t + hv + 4 * r) * KS + c];
+      // ---- the recurrence on the 16 columns at once; vectors stay in the result layout.  v_0 = Z,
+      //      v_{j+1} = 2 (alpha G (D^2 o v_j) - v_j) - v_{j-1}; D enters as D^2 in the products' right-hand side and once at
+      //      the end; slots that are not local to a column (D = 0) carry bounded junk that D^2 = 0 keeps out of every product
+      auto product = [&](const d4t (&tv)[UT]) {
+#pragma unroll
+        for (int t = 0; t < UT; ++t) y[t] = d4t{0., 0., 0., 0.};
+#pragma unroll
+        for (int tk = 0; tk < UT; ++tk)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const double b = d2[tk][q] * tv[tk][q];
+#pragma unroll
+            for (int t = 0; t < UT; ++t) y[t] = MIA_MFMA64(G[tk][t][q], b, y[t]);
+          }
+      };
+      // vnew = 2 (alpha y - vcur) - vold, written over vold; the two weight functions accumulate c_j vnew
+      auto advance = [&](d4t (&vold)[UT], const d4t (&vcur)[UT], const double2 cj) {
+        product(vcur);
+#pragma unroll
+        for (int t = 0; t < UT; ++t) {
+          vold[t] = 2.0 * (alpha * y[t] - vcur[t]) - vold[t];
+          aphi[t] = cj.x * vold[t] + aphi[t];
+          apsi[t] = cj.y * vold[t] + apsi[t];
+        }
+      };
+      {
+        const double2 c0 = coef(0), c1 = coef(1);
+        product(va);
+#pragma unroll
+        for (int t = 0; t < UT; ++t) {
+          vb[t] = alpha * y[t] - va[t];
+          aphi[t] = c0.x * va[t] + c1.x * vb[t];
+          apsi[t] = c0.y * va[t] + c1.y * vb[t];
+        }
+      }
+      int j = 2;
+      double2 cj = coef(2), cj1 = coef(3);
+#pragma clang loop unroll(disable)
+      for (; j + 1 <= degmax; j += 2) {
+        const double2 nj = coef(j + 2), nj1 = coef(j + 3);       // requested one trip ahead
+        advance(va, vb, cj);          // va = v_j
+        advance(vb, va, cj1);         // vb = v_{j+1}
+        cj = nj; cj1 = nj1;
+      }
+      if (j <= degmax) advance(va, vb, cj);
+      // ---- wm_c = sum_b e_b psi_b: one more product, e o Psi of the sixteen points in the B operand under a block of ones --
+      //      on the matrix cores like everything else, because their enumeration IS the canonical summation order.  Every row
+      //      of the result block is the sum: register 0 of lane (lrv, hv) is that of point lrv.
+      d4t zacc = {0., 0., 0., 0.};
+#pragma unroll
+      for (int tk = 0; tk < UT; ++tk)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const double e = Dl[lrv * DS + 16 * tk + hv + 4 * q];
+          zacc = MIA_MFMA64(1.0, e * apsi[tk][q], zacc);
+        }
+      const double wm = zacc[0];
+#pragma unroll
+      for (int t = 0; t < UT; ++t) aphi[t] *= d2[t];          // D o phi(S) z = D^2 o (accumulated v): right-hand side of the last product
+      // row c of the sixteen points' weights: wave-uniform 64-bit base (tile, row c) + 32-bit lane offset (point lrv, column j)
+      char* obase = reinterpret_cast<char*>(P.W + (p0 * k + c) * (int64_t)k);
+      const unsigned olane = (unsigned)lrv * kk8 + (unsigned)hv * 8u;
+      const bool wr = colact && !decl;
+#pragma unroll
+      for (int tj = 0; tj < KT; ++tj) {
+        d4t acc = {0., 0., 0., 0.};
+        const int mcol = 16 * tj + lrv < k ? 16 * tj + lrv : k - 1;      // the output column this lane supplies to the A operand
+#pragma unroll
+        for (int tk = 0; tk < UT; ++tk)
+#pragma unroll
+          for (int q = 0; q < 4; ++q) acc = MIA_MFMA64(Yw[(16 * tk + 4 * q + hv) * KS + mcol], aphi[tk][q], acc);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int mem = 16 * tj + hv + 4 * r;
+          const double o = acc[r] + (wm + (mem == c ? P.f0 : 0.0));
+          if (!(fabs(o) <= 1e300) && mem < k) pflag |= MIA_FLAG_NONFINITE;
+          if (wr && mem < k) *reinterpret_cast<double*>(obase + (olane + (unsigned)(16 * tj + 4 * r) * 8u)) = o;
+        }
+      }
+    }
+    {
+      if (!(colact && !decl)) pflag = 0;          // (columns that are not written do not report)
+      const unsigned long long fb = __ballot(pflag != 0);
+      const bool anyf = ((fb >> lr) & 0x0001000100010001ull) != 0ull;
+      if (h == 0 && colact && !decl) P.flags[p0 + lr] = (anyf ? MIA_FLAG_NONFINITE : 0) | (deg << 8);
+    }
+    lo = hi;
+    __syncthreads();
+  }
+}
+
+static size_t lienks64_lds_bytes(int ut, int kp) {
+  const int umax = 16 * ut;
+  return align_up(((size_t)umax * (kp | 1) + 16 * (size_t)(umax + 1)) * sizeof(double) + (size_t)umax * sizeof(int), 16);
+}
+
+template <int UT, int KT>
+static int lienks64_launch_t(const Lienks64Params& tp, hipStream_t stream) {
+  const size_t lds = lienks64_lds_bytes(UT, tp.kp);
+  if (lds > kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
+  auto kern = lienks_update64_kernel<UT, KT>;
+  if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const int64_t ntile = (tp.ng + 15) >> 4;
+  const int64_t gx = ntile < 65536 ? ntile : 65536;
+  const int64_t gy = (ntile + gx - 1) / gx;
+  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
+  kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(64), lds, stream>>>(tp);
+  note_analysis_kernel("lienks_update64_kernel<%d, %d>", UT, KT);
+  MIA_LAUNCH_CHECK();
+  return MIA_OK;
+}
+
+template <int UT>
+static int lienks64_launch_u(const Lienks64Params& tp, int kt, hipStream_t stream) {
+  switch (kt) {
+    case 1: return lienks64_launch_t<UT, 1>(tp, stream);
+    case 2: return lienks64_launch_t<UT, 2>(tp, stream);
+    case 3: return lienks64_launch_t<UT, 3>(tp, stream);
+    case 4: return lienks64_launch_t<UT, 4>(tp, stream);
+  }
+  return MIA_ERR_UNSUPPORTED;
+}
+
+// slots of an instantiation: the analysis kernel's rule (letkf_tile64.hip, tile64_ut)
+static int lienks64_ut(int p_max) {
+  const int ut = (p_max + 8 + 15) >> 4;
+  return ut < 1 ? 1 : (ut > 4 ? 4 : ut);
+}
+
+bool lienks64_route_covers(int k, int p_max, int64_t ng) {
+  if (k < 2 || k > 64 || p_max < 0 || p_max > k || ng < 0) return false;
+  if (lienks64_lds_bytes(lienks64_ut(p_max), (k + 1 + 3) & ~3) > kMaxDynamicLds) return false;
+  return ((ng + 15) >> 4) <= (int64_t)65536 * 65535;
+}
+
+int lienks64_launch(const double* W_in, int64_t w_stride, int k, int64_t ng, const double* rec, const int32_t* nbr_cnt,
+                    const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max, double epsilon, double* W_out,
+                    int32_t* flags, int32_t* retry_count, hipStream_t stream) {
+  if (!option(MIA_OPT_TILE) || !W_in || !W_out || !flags || !retry_count) return MIA_ERR_UNSUPPORTED;
+  if (w_stride != 0 && w_stride != (int64_t)k * k) return MIA_ERR_UNSUPPORTED;
+  if (!lienks64_route_covers(k, p_max, ng)) return MIA_ERR_UNSUPPORTED;
+  const CoefTable64* tab = cheb_coef_table64(stream, kTab64Dual);
+  if (!tab) return MIA_ERR_UNSUPPORTED;
+  Lienks64Params tp;
+  tp.k = k; tp.kp = (k + 1 + 3) & ~3;
+  tp.ng = ng; tp.Win = W_in; tp.w_stride = w_stride; tp.rec = rec;
+  tp.cnt = nbr_cnt; tp.idx = nbr_idx; tp.w = nbr_w; tp.p_cap = p_cap; tp.p_max = p_max;
+  tp.transform = epsilon > 0.0 ? 0 : 1;
+  tp.dscale = epsilon > 0.0 ? 1.0 / epsilon : 1.0;
+  tp.dshift = epsilon > 0.0 ? epsilon : 1.0;
+  // the constants of weights64_launch at inf_factor = 1: reg = k - 1, f0 = 1
+  const double rg = (double)(k - 1), km = (double)(k - 1);
+  tp.reg = rg;
+  tp.inv_reg = 1.0 / rg;
+  tp.f0 = sqrt(km / rg);
+  tp.cs_phi = sqrt(km) / (rg * sqrt(rg));
+  tp.cs_psi = 1.0 / rg;
+  tp.W = W_out; tp.flags = flags; tp.retry_count = retry_count;
+  tp.dmax = kTab64Deg - 1;
+  tp.tab_hdr = tab->hdr; tp.tab_c = tab->c;
+  const int kt = (k + 15) >> 4;
+  switch (lienks64_ut(p_max)) {
+    case 1: return lienks64_launch_u<1>(tp, kt, stream);
+    case 2: return lienks64_launch_u<2>(tp, kt, stream);
+    case 3: return lienks64_launch_u<3>(tp, kt, stream);
+    case 4: return lienks64_launch_u<4>(tp, kt, stream);
+  }
+  return MIA_ERR_UNSUPPORTED;
+}
+
+}  // namespace mia

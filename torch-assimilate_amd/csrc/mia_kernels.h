@@ -88,6 +88,16 @@ int weights64_launch(int k, int64_t ng, const double* rec, const int32_t* nbr_cn
                      const double* nbr_w, int p_cap, int p_max, double inf_factor, double* W, int32_t* flags,
                      int32_t* retry_count, hipStream_t stream);
 
+// lienks_tile64.hip: the float64 localised IEnKS weight update with tau = 1 on the same frame (core/ienks.py:108-141 without an
+// eigensolver): the weights at inflation 1 with the innovations shifted by D^T w_mean; epsilon > 0 = bundle variant, else the
+// transform variant, which declines every point whose Wp is not the identity.  lienks64_route_covers: shape test (host only;
+// weights64_route_covers' bounds); lienks64_launch: MIA_ERR_UNSUPPORTED outside it, with the option tile = 0, and when the
+// float64 coefficient table cannot be had.
+bool lienks64_route_covers(int k, int p_max, int64_t ng);
+int lienks64_launch(const double* W_in, int64_t w_stride, int k, int64_t ng, const double* rec, const int32_t* nbr_cnt,
+                    const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max, double epsilon, double* W_out,
+                    int32_t* flags, int32_t* retry_count, hipStream_t stream);
+
 // letkf_dense64.hip: the float64 analysis on tiles for dense local networks (primal form, 2 <= k <= 64, k < p_max <= the
 // slots of the LDS record image, any number of state rows): the union streams through the wave block by block, C_g is never
 // formed.  dense64_route_covers: shape test (host only; false for p_max <= k, which is letkf_tile64.hip's);

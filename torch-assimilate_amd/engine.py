@@ -924,14 +924,35 @@ class LetkfEngine:
         return res[0] if len(res) == 1 else tuple(res)
 
     # ------------------------------------------------------------------- IEnKS
+    # ienks_update(method="auto") hands float64 updates with tau = 1 to the tile kernel (csrc/lienks_tile64.hip) only from this
+    # ensemble size on: the project's rule for WEIGHTS64_AUTO_MIN_K -- the smallest measured k at which the route, counter read
+    # included, is at least 2x the general kernel (ienks_update_kernel<double, 256>) in BOTH variants.  Measured on MI355X
+    # (tools/time_ienks64.py, profiles/ienks64_time.json), 1e5 points, bundle (per-point weights) / transform (shared prior):
+    # k 40 p 20 3.27x (15.32 / 4.69 ms) / 7.65x (34.23 / 4.48 ms), k 64 p 31 5.60x (103.6 / 18.5 ms) / 12.7x (209.9 / 16.5 ms), but
+    # k 20 p 10 only 1.76x (3.89 / 2.21 ms) in the bundle variant (transform 3.00x, 6.27 / 2.09 ms; spreads below 1 % everywhere).
+    # The default therefore starts at the smallest measured k that passed in both; method="tile64" names the kernel everywhere it covers
+    IENKS64_AUTO_MIN_K = 40
+
     def ienks_update(self, weights: torch.Tensor, Yb: Optional[torch.Tensor], d: Optional[torch.Tensor],
                      nbrs: NeighbourLists, tau: float = 1.0, epsilon: Optional[float] = None,
-                     rec: Optional[torch.Tensor] = None, return_flags: bool = False, method: str = "auto"):
+                     rec: Optional[torch.Tensor] = None, return_flags: bool = False, method: str = "auto",
+                     defer_retry: bool = False, out: Optional[torch.Tensor] = None):
         """One IEnKS weight update per grid point of the shard ``nbrs`` (core/ienks.py:108-141 on the localised
         block, interface/lienks.py:75-118).  ``weights``: (k, k) shared by all points (e.g. the prior weights) or
         (n, k, k); ``epsilon`` None = transform variant, a positive value = bundle variant.  Returns (n, k, k).
         ``method`` "auto": float32 updates with tau = 1 go through the eigensolver-free weights kernel (bundle variant
-        always, transform variant while Wp = I), the general kernel redoing what it declines; "eig": general kernel."""
+        always, transform variant while Wp = I), the general kernel redoing what it declines; float64 updates with tau = 1 go
+        through the tile kernel of csrc/lienks_tile64.hip where mia_lienks_update_f64_cover says yes (2 <= k <= 64, p_max <= k),
+        k >= IENKS64_AUTO_MIN_K, and the variant is bundle or the weights are ONE shared (k, k) matrix (per-point weights of the
+        transform variant have Wp != I everywhere: the launch would be declined whole).  "tile64": that kernel by name
+        (ValueError outside float64, tau = 1 and the cover); "eig": general kernel.  Points the tile kernel declines are redone
+        by the general kernel (mia_lienks_update_retry_f64) behind the 8-byte read of the decline counter; with ``defer_retry``
+        (method "tile64" only) that read is left to the caller, who must invoke the trailing callable of the result (it
+        returns the number of points redone).  ``out``: a contiguous (n, k, k) tensor of the weights' dtype to write into."""
+        if method not in ("auto", "eig", "tile64"):
+            raise ValueError("method must be 'auto', 'eig' or 'tile64'")
+        if defer_retry and method != "tile64":
+            raise ValueError("defer_retry needs method='tile64'")
         weights = torch.as_tensor(weights)
         dtype = weights.dtype if weights.dtype in (torch.float32, torch.float64) else torch.float64
         weights = weights.to(device=self.device, dtype=dtype).contiguous()
@@ -949,10 +970,20 @@ class LetkfEngine:
             raise ValueError("tau must lie in [0, 1]")           # bound_tensor(0, 1), interface/ienks.py:82-86
         if epsilon is not None and not float(epsilon) > 0.0:
             raise ValueError("epsilon must be positive")
-        out = torch.empty((n, k, k), dtype=dtype, device=self.device)
+        if out is None:
+            out = torch.empty((n, k, k), dtype=dtype, device=self.device)
+        elif out.shape != (n, k, k) or out.dtype != dtype or not out.is_contiguous() or out.device != weights.device:
+            raise ValueError("out must be a contiguous tensor (n, k, k) of the weights' dtype on the engine's device")
         flags = torch.empty(n, dtype=torch.int32, device=self.device)
         wstride = k * k if weights.dim() == 3 else 0
         eps_c = float(epsilon) if epsilon is not None else 0.0
+        if method == "tile64":
+            if dtype != torch.float64:
+                raise ValueError("method='tile64' needs float64 weights (float32 has its own route under 'auto')")
+            if float(tau) != 1.0:
+                raise ValueError("method='tile64' needs tau = 1 (tau = %g)" % float(tau))
+            if not self.lib.mia_lienks_update_f64_cover(k, min(nbrs.p_max, nbrs.p_cap), n, rec.shape[0]):
+                raise ValueError("method='tile64' covers 2 <= k <= 64 and p_max <= k (k = %d, p_max = %d)" % (k, nbrs.p_max))
         if dtype == torch.float32 and float(tau) == 1.0 and n > 0 and method != "eig":
             # tau = 1 through the eigensolver-free weights kernel; -3 = shape outside it (primal route, order > 32)
             retry = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -967,6 +998,39 @@ class LetkfEngine:
                         _ptr(nbrs.idx), _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max, 1.0, eps_c, _ptr(out), _ptr(flags),
                         self._stream()), "mia_lienks_update_retry_f32")
                 return (out, flags) if return_flags else out
+        take64 = False
+        if method == "tile64":
+            take64 = True
+        elif method == "auto" and dtype == torch.float64 and float(tau) == 1.0 and n > 0 and k >= self.IENKS64_AUTO_MIN_K:
+            take64 = (epsilon is not None or weights.dim() == 2) and bool(
+                self.lib.mia_lienks_update_f64_cover(k, min(nbrs.p_max, nbrs.p_cap), n, rec.shape[0]))
+        if take64:
+            retry = torch.zeros(1, dtype=torch.int32, device=self.device)
+            rc = self.lib.mia_lienks_update_matfun_f64(
+                _ptr(weights), wstride, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0], _ptr(nbrs.cnt), _ptr(nbrs.idx),
+                _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max, eps_c, _ptr(out), _ptr(flags), _ptr(retry), self._stream())
+            if rc == -3 and method == "tile64":
+                raise ValueError("method='tile64': the tile kernel is not available (option tile = 0, or the stream is being "
+                                 "captured before the coefficient table exists)")
+            if rc != -3:
+                _cabi.check(rc, "mia_lienks_update_matfun_f64")
+
+                def finish():         # (a closure over the weights, rec, the lists and out: a deferred retry finds them alive)
+                    n_retry = int(retry.item())        # host sync (8 bytes): the general kernel redoes the declined points
+                    if n_retry:
+                        _cabi.check(self.lib.mia_lienks_update_retry_f64(
+                            _ptr(weights), wstride, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0], _ptr(nbrs.cnt),
+                            _ptr(nbrs.idx), _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max, 1.0, eps_c, _ptr(out), _ptr(flags),
+                            self._stream()), "mia_lienks_update_retry_f64")
+                    return n_retry
+                if not defer_retry:
+                    finish()
+                res = [out]
+                if return_flags:
+                    res.append(flags)
+                if defer_retry:
+                    res.append(finish)
+                return res[0] if len(res) == 1 else tuple(res)
         sfx = "f32" if dtype == torch.float32 else "f64"
         fn = getattr(self.lib, "mia_lienks_update_" + sfx)
         _cabi.check(fn(_ptr(weights), k * k if weights.dim() == 3 else 0, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0],

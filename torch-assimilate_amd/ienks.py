@@ -77,7 +77,11 @@ class IEnKSBundleModule(IEnKSTransformModule):
 
 
 class LocalizedIEnKSTransform(LETKF):
-    """interface/lienks.py:34-118 (localization=None: interface/ienks.py:33-96, one global block)."""
+    """interface/lienks.py:34-118 (localization=None: interface/ienks.py:33-96, one global block).
+
+    With ``dtype=torch.float64`` and tau = 1 the first iteration of the localised loop (from the prior weights, Wp = I) runs on the
+    float64 tile kernel (csrc/lienks_tile64.hip) from ``LetkfEngine.IENKS64_AUTO_MIN_K`` members on, where the shape is covered
+    (k <= 64, no more local observations than members); every later iteration has Wp != I and stays on the general kernel."""
     _epsilon: Optional[float] = None
 
     def __init__(self, forward_model: Callable, localization=None, tau: float = 1.0, max_iter: int = 10,
@@ -161,7 +165,12 @@ class LocalizedIEnKSTransform(LETKF):
 
 
 class LocalizedIEnKSBundle(LocalizedIEnKSTransform):
-    """interface/lienks.py:121-163 (localization=None: interface/ienks.py:99-164)."""
+    """interface/lienks.py:121-163 (localization=None: interface/ienks.py:99-164).
+
+    With ``dtype=torch.float64`` and tau = 1 EVERY iteration of the localised loop runs on the float64 tile kernel
+    (csrc/lienks_tile64.hip: the bundle update depends on the incoming weights through their row means alone) from
+    ``LetkfEngine.IENKS64_AUTO_MIN_K`` members on, where the shape is covered (k <= 64, no more local observations than members);
+    tau < 1 and every other shape stay on the general kernel."""
 
     def __init__(self, forward_model: Callable, localization=None, tau: float = 1.0, epsilon: float = 1e-4,
                  max_iter: int = 10, smoother: bool = False, gpu: bool = True, pre_transform=None,
