@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Randomised check of the localised IEnKS update and the kernel-expression LKETKF against the CPU oracle
-(test infrastructure): ensemble sizes incl. odd ones, sparse / dense local lists, tau, both variants, two chained
-iterations; random kernel compositions.  float64 <= 1e-8, float32 <= 2e-4 on weights."""
+(test infrastructure): ensemble sizes incl. odd ones and one above 64 members, sparse / dense local lists, tau, both variants, two
+chained iterations from the prior weights and from per-point weights whose Wp makes the kernel's Gauss-Jordan inverse swap rows
+(the construction of tests/test_gpu_ienks_general.py); random kernel compositions.  float64 <= 1e-8, float32 <= 2e-4 on weights."""
 import os
 import sys
 
@@ -19,8 +20,22 @@ rs = np.random.RandomState(int(sys.argv[1]) if len(sys.argv) > 1 else 0)
 n_cases = int(sys.argv[2]) if len(sys.argv) > 2 else 30
 rel = lambda a, b: float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
 worst = {}
+
+
+def permuted_weights(n, k):
+    """(n, k, k): (I + 0.5 / sqrt(k) N)[perm, :] + 0.3 c 1^T with a fresh permutation per point, redrawn while cond(Wp) > 10"""
+    out = np.empty((n, k, k))
+    for g in range(n):
+        while True:
+            w = (np.eye(k) + 0.5 / np.sqrt(k) * rs.normal(size=(k, k)))[rs.permutation(k)] + 0.3 * rs.normal(size=(k, 1))
+            if np.linalg.cond(w - (w - np.eye(k)).mean(axis=1, keepdims=True)) <= 10.0:
+                break
+        out[g] = w
+    return out
+
+
 for case in range(n_cases):
-    k = int(rs.choice([5, 7, 10, 24, 40, 64]))
+    k = int(rs.choice([5, 7, 10, 24, 40, 64, 80]))
     G = 12
     P = int(rs.choice([6, 40, 300]))
     c = float(rs.choice([0.05, 0.3]))
@@ -32,20 +47,21 @@ for case in range(n_cases):
     scale = 1.0 if eps is None else eps
     nb = eng.localize(grid, obs, [c])
     tag = "k%d P%d pmax%d c%.2f tau%.1f eps%s" % (k, P, nb.p_max, c, tau, eps)
-    for dtype, name in ((torch.float64, "ienks f64"), (torch.float32, "ienks f32")):
-        w_ref = np.eye(k)
-        w = torch.eye(k, dtype=dtype, device=dev)
-        try:
-            for it in range(2):
-                w_ref = O.lienks_weights(w_ref, grid, obs, yb * scale, d, c, tau, eps)
-                w = eng.ienks_update(w, torch.as_tensor(yb * scale, dtype=dtype, device=dev), torch.as_tensor(d, dtype=dtype, device=dev),
-                                     nb, tau, eps)
-        except mia.MiaError as err:
-            print("skipped (unsupported shape):", tag, str(err)[:50])
-            continue
-        e = rel(w.cpu().numpy(), w_ref)
-        if e > worst.get(name, (0, ""))[0]:
-            worst[name] = (e, tag)
+    for start, w0 in (("prior", np.eye(k)), ("permuted", permuted_weights(G, k))):
+        for dtype, name in ((torch.float64, "ienks f64"), (torch.float32, "ienks f32")):
+            w_ref = w0
+            w = torch.as_tensor(w0, dtype=dtype, device=dev)
+            try:
+                for it in range(2):
+                    w_ref = O.lienks_weights(w_ref, grid, obs, yb * scale, d, c, tau, eps)
+                    w = eng.ienks_update(w, torch.as_tensor(yb * scale, dtype=dtype, device=dev),
+                                         torch.as_tensor(d, dtype=dtype, device=dev), nb, tau, eps)
+            except mia.MiaError as err:
+                print("skipped (unsupported shape):", tag, str(err)[:50])
+                continue
+            e = rel(w.cpu().numpy(), w_ref)
+            if e > worst.get(name, (0, ""))[0]:
+                worst[name] = (e, tag + " from " + start)
     # a random kernel composition through the expression route
     kerns = [(K.PolyKernel(2.0, 1.0), lambda x, y: O.poly_kernel(x, y, 2.0, 1.0)),
              (K.OrnsteinUhlenbeckKernel(5.0), lambda x, y: O.orn_uhl_kernel(x, y, 5.0)),
