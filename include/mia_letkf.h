@@ -474,6 +474,32 @@ int mia_letkf_analysis_wide_f64(const double* X, int64_t ldx, int m, int k, int6
                                 void* stream);
 int mia_letkf_wide_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P);
 
+/* The WEIGHTS of mia_letkf_weights_matfun_f64 for ensembles ABOVE 64 members (csrc/letkf_wide64w.hip): the frame of
+ * mia_letkf_analysis_wide_f64 -- union, one record image per workgroup, row blocks split over two (up to 96 slots) or four
+ * (up to 128) wavefronts, Gram matrix, Gershgorin bound, table row, degree and decline of every point are its own, bit for
+ * bit -- with one pass of the Chebyshev recurrence per MEMBER c < k on column c of the records, which yields row c of the
+ * sixteen points' weights.  Every sum over the union is one chain of v_mfma_f64_16x16x4_f64 in ascending slot order, so a
+ * point's bits do not depend on its tile, the shard boundary or the number of wavefronts.
+ * mia_letkf_weights_wide_f64: argument list and validation order of mia_letkf_weights_matfun_f64 (X and Xa may be NULL).
+ * Shapes: 2 <= k <= 128 (k <= 64 is accepted so that the route can be compared with mia_letkf_weights_matfun_f64, which
+ * keeps its own answers: k > 64 stays MIA_ERR_UNSUPPORTED there), 0 <= p_max <= k, gamma <= 0; everything else returns
+ * MIA_ERR_UNSUPPORTED before any launch, as do the option "tile" = 0 and a coefficient table that cannot be had (stream being
+ * captured).  Declined points (degree above the cap 127): MIA_FLAG_RETRY, counted in *retry_count (device int32, zeroed by
+ * the caller), W untouched; mia_letkf_weights_retry_f64 redoes them on the Jacobi kernel.  That kernel holds about 70 local
+ * observations: where a declined point has more, the redo fails with MIA_ERR_UNSUPPORTED AFTER every other point has been
+ * written -- a data-dependent limit, the one mia_letkf_analysis_wide_f64 has with mia_letkf_analysis_retry_f64.  A point
+ * without observations gets sqrt(inf_factor) I exactly; the Chebyshev degree of a written point is in bits 8-15 of its flag.
+ * mia_letkf_weights_wide_f64_cover: 1 when the shape is inside the route (2 <= k <= 128, 0 <= p_max <= k, the LDS of the
+ * chosen instantiation, the launch grid, 16 k^2 8 < 2^31 for the 32-bit offsets inside a tile's weights), 0 when not (host
+ * only, no device work). */
+int mia_letkf_weights_wide_f64(const double* X /* may be NULL */, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
+                               const double* rec, int64_t P,
+                               const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w,
+                               int p_cap, int p_max, double inf_factor, double gamma,
+                               double* Xa /* may be NULL */, int64_t ldo, int64_t o0, double* W /* [g1-g0][k][k] */,
+                               int32_t* flags, int32_t* retry_count, void* stream);
+int mia_letkf_weights_wide_f64_cover(int k, int p_max, int64_t n_points, int64_t P);
+
 /* The float64 RBF-kernelised analysis on tiles (csrc/lketkf_tile64.hip): KETKFModule._estimate_weights (core/ketkf.py:65-94)
  * with RBFKernel(gamma) / GaussKernel (kernels/rbf.py:75-81,110-111) under wrapper_localization (interface/wrapper.py:86-98)
  * and the transform of interface/base.py:257-278, sixteen grid points per workgroup of four wavefronts, without an

@@ -77,6 +77,9 @@ _PROTOS = {
     "mia_letkf_weights_retry_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
                                      vp, i64, i64, vp, vp, vp], i32),
     "mia_letkf_weights_f64_cover": ([i32, i32, i64, i64], i32),
+    "mia_letkf_weights_wide_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
+                                    vp, i64, i64, vp, vp, vp, vp], i32),
+    "mia_letkf_weights_wide_f64_cover": ([i32, i32, i64, i64], i32),
     "mia_letkf_weights_matfun_f32": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f32, f32,
                                       vp, i64, i64, vp, vp, vp, vp], i32),
     "mia_letkf_weights_retry_f32": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f32, f32,
@@ -185,7 +188,7 @@ ALLREDUCE_MAX_I32_FN = C.CFUNCTYPE(C.c_int, vp, vp, C.c_int, vp)
 
 
 class MiaError(RuntimeError):
-    pass
+    status = None          # the C status code (include/mia_letkf.h) when check() raised it
 
 
 def lib():
@@ -285,4 +288,6 @@ def check(status, what):
         msg = lib().mia_status_string(status).decode()
         if status == -6:
             msg += ": " + lib().mia_comm_last_error().decode()
-        raise MiaError("%s failed with status %d: %s" % (what, status, msg))
+        err = MiaError("%s failed with status %d: %s" % (what, status, msg))
+        err.status = status
+        raise err

@@ -120,6 +120,16 @@ int wide64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g
                            double inf_factor, double* Xa, int64_t ldo, int64_t o0, int32_t* flags, int32_t* retry_count,
                            hipStream_t stream);
 
+// letkf_wide64w.hip: letkf_tile64w.hip's float64 WEIGHTS [ng][k][k] for ensembles up to 128 members on letkf_wide64.hip's
+// frame (2 <= k <= 128, p_max <= k): one pass of the recurrence per member, the row blocks of the union split over two or
+// four wavefronts.  weights_wide64_route_covers: shape test (host only: the LDS of the chosen instantiation, the launch grid,
+// the 32-bit offsets inside a tile's weights); weights_wide64_launch: MIA_ERR_UNSUPPORTED outside it, with the option
+// tile = 0, and when the float64 coefficient table cannot be had.
+bool weights_wide64_route_covers(int k, int p_max, int64_t ng);
+int weights_wide64_launch(int k, int64_t ng, const double* rec, const int32_t* nbr_cnt, const int32_t* nbr_idx,
+                          const double* nbr_w, int p_cap, int p_max, double inf_factor, double* W, int32_t* flags,
+                          int32_t* retry_count, hipStream_t stream);
+
 // lketkf_tile64.hip: the float64 RBF-kernelised analysis on tiles (2 <= k <= 40, lists of at most 64 observations, any number
 // of state rows; no p_max <= k condition): one workgroup of four wavefronts per tile, the pair statistic on the matrix
 // cores, a point's k x k matrix in LDS.  rbf64_route_covers: shape test (host only, the LDS of the chosen instantiation

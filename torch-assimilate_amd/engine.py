@@ -923,6 +923,77 @@ class LetkfEngine:
             res.append(finish)
         return res[0] if len(res) == 1 else tuple(res)
 
+    # LETKF.estimate_weights_arrays hands float64 weights of ensembles above weights64's 64 members to weights_wide64 from this
+    # ensemble size on (the project's rule: the smallest MEASURED k from which every measured case is at least 2x the Jacobi
+    # kernel with W beyond both spreads, counter read included).  Measured on MI355X (tools/time_wide64w.py,
+    # profiles/wide64w_time.json), 1e5 points, Jacobi kernel with W / weights_wide64 with the counter read: k 65 p 53
+    # 4.53x (312.8 / 69.1 ms; worst round against best 4.51x), k 80 p 63 5.66x (417.7 / 73.8 ms; 5.65x); spreads at most 0.5 ms.
+    # The gate is therefore the route's first ensemble size, 65.  NOT measured against the Jacobi kernel, because it answers
+    # MIA_ERR_UNSUPPORTED with W there: k 96 p 81, k 128 p 97 and also k 128 p 62 (206.6 ms per 1e5 points, 116.1 and 107.5 ms per
+    # 5e4 points on this route); no shape between 65 and 80 or 80 and 96 members, no list shorter than 53, was measured either.
+    # Below 65 members letkf_weights64_kernel keeps the class route (k 64 p 57: 84.9 ms against 59.3 ms here, 1.43x, equal bits
+    # -- a factor below the rule's 2); weights_wide64 itself stays available everywhere the kernel covers
+    WEIGHTS_WIDE64_AUTO_MIN_K = 65
+
+    def weights_wide64(self, Yb: Optional[torch.Tensor], d: Optional[torch.Tensor], nbrs: NeighbourLists,
+                       inf_factor: float = 1.0, rec: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                       return_flags: bool = False, defer_retry: bool = False, rbf_gamma: Optional[float] = None):
+        """:meth:`weights64` for ensembles of up to 128 members (mia_letkf_weights_wide_f64, csrc/letkf_wide64w.hip): the same
+        float64 weights W (n, k, k) with a tile's union split over two or four wavefronts, 2 <= k <= 128, p_max <= k, plain
+        ETKF core; the same arguments and the same answers -- W [, flags (n,)] [, finish], or None where the entry answers
+        MIA_ERR_UNSUPPORTED (any other shape, float32 input, ``rbf_gamma``, option tile = 0).  Points the kernel declines are
+        redone by the Jacobi kernel (mia_letkf_weights_retry_f64) behind the 8-byte read of the decline counter; with
+        ``defer_retry`` that read is left to the caller, who must invoke the trailing callable (it returns the number of points
+        redone).  The Jacobi kernel holds about 70 local observations: a declined point with more makes the redo raise MiaError
+        AFTER every other point has been written -- data-dependent, as ``analysis(method="wide64")`` documents for the analysis."""
+        if rec is None:
+            if Yb.dim() != 2 or Yb.dtype != torch.float64:
+                return None
+            rec = self.pack_obs(Yb, d, torch.float64)
+        if rec.dtype != torch.float64 or rec.dim() != 2 or rec.shape[1] < 3:
+            return None
+        kp = rec.shape[1]
+        k = int(Yb.shape[0]) if Yb is not None else (int(out.shape[-1]) if out is not None else None)
+        if k is None:
+            raise ValueError("weights_wide64 from packed records alone needs out= (n, k, k) for the ensemble size")
+        if kp != (k + 1 + 3) // 4 * 4:
+            raise ValueError("packed records do not match the ensemble size")
+        n = nbrs.g1 - nbrs.g0
+        if out is None:
+            out = torch.empty((n, k, k), dtype=torch.float64, device=self.device)
+        elif out.shape != (n, k, k) or out.dtype != torch.float64 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float64 tensor (n, k, k)")
+        W = out
+        flags = torch.empty(n, dtype=torch.int32, device=self.device)
+        retry = torch.zeros(1, dtype=torch.int32, device=self.device)
+        gamma = float(rbf_gamma) if rbf_gamma is not None else 0.0
+
+        def args(X, Xa):      # (a closure over rec, the lists and W: a deferred retry finds them alive)
+            return (_ptr(X), nbrs.g1, 1, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0], _ptr(nbrs.cnt), _ptr(nbrs.idx),
+                    _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max, float(inf_factor), gamma, _ptr(Xa), n, 0, _ptr(W), _ptr(flags))
+        rc = self.lib.mia_letkf_weights_wide_f64(*args(None, None), _ptr(retry), self._stream())
+        if rc == -3:
+            return None
+        _cabi.check(rc, "mia_letkf_weights_wide_f64")
+
+        def finish():
+            n_retry = int(retry.item())          # host sync (8 bytes)
+            if n_retry:
+                # the Jacobi kernel computes an analysis next to the weights: a one-row zero state and its output, from the
+                # workspace, and only now that a point needs them
+                x0 = self._workspace("weights64_x0", 8 * k * max(nbrs.g1, 1)).view(torch.float64)[:k * nbrs.g1].zero_()
+                xa = self._workspace("weights64_xa", 8 * k * max(n, 1)).view(torch.float64)
+                _cabi.check(self.lib.mia_letkf_weights_retry_f64(*args(x0, xa), self._stream()), "mia_letkf_weights_retry_f64")
+            return n_retry
+        if not defer_retry:
+            finish()
+        res = [W]
+        if return_flags:
+            res.append(flags)
+        if defer_retry:
+            res.append(finish)
+        return res[0] if len(res) == 1 else tuple(res)
+
     # ------------------------------------------------------------------- IEnKS
     # ienks_update(method="auto") hands float64 updates with tau = 1 to the tile kernel (csrc/lienks_tile64.hip) only from this
     # ensemble size on: the project's rule for WEIGHTS64_AUTO_MIN_K -- the smallest measured k at which the route, counter read

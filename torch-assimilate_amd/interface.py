@@ -27,6 +27,7 @@ from typing import Callable, Iterable, List, Optional, Sequence, Union
 import numpy as np
 import torch
 
+from ._cabi import MiaError
 from .engine import LetkfEngine, warn_if_noconv
 from .kernels import kernel_is_psd, kernel_route
 from .localization import GaspariCohn
@@ -254,7 +255,18 @@ class LETKF(ETKF):
         W = self._weights_on_tiles64(yb, d, nb)
         if W is not None:
             return W
-        _, W = self.engine.analysis(x, yb, d, nb, self.inf_factor, return_weights=True, **self._kernel_args())
+        W = self._weights_on_wide64(yb, d, nb)
+        if W is not None:
+            return W
+        try:
+            _, W = self.engine.analysis(x, yb, d, nb, self.inf_factor, return_weights=True, **self._kernel_args())
+        except MiaError as err:
+            # the Jacobi kernel cannot hold the shape (about 70 local observations): below the gate the wide kernel still can
+            if err.status != -3:
+                raise
+            W = self._weights_on_wide64(yb, d, nb, gated=False)
+            if W is None:
+                raise
         return W
 
     def _weights_on_tiles(self, x, yb, d, nb, grid_coords, obs_coords, p_max=None, g0=None, g1=None, lists=None):
@@ -306,6 +318,20 @@ class LETKF(ETKF):
                 or nb.g1 - nb.g0 <= 0 or yb.shape[0] < self.engine.WEIGHTS64_AUTO_MIN_K):
             return None
         return self.engine.weights64(yb, d, nb, self.inf_factor)
+
+    def _weights_on_wide64(self, yb, d, nb, gated=True):
+        """The float64 weights of ensembles up to 128 members (engine.weights_wide64, csrc/letkf_wide64w.hip) where that route
+        applies: the default dtype, the plain ETKF core, p_max <= k <= 128 and -- ``gated`` -- k >= WEIGHTS_WIDE64_AUTO_MIN_K
+        (LetkfEngine: the measured factor 2 over the Jacobi kernel); ungated it serves where the Jacobi kernel cannot hold the
+        shape at all.  From the per-point lists, so with every localisation.  Declined points are redone with weights by the
+        Jacobi kernel inside the engine call: where it cannot hold such a point (about 70 local observations or more) that
+        redo raises MiaError after the other points are written -- data-dependent, as for the analysis of these ensembles.
+        None: the caller takes ``engine.analysis(return_weights=True)``."""
+        ka = self._kernel_args()
+        if (yb.dtype != torch.float64 or ka.get("rbf_gamma") is not None or ka.get("kernel_program") is not None
+                or nb.g1 - nb.g0 <= 0 or (gated and yb.shape[0] < self.engine.WEIGHTS_WIDE64_AUTO_MIN_K)):
+            return None
+        return self.engine.weights_wide64(yb, d, nb, self.inf_factor)
 
     def _analysis_by_step_driver(self, x, yb, d, grid_coords, obs_coords, g0, g1):
         """The whole analysis as ONE call of the native step driver (sharded.ShardedLetkf on one rank: observation index, the
