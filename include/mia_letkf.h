@@ -720,6 +720,28 @@ int mia_lienks_update_retry_f64(const double* W_in, int64_t w_stride, int k, int
                                 const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
                                 double tau, double epsilon, double* W_out, int32_t* flags, void* stream);
 int mia_lienks_update_f64_cover(int k, int p_max, int64_t n_points, int64_t P);
+/* mia_lienks_update_matfun_f64 for ensembles ABOVE 64 members (csrc/lienks_wide64.hip): the frame of
+ * mia_letkf_weights_wide_f64 -- union, one record image per workgroup, row blocks split over two (up to 96 slots) or four
+ * (up to 128) wavefronts, Gram matrix, Gershgorin bound, table row, degree and decline of every point -- at inflation 1, with
+ * the row means of W_in, the shift D^T w_mean as one more accumulator chain of the Gram loop and the 1 / epsilon scaling of
+ * the bundle variant as in mia_lienks_update_matfun_f64.  Every sum over the union is one chain of v_mfma_f64_16x16x4_f64 in
+ * ascending slot order and the row means are summed in an order that depends on (i, j) alone, so a point's bits do not depend
+ * on its tile, the shard boundary or the number of wavefronts.
+ * mia_lienks_update_wide_f64: argument list, validation order and conventions of mia_lienks_update_matfun_f64 (empty lists,
+ * the transform variant's decline away from the prior -- max |W_in - w_mean 1^T - I| <= 1e-14 perturbs D by at most 1.3e-12 at
+ * k = 128 --, flags, decline counter, degree in bits 8-15).  Shapes: 2 <= k <= 128 (k <= 64 is accepted so that the route can
+ * be compared with mia_lienks_update_matfun_f64, which keeps its own answers: k > 64 stays MIA_ERR_UNSUPPORTED there),
+ * 0 <= p_max <= k; everything else returns MIA_ERR_UNSUPPORTED before any launch and before anything is dereferenced, as do
+ * the option "tile" = 0 and a coefficient table that cannot be had (stream being captured).  Declined points are redone by
+ * mia_lienks_update_retry_f64; where the general kernel cannot hold a declined point's shape that redo fails with
+ * MIA_ERR_UNSUPPORTED AFTER every other point has been written -- a data-dependent limit, as with mia_letkf_weights_wide_f64.
+ * mia_lienks_update_wide_f64_cover: mia_letkf_weights_wide_f64_cover's arithmetic (2 <= k <= 128, 0 <= p_max <= k, the LDS of
+ * the chosen instantiation, the launch grid, 16 k^2 8 < 2^31), host only, no device work. */
+int mia_lienks_update_wide_f64(const double* W_in, int64_t w_stride, int k, int64_t g0, int64_t g1,
+                               const double* rec, int64_t P,
+                               const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                               double epsilon, double* W_out, int32_t* flags, int32_t* retry_count, void* stream);
+int mia_lienks_update_wide_f64_cover(int k, int p_max, int64_t n_points, int64_t P);
 
 /* ------------------------------------------------------------------------------------
  * Observation-space preparation, the step immediately upstream of the analysis

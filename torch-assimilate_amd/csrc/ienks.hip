@@ -475,6 +475,27 @@ extern "C" int mia_lienks_update_f64_cover(int k, int p_max, int64_t n_points, i
   if (P < 0) return 0;
   return lienks64_route_covers(k, p_max, n_points) ? 1 : 0;
 }
+// tau = 1 in float64 on tiles for ensembles up to 128 members (lienks_wide64.hip): mia_lienks_update_matfun_f64's validation in
+// its order, then the option and the cover, then the one kernel of the route
+extern "C" int mia_lienks_update_wide_f64(const double* W_in, int64_t w_stride, int k, int64_t g0, int64_t g1,
+                                          const double* rec, int64_t P, const int32_t* nbr_cnt, const int32_t* nbr_idx,
+                                          const double* nbr_w, int p_cap, int p_max, double epsilon, double* W_out,
+                                          int32_t* flags, int32_t* retry_count, void* stream) {
+  (void)hipGetLastError();
+  if (g1 < g0 || g0 < 0 || k < 2 || P < 0 || p_cap < 1 || p_max < 0) return MIA_ERR_SIZE;
+  if (w_stride != 0 && w_stride != (int64_t)k * k) return MIA_ERR_SIZE;
+  const int64_t ng = g1 - g0;
+  if (ng == 0) return MIA_OK;
+  if (!W_in || !W_out || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
+  if (P > 0 && !rec) return MIA_ERR_NULL;
+  if (p_max > p_cap) p_max = p_cap;
+  return lienks_wide64_launch(W_in, w_stride, k, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, epsilon, W_out, flags,
+                              retry_count, (hipStream_t)stream);
+}
+extern "C" int mia_lienks_update_wide_f64_cover(int k, int p_max, int64_t n_points, int64_t P) {
+  if (P < 0) return 0;
+  return lienks_wide64_route_covers(k, p_max, n_points) ? 1 : 0;
+}
 extern "C" int mia_apply_local_weights_f32(const float* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
                                            const float* W, float* Xa, int64_t ldo, int64_t o0, void* stream) {
   (void)hipGetLastError();

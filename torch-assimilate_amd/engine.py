@@ -1003,6 +1003,20 @@ class LetkfEngine:
     # k 20 p 10 only 1.76x (3.89 / 2.21 ms) in the bundle variant (transform 3.00x, 6.27 / 2.09 ms; spreads below 1 % everywhere).
     # The default therefore starts at the smallest measured k that passed in both; method="tile64" names the kernel everywhere it covers
     IENKS64_AUTO_MIN_K = 40
+    # Above lienks_update64_kernel's 64 members, ienks_update(method="auto") hands float64 updates with tau = 1 to the wide tile
+    # kernel (csrc/lienks_wide64.hip) from this ensemble size on.  The rule is the one above: the smallest MEASURED k >= 65 from
+    # which every measured case, counter read included, is at least 2x the general kernel in BOTH variants, beyond both spreads.
+    # Measured on MI355X (tools/time_ienks_wide64.py, profiles/ienks_wide64_time.json), 1e5 points, general kernel /
+    # route with the counter read, bundle (per-point weights) and transform (shared prior): k 65 p 53 4.27x (287.5 / 67.4 ms) and
+    # 6.14x (405.0 / 66.0 ms), k 80 p 63 bundle 5.20x (375.9 / 72.2 ms; the general kernel refuses the transform variant there),
+    # k 80 p 20 5.84x (62.3 / 10.7 ms) and 24.9x (244.1 / 9.8 ms); worst round against best round at least 4.26x, spreads at
+    # most 0.9 ms.  The gate is therefore the route's first ensemble size, 65.  NOT measured against the general kernel, because it
+    # answers MIA_ERR_UNSUPPORTED there in both variants: k 96 p 81 (201.2 / 197.5 ms per 1e5 points on this route), k 128 p 97
+    # (114.1 / 111.6 ms per 5e4 points) and k 128 p 62 (106.2 / 103.7 ms per 5e4 points); no shape between 65 and 80 or 80 and 96
+    # members, and no list shorter than 20, was measured either.  Where the general kernel refuses a shape the route is taken
+    # whatever this gate says.  Below 65 members lienks_update64_kernel keeps "auto" (k 64 p 57: 83.4 / 81.1 ms against 57.9 /
+    # 56.6 ms here, 1.44x / 1.43x, equal bits -- a factor below the rule's 2); method="wide64" names the kernel everywhere it covers
+    IENKS_WIDE64_AUTO_MIN_K = 65
 
     def ienks_update(self, weights: torch.Tensor, Yb: Optional[torch.Tensor], d: Optional[torch.Tensor],
                      nbrs: NeighbourLists, tau: float = 1.0, epsilon: Optional[float] = None,
@@ -1015,15 +1029,20 @@ class LetkfEngine:
         always, transform variant while Wp = I), the general kernel redoing what it declines; float64 updates with tau = 1 go
         through the tile kernel of csrc/lienks_tile64.hip where mia_lienks_update_f64_cover says yes (2 <= k <= 64, p_max <= k),
         k >= IENKS64_AUTO_MIN_K, and the variant is bundle or the weights are ONE shared (k, k) matrix (per-point weights of the
-        transform variant have Wp != I everywhere: the launch would be declined whole).  "tile64": that kernel by name
-        (ValueError outside float64, tau = 1 and the cover); "eig": general kernel.  Points the tile kernel declines are redone
-        by the general kernel (mia_lienks_update_retry_f64) behind the 8-byte read of the decline counter; with ``defer_retry``
-        (method "tile64" only) that read is left to the caller, who must invoke the trailing callable of the result (it
-        returns the number of points redone).  ``out``: a contiguous (n, k, k) tensor of the weights' dtype to write into."""
-        if method not in ("auto", "eig", "tile64"):
-            raise ValueError("method must be 'auto', 'eig' or 'tile64'")
-        if defer_retry and method != "tile64":
-            raise ValueError("defer_retry needs method='tile64'")
+        transform variant have Wp != I everywhere: the launch would be declined whole); above 64 members, under the same
+        variant condition, through the wide tile kernel of csrc/lienks_wide64.hip where mia_lienks_update_wide_f64_cover says
+        yes (2 <= k <= 128, p_max <= k) and k >= IENKS_WIDE64_AUTO_MIN_K -- and, whatever that gate says, where the general
+        kernel answers MIA_ERR_UNSUPPORTED because its LDS cannot hold the shape.  "tile64" / "wide64": those kernels by name
+        (ValueError outside float64, tau = 1 and the kernel's cover); "eig": general kernel.  Points a tile kernel declines are
+        redone by the general kernel (mia_lienks_update_retry_f64) behind the 8-byte read of the decline counter; where the
+        general kernel cannot hold a declined point's shape that redo raises MiaError AFTER every other point has been
+        written -- data-dependent, as ``weights_wide64`` documents.  With ``defer_retry`` (methods "tile64" and "wide64" only)
+        the read is left to the caller, who must invoke the trailing callable of the result (it returns the number of points
+        redone).  ``out``: a contiguous (n, k, k) tensor of the weights' dtype to write into."""
+        if method not in ("auto", "eig", "tile64", "wide64"):
+            raise ValueError("method must be 'auto', 'eig', 'tile64' or 'wide64'")
+        if defer_retry and method not in ("tile64", "wide64"):
+            raise ValueError("defer_retry needs method='tile64' or 'wide64'")
         weights = torch.as_tensor(weights)
         dtype = weights.dtype if weights.dtype in (torch.float32, torch.float64) else torch.float64
         weights = weights.to(device=self.device, dtype=dtype).contiguous()
@@ -1055,6 +1074,13 @@ class LetkfEngine:
                 raise ValueError("method='tile64' needs tau = 1 (tau = %g)" % float(tau))
             if not self.lib.mia_lienks_update_f64_cover(k, min(nbrs.p_max, nbrs.p_cap), n, rec.shape[0]):
                 raise ValueError("method='tile64' covers 2 <= k <= 64 and p_max <= k (k = %d, p_max = %d)" % (k, nbrs.p_max))
+        if method == "wide64":
+            if dtype != torch.float64:
+                raise ValueError("method='wide64' needs float64 weights (float32 has its own route under 'auto')")
+            if float(tau) != 1.0:
+                raise ValueError("method='wide64' needs tau = 1 (tau = %g)" % float(tau))
+            if not self.lib.mia_lienks_update_wide_f64_cover(k, min(nbrs.p_max, nbrs.p_cap), n, rec.shape[0]):
+                raise ValueError("method='wide64' covers 2 <= k <= 128 and p_max <= k (k = %d, p_max = %d)" % (k, nbrs.p_max))
         if dtype == torch.float32 and float(tau) == 1.0 and n > 0 and method != "eig":
             # tau = 1 through the eigensolver-free weights kernel; -3 = shape outside it (primal route, order > 32)
             retry = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -1069,45 +1095,67 @@ class LetkfEngine:
                         _ptr(nbrs.idx), _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max, 1.0, eps_c, _ptr(out), _ptr(flags),
                         self._stream()), "mia_lienks_update_retry_f32")
                 return (out, flags) if return_flags else out
-        take64 = False
+        f64_tau1 = dtype == torch.float64 and float(tau) == 1.0 and n > 0
+        # (per-point weights of the transform variant have Wp != I everywhere: a tile launch would be declined whole)
+        variant_ok = epsilon is not None or weights.dim() == 2
+        entry = None
         if method == "tile64":
-            take64 = True
-        elif method == "auto" and dtype == torch.float64 and float(tau) == 1.0 and n > 0 and k >= self.IENKS64_AUTO_MIN_K:
-            take64 = (epsilon is not None or weights.dim() == 2) and bool(
-                self.lib.mia_lienks_update_f64_cover(k, min(nbrs.p_max, nbrs.p_cap), n, rec.shape[0]))
-        if take64:
+            entry = "mia_lienks_update_matfun_f64"
+        elif method == "wide64":
+            entry = "mia_lienks_update_wide_f64"
+        elif method == "auto" and f64_tau1 and variant_ok:
+            if k >= self.IENKS64_AUTO_MIN_K and self.lib.mia_lienks_update_f64_cover(
+                    k, min(nbrs.p_max, nbrs.p_cap), n, rec.shape[0]):
+                entry = "mia_lienks_update_matfun_f64"
+            elif k >= self.IENKS_WIDE64_AUTO_MIN_K and self.lib.mia_lienks_update_wide_f64_cover(
+                    k, min(nbrs.p_max, nbrs.p_cap), n, rec.shape[0]):
+                entry = "mia_lienks_update_wide_f64"
+
+        def tile_route(entry):
+            """The tile kernel behind ``entry`` and the redo of what it declines; None where the entry answers -3."""
             retry = torch.zeros(1, dtype=torch.int32, device=self.device)
-            rc = self.lib.mia_lienks_update_matfun_f64(
+            rc = getattr(self.lib, entry)(
                 _ptr(weights), wstride, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0], _ptr(nbrs.cnt), _ptr(nbrs.idx),
                 _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max, eps_c, _ptr(out), _ptr(flags), _ptr(retry), self._stream())
-            if rc == -3 and method == "tile64":
-                raise ValueError("method='tile64': the tile kernel is not available (option tile = 0, or the stream is being "
-                                 "captured before the coefficient table exists)")
-            if rc != -3:
-                _cabi.check(rc, "mia_lienks_update_matfun_f64")
+            if rc == -3:
+                return None
+            _cabi.check(rc, entry)
 
-                def finish():         # (a closure over the weights, rec, the lists and out: a deferred retry finds them alive)
-                    n_retry = int(retry.item())        # host sync (8 bytes): the general kernel redoes the declined points
-                    if n_retry:
-                        _cabi.check(self.lib.mia_lienks_update_retry_f64(
-                            _ptr(weights), wstride, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0], _ptr(nbrs.cnt),
-                            _ptr(nbrs.idx), _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max, 1.0, eps_c, _ptr(out), _ptr(flags),
-                            self._stream()), "mia_lienks_update_retry_f64")
-                    return n_retry
-                if not defer_retry:
-                    finish()
-                res = [out]
-                if return_flags:
-                    res.append(flags)
-                if defer_retry:
-                    res.append(finish)
-                return res[0] if len(res) == 1 else tuple(res)
+            def finish():         # (a closure over the weights, rec, the lists and out: a deferred retry finds them alive)
+                n_retry = int(retry.item())        # host sync (8 bytes): the general kernel redoes the declined points
+                if n_retry:
+                    _cabi.check(self.lib.mia_lienks_update_retry_f64(
+                        _ptr(weights), wstride, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0], _ptr(nbrs.cnt),
+                        _ptr(nbrs.idx), _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max, 1.0, eps_c, _ptr(out), _ptr(flags),
+                        self._stream()), "mia_lienks_update_retry_f64")
+                return n_retry
+            if not defer_retry:
+                finish()
+            res = [out]
+            if return_flags:
+                res.append(flags)
+            if defer_retry:
+                res.append(finish)
+            return res[0] if len(res) == 1 else tuple(res)
+        if entry is not None:
+            res = tile_route(entry)
+            if res is not None:
+                return res
+            if method in ("tile64", "wide64"):
+                raise ValueError("method='%s': the tile kernel is not available (option tile = 0, or the stream is being "
+                                 "captured before the coefficient table exists)" % method)
         sfx = "f32" if dtype == torch.float32 else "f64"
         fn = getattr(self.lib, "mia_lienks_update_" + sfx)
-        _cabi.check(fn(_ptr(weights), k * k if weights.dim() == 3 else 0, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0],
-                       _ptr(nbrs.cnt), _ptr(nbrs.idx), _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max, float(tau),
-                       float(epsilon) if epsilon is not None else 0.0, _ptr(out), _ptr(flags), self._stream()),
-                    "mia_lienks_update_" + sfx)
+        rc = fn(_ptr(weights), k * k if weights.dim() == 3 else 0, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0],
+                _ptr(nbrs.cnt), _ptr(nbrs.idx), _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max, float(tau),
+                float(epsilon) if epsilon is not None else 0.0, _ptr(out), _ptr(flags), self._stream())
+        if (rc == -3 and method == "auto" and f64_tau1 and variant_ok and entry != "mia_lienks_update_wide_f64" and
+                self.lib.mia_lienks_update_wide_f64_cover(k, min(nbrs.p_max, nbrs.p_cap), n, rec.shape[0])):
+            # the general kernel cannot hold the shape (its LDS): the wide tile kernel can, whatever the gate says
+            res = tile_route("mia_lienks_update_wide_f64")
+            if res is not None:
+                return res
+        _cabi.check(rc, "mia_lienks_update_" + sfx)
         return (out, flags) if return_flags else out
 
     def apply_local_weights(self, X: torch.Tensor, W: torch.Tensor, g0: int = 0, g1: Optional[int] = None) -> torch.Tensor:

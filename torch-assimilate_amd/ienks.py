@@ -81,7 +81,10 @@ class LocalizedIEnKSTransform(LETKF):
 
     With ``dtype=torch.float64`` and tau = 1 the first iteration of the localised loop (from the prior weights, Wp = I) runs on the
     float64 tile kernel (csrc/lienks_tile64.hip) from ``LetkfEngine.IENKS64_AUTO_MIN_K`` members on, where the shape is covered
-    (k <= 64, no more local observations than members); every later iteration has Wp != I and stays on the general kernel."""
+    (k <= 64, no more local observations than members); for 65 .. 128 members it runs on the wide tile kernel
+    (csrc/lienks_wide64.hip) from ``LetkfEngine.IENKS_WIDE64_AUTO_MIN_K`` members on, and wherever the general kernel cannot
+    hold the shape.  Every later iteration has Wp != I and stays on the general kernel, which above 64 members holds only short
+    observation lists (e.g. not k = 80 with 63): there the second iteration raises MiaError."""
     _epsilon: Optional[float] = None
 
     def __init__(self, forward_model: Callable, localization=None, tau: float = 1.0, max_iter: int = 10,
@@ -170,7 +173,9 @@ class LocalizedIEnKSBundle(LocalizedIEnKSTransform):
     With ``dtype=torch.float64`` and tau = 1 EVERY iteration of the localised loop runs on the float64 tile kernel
     (csrc/lienks_tile64.hip: the bundle update depends on the incoming weights through their row means alone) from
     ``LetkfEngine.IENKS64_AUTO_MIN_K`` members on, where the shape is covered (k <= 64, no more local observations than members);
-    tau < 1 and every other shape stay on the general kernel."""
+    for 65 .. 128 members on the wide tile kernel (csrc/lienks_wide64.hip) from ``LetkfEngine.IENKS_WIDE64_AUTO_MIN_K`` members
+    on, and wherever the general kernel cannot hold the shape (e.g. k = 96 with 81 or k = 128 with 62 local observations).
+    tau < 1, more local observations than members and more than 128 members stay on the general kernel."""
 
     def __init__(self, forward_model: Callable, localization=None, tau: float = 1.0, epsilon: float = 1e-4,
                  max_iter: int = 10, smoother: bool = False, gpu: bool = True, pre_transform=None,
