@@ -452,6 +452,32 @@ int mia_letkf_analysis_dense_f64(const double* X, int64_t ldx, int m, int k, int
                                  void* stream);
 int mia_letkf_dense_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P);
 
+/* The analysis of mia_letkf_analysis_dense_f64 for DENSE local networks of ensembles up to 128 members
+ * (csrc/letkf_stream64.hip; what it replaces per point: the gather and sqrt(rho) scaling of interface/wrapper.py:86-98, the
+ * decomposition and weights of core/etkf.py:57-103, the transform of interface/base.py:257-278).  The same mathematics,
+ * prologue, streamed Gershgorin bound, coefficient table (target exp(-26), margin 2, degree cap 127), flags and decline
+ * counter; the one difference is that the records of a tile's union are NOT resident in LDS: every pass over the union
+ * gathers its sixteen-slot blocks of `rec` rows through a ring of two blocks, the next block on its way while the current
+ * one is multiplied (both products of a step read it, so a block is fetched once per step).  LDS per wavefront: the
+ * sqrt(rho) table, the slot table, the ring and the tile's right-hand side -- 256 slots at every ensemble size.  Every sum
+ * over the union is one chain of v_mfma_f64_16x16x4_f64 in ascending slot order, so a point's bits do not depend on its
+ * tile, the shard boundary or the halving of a tile.  Argument list and validation order as mia_letkf_analysis_dense_f64;
+ * declined points are redone by mia_letkf_analysis_retry_f64, which holds a point's matrices in LDS and answers
+ * MIA_ERR_UNSUPPORTED from 97 members on: a declined point then fails AFTER every other point has been written -- a
+ * data-dependent limit, the one mia_letkf_analysis_wide_f64 has.  Shapes: 2 <= k <= 128 (k <= 64 is accepted so that the
+ * route can be compared with mia_letkf_analysis_dense_f64), k < p_max <= 256, any m; everything else -- p_max <= k
+ * included, which is the dual routes' -- returns MIA_ERR_UNSUPPORTED before any launch, as do gamma > 0, the option "tile" = 0
+ * and a coefficient table that cannot be had (stream being captured).
+ * mia_letkf_stream_f64_cover: 1 when the shape is inside the route (2 <= k <= 128, k < p_max <= 256, k * ld * 8 < 2^31 for
+ * both leading dimensions, at most 65536 * 65535 tiles), 0 when not (host only, no device work). */
+int mia_letkf_analysis_stream_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
+                                  const double* rec, int64_t P,
+                                  const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w,
+                                  int p_cap, int p_max, double inf_factor, double gamma,
+                                  double* Xa, int64_t ldo, int64_t o0, int32_t* flags, int32_t* retry_count,
+                                  void* stream);
+int mia_letkf_stream_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P);
+
 /* The analysis of mia_letkf_analysis_matfun_f64 for ensembles ABOVE 64 members (csrc/letkf_wide64.hip): the same mathematics,
  * input, prologue, coefficient table (target exp(-26), margin 2, degree cap 127), flags and decline counter, with the
  * sixteen-slot row blocks of a tile's union split over the two (up to 96 slots) or four (up to 128) wavefronts of a

@@ -109,6 +109,17 @@ int dense64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t 
                             double inf_factor, double* Xa, int64_t ldo, int64_t o0, int32_t* flags, int32_t* retry_count,
                             hipStream_t stream);
 
+// letkf_stream64.hip: letkf_dense64.hip's analysis with the union's records streamed through a ring of two sixteen-slot blocks
+// in LDS instead of a resident image (primal form, 2 <= k <= 128, k < p_max <= 256, any number of state rows): what dense
+// networks of 65 .. 128 members run.  stream64_route_covers: shape test (host only; false for p_max <= k, which is the dual
+// routes'); stream64_analysis_launch: MIA_ERR_UNSUPPORTED outside it, with the option tile = 0, and when its coefficient
+// table cannot be had.
+bool stream64_route_covers(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t ng);
+int stream64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t ng, const double* rec,
+                             const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                             double inf_factor, double* Xa, int64_t ldo, int64_t o0, int32_t* flags, int32_t* retry_count,
+                             hipStream_t stream);
+
 // letkf_wide64.hip: letkf_tile64.hip's analysis for ensembles up to 128 members (dual route, 2 <= k <= 128, p_max <= k, any
 // number of state rows): the row blocks of the union are split over the two or four wavefronts of a workgroup, which share
 // one record image.  wide64_route_covers: shape test (host only, the LDS of the chosen instantiation included);

@@ -578,6 +578,50 @@ class LetkfEngine:
     WIDE64_AUTO_MIN_K = 65
     WIDE64_AUTO_MAX_ROWS = 8
 
+    # method="auto" hands a float64 shape with p_max > k that none of the routes above took to the streamed dense route
+    # (csrc/letkf_stream64.hip) in two cases.  (1) Wherever the Jacobi kernel cannot hold the shape (it keeps two
+    # k x (k + 1) float64 matrices in LDS and answers MIA_ERR_UNSUPPORTED from 97 members on, see
+    # _jacobi_primal_fits): there is nothing to compare with, the alternative is MiaError.  (2) Where the Jacobi kernel
+    # runs, from STREAM64_AUTO_MIN_K members on, only while STREAM64_AUTO_DEN * p_max <= STREAM64_AUTO_NUM * k and
+    # m <= STREAM64_AUTO_MAX_ROWS: the range in which every measured case beat it by the project's factor 2.
+    # Measured on MI355X (tools/time_stream64.py, profiles/stream64_time.json), 1e5 points (5e4 at k 128), counter read
+    # included, Jacobi kernel on a build of the parent commit / this route, median ms, m = 1 and m = 8:
+    #   k 80  p  93: 126.5x (858.4 / 6.78)    22.1x (915.6 / 41.5)       k 80  p 173: 33.8x (744.2 / 22.0)   6.2x (803.0 / 129.1)
+    #   k 96  p 107: 104.6x (1353.8 / 12.94)  17.8x (1421.5 / 79.9)      k 96  p 173: 47.4x (1154.1 / 24.4)  8.5x (1225.5 / 143.8)
+    #   316 x 316 mesh, k 80 p 101 (tiles in 2.7 parts): 15.5x (868.4 / 56.0)   3.26x (929.5 / 284.9)
+    #   k 128 p 139: 11.35 ms, 69.2 ms at m 8; p 203: 19.0 / 111.9 ms per 5e4 points -- the parent raises MiaError, no ratio
+    # Every measured case passes the factor 2 beyond both spreads (all below 0.2 %), the mesh included, so the rule is the range
+    # that was measured: the route's first ensemble size (as WIDE64_AUTO_MIN_K: nothing between 65 and 80 was measured), p_max / k
+    # up to the largest measured (173 / 80 = 2.16), up to the 8 state rows that were measured (a further row costs 32.7 ms here
+    # and 8.7 ms on the Jacobi kernel on the mesh: the factor would fall below 2 near 14 rows).  NOT measured: p_max / k above
+    # 2.16 (up to 256 / 65), more than 8 rows, rows between 1 and 8, ensembles between 65 and 80 or 80 and 96 members, a mesh at
+    # k 96; there "auto" stays on the Jacobi kernel where it runs.  For information, k 64 p 153: 12.56 ms against dense64's
+    # 28.35 ms (the resident image leaves one workgroup a compute unit, the ring three); "auto" keeps dense64's rule at k <= 64.
+    # "auto" never takes the route at k <= 64 (dense64 has those shapes under its own rule); method="stream64" names it
+    # everywhere the kernel covers
+    STREAM64_AUTO_MIN_K = 65
+    STREAM64_AUTO_NUM, STREAM64_AUTO_DEN = 173, 80
+    STREAM64_AUTO_MAX_ROWS = 8
+    JACOBI_MAX_LDS = 160 * 1024 - 1024           # kMaxDynamicLds (csrc/mia_common.h)
+
+    @staticmethod
+    def _jacobi_primal_fits(k: int, p_max: int) -> bool:
+        """Restates wave_lds_bytes (csrc/letkf_wave.hip) for float64 in the primal form (p_max > k, no weights): whether the
+        Jacobi kernel can hold a point's two k x (k + 1) matrices.  It can up to 96 members (162 104 bytes at p_max 256) and
+        cannot from 97 on, where mia_letkf_analysis_packed_f64 answers MIA_ERR_UNSUPPORTED."""
+        nmax = max((k + 1) & ~1, 2)
+        pl = (p_max + 3) & ~1
+        nb = nmax // 2
+        b = 8 * (2 * nmax * (nmax + 1) + 8 * nmax + 2 * k + 8 + pl) + 4 * pl + 16 + 2 * ((nb * (nb - 1) // 2 + 7) & ~7)
+        return (b + 15) // 16 * 16 <= LetkfEngine.JACOBI_MAX_LDS
+
+    def _stream64_auto(self, m: int, k: int, p_max: int) -> bool:
+        if k < self.STREAM64_AUTO_MIN_K:
+            return False
+        if not self._jacobi_primal_fits(k, p_max):
+            return True
+        return self.STREAM64_AUTO_DEN * p_max <= self.STREAM64_AUTO_NUM * k and m <= self.STREAM64_AUTO_MAX_ROWS
+
     # method="auto" hands a float64 analysis with rbf_gamma to the RBF tile route (csrc/lketkf_tile64.hip) only for
     # k >= RBF64_AUTO_MIN_K and either ONE state row with p_max <= RBF64_AUTO_MAX_P or up to RBF64_AUTO_MAX_ROWS state rows with
     # p_max <= RBF64_AUTO_MAX_P_ROWS (and k <= 40: the kernel's cover).  Measured on MI355X (tools/time_rbf64.py,
@@ -643,11 +687,15 @@ class LetkfEngine:
         the same route in float64 on tiles of sixteen points (2 <= k <= 64, p_max <= k, plain ETKF core,
         no weights); "dense64" = its primal form for dense local networks (2 <= k <= 64, k < p_max <= 256 slots, same
         conditions); "wide64" = matfun64's analysis with a tile's union split over two or four wavefronts (2 <= k <= 128,
-        p_max <= k, same conditions; what ensembles of 65 .. 128 members run); "rbf64" = the RBF-kernelised core in float64 on
+        p_max <= k, same conditions; what ensembles of 65 .. 128 members run); "stream64" = dense64's analysis with the union's
+        records streamed through a ring in LDS instead of a resident image (2 <= k <= 128, k < p_max <= 256, same conditions;
+        what dense networks of 65 .. 128 members run -- "auto" takes it from STREAM64_AUTO_MIN_K members on wherever the Jacobi
+        kernel cannot hold the shape, k >= 97, and elsewhere only inside STREAM64_AUTO_*; a point it declines is redone by the
+        Jacobi kernel, and at k >= 97 that redo raises MiaError AFTER the other points have been written, as below); "rbf64" = the RBF-kernelised core in float64 on
         tiles (``rbf_gamma`` given, 2 <= k <= 40, lists of at most 64 observations -- no p_max <= k condition --, no
         ``kernel_program``, no weights; csrc/lketkf_tile64.hip); "kern64" = the same kernel with K from a ``kernel_program``
         (float64, the cover of rbf64, ``kernel_psd=True``, no tanh / sin, no weights; csrc/lketkf_kern64.hip); "auto" picks
-        matfun / matfun64 / dense64 / wide64 / rbf64 / kern64 by
+        matfun / matfun64 / dense64 / wide64 / stream64 / rbf64 / kern64 by
         the state's dtype, the core and the shape when one applies (dense64 only while p_max <= 2.4 k and m <= 8, see
         DENSE64_AUTO_NUM; wide64 only from WIDE64_AUTO_MIN_K members and up to WIDE64_AUTO_MAX_ROWS state rows -- below
         65 members matfun64 has taken the shape already; rbf64 from RBF64_AUTO_MIN_K members, with one state row while
@@ -685,8 +733,8 @@ class LetkfEngine:
             self._keep_rec = rec      # (a record buffer packed during HIP-graph capture must outlive the capture)
         if rec.dtype != dtype or rec.shape[1] != (k + 1 + 3) // 4 * 4:
             raise ValueError("packed records do not match the state's dtype / ensemble size")
-        if method not in ("auto", "eig", "matfun", "matfun64", "dense64", "wide64", "rbf64", "kern64"):
-            raise ValueError("method must be 'auto', 'eig', 'matfun', 'matfun64', 'dense64', 'wide64', 'rbf64' or 'kern64'")
+        if method not in ("auto", "eig", "matfun", "matfun64", "dense64", "wide64", "stream64", "rbf64", "kern64"):
+            raise ValueError("method must be 'auto', 'eig', 'matfun', 'matfun64', 'dense64', 'wide64', 'stream64', 'rbf64' or 'kern64'")
         # float64 RBF-kernelised filter on tiles (csrc/lketkf_tile64.hip): 2 <= k <= 40, lists of at most 64 observations, no weights
         can_rbf64 = dtype == torch.float64 and not return_weights and rbf_gamma is not None and kernel_program is None
         if method == "rbf64" and not can_rbf64:
@@ -775,10 +823,11 @@ class LetkfEngine:
         if method == "matfun" and not can_matfun:
             raise ValueError("the matfun route needs float32 and cannot return the weights")
         # float64 on tiles (csrc/letkf_tile64.hip: p_max <= k <= 64; csrc/letkf_dense64.hip: p_max > k; csrc/letkf_wide64.hip:
-        # p_max <= k <= 128): plain ETKF core, no weights.  "auto" tries the three in this order (the dense one up to
-        # p_max = 2.4 k, the wide one under WIDE64_AUTO_*) and falls back to the Jacobi kernel elsewhere; "matfun64", "dense64"
-        # and "wide64" name one route and raise there instead.
-        tile64_methods = ("matfun64", "dense64", "wide64")
+        # p_max <= k <= 128; csrc/letkf_stream64.hip: k < p_max <= 256, k <= 128): plain ETKF core, no weights.  "auto" tries the
+        # four in this order (the dense one up to p_max = 2.4 k, the wide one under WIDE64_AUTO_*, the streamed one under
+        # STREAM64_AUTO_*) and falls back to the Jacobi kernel elsewhere; "matfun64", "dense64", "wide64" and "stream64" name
+        # one route and raise there instead.
+        tile64_methods = ("matfun64", "dense64", "wide64", "stream64")
         can_matfun64 = dtype == torch.float64 and not return_weights and rbf_gamma is None
         if method in tile64_methods and not can_matfun64:
             raise ValueError("the %s route needs float64, the plain ETKF core and cannot return the weights" % method)
@@ -799,6 +848,10 @@ class LetkfEngine:
             if rc == -3 and wide_ok:
                 name = "mia_letkf_analysis_wide_f64"
                 rc = self.lib.mia_letkf_analysis_wide_f64(*args, _ptr(flags), _ptr(retry), self._stream())
+            stream_ok = method == "stream64" or (method == "auto" and self._stream64_auto(m, k, nbrs.p_max))
+            if rc == -3 and stream_ok:
+                name = "mia_letkf_analysis_stream_f64"
+                rc = self.lib.mia_letkf_analysis_stream_f64(*args, _ptr(flags), _ptr(retry), self._stream())
             if rc == -3 and method == "auto":      # shape outside the tile kernels (or tile = 0): the Jacobi kernel below
                 pass
             else:

@@ -59,7 +59,9 @@ class ETKF:
         # analysis then runs on a float64 tile kernel (per-point lists, every product on the matrix cores): csrc/letkf_tile64.hip
         # while no point sees more observations than there are members, csrc/letkf_dense64.hip for dense networks (k < p_max <= 2.4 k, m <= 8,
         # LetkfEngine.DENSE64_AUTO_NUM), csrc/letkf_wide64.hip for ensembles of 65 .. 128 members (p_max <= k, m <= 8,
-        # LetkfEngine.WIDE64_AUTO_*); on the Jacobi kernel everywhere else.  An explicit dtype=torch.float32 chooses the
+        # LetkfEngine.WIDE64_AUTO_*), csrc/letkf_stream64.hip for dense networks of 65 .. 128 members (k < p_max <= 256: wherever the
+        # Jacobi kernel cannot hold the shape, 97 members and more, and below that inside LetkfEngine.STREAM64_AUTO_*); on the Jacobi
+        # kernel everywhere else.  An explicit dtype=torch.float32 chooses the
         # float32 tile kernels and the step driver -- the benchmarked hot path
         self._dtype = torch.float64
         self.dtype = dtype
@@ -385,7 +387,7 @@ class LETKF(ETKF):
         applies: float32, a built-in distance, a shape the kernels take (mia_letkf_tiles_cover).  Declined points are redone by
         the eigensolver kernel from the per-point lists.  Returns (Xa, flags) or None: the caller takes the per-point route
         (float64, the default dtype: ``engine.analysis(method="auto")`` forms the tiles' unions itself from the per-point lists of
-        any metric and runs letkf_tile64_kernel, or letkf_dense64_kernel where k < p_max <= 2.4 k, or letkf_wide64_kernel for 65 .. 128 members with p_max <= k; with an RBF / Gauss kernel
+        any metric and runs letkf_tile64_kernel, or letkf_dense64_kernel where k < p_max <= 2.4 k, or letkf_wide64_kernel for 65 .. 128 members with p_max <= k, or letkf_stream64_kernel for 65 .. 128 members with k < p_max <= 256 (LetkfEngine.STREAM64_AUTO_*); with an RBF / Gauss kernel
         it runs lketkf_tile64_kernel for RBF64_AUTO_MIN_K <= k <= 40 with one state row and p_max <= RBF64_AUTO_MAX_P, or up to
         RBF64_AUTO_MAX_ROWS state rows and p_max <= RBF64_AUTO_MAX_P_ROWS; with any other positive semidefinite kernel expression
         (``kernels.kernel_is_psd``) it runs lketkf_tile64_kernel<UT, NR, ST> for KERN64_AUTO_MIN_K <= k <= 40 with one state row and
