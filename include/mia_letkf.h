@@ -452,6 +452,42 @@ int mia_letkf_analysis_dense_f64(const double* X, int64_t ldx, int m, int k, int
                                  void* stream);
 int mia_letkf_dense_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P);
 
+/* The analysis of mia_letkf_analysis_dense_f64 with the sixteen points of a tile taken from a MAP (csrc/letkf_patch64.hip; what
+ * it replaces per point is unchanged: the decomposition and weights of core/etkf.py:57-77, the gather of
+ * interface/wrapper.py:86-98, the transform of interface/base.py:257-278).  On a row-major 2-D mesh sixteen consecutive points
+ * are a 16 x 1 strip whose lists have a far larger union than those of a 4 x 4 patch; with a map of patches the union fits one
+ * record image and a tile runs in one pass.  tile_pts [n_tiles][16] int32: tile_pts[16 t + s] is the point of slot s of tile t
+ * as an index into [0, g1 - g0), or -1 for an empty slot; every point of the range must occur exactly once
+ * (mia_letkf_tile_union_census checks it; this entry trusts the map except that an entry outside the range is treated as
+ * empty).  union_blocks: sixteen-slot blocks of the record image in LDS, 1 <= union_blocks <= the capacity at this ensemble
+ * size (16, fewer where 256 records of k + 1 doubles do not fit: 14 at k = 64); a tile whose union exceeds it runs in halves
+ * of its slots, a single list longer than 16 union_blocks is MIA_FLAG_OVERFLOW and NaN output.  Lists, flags and outputs stay
+ * in natural point order, so declined points are redone by mia_letkf_analysis_retry_f64 unchanged.  A point's bits are those
+ * of mia_letkf_analysis_dense_f64 under any map.  Validation before any launch, in the order of
+ * mia_letkf_analysis_dense_f64, n_tiles < 0 and union_blocks < 1 among the sizes (MIA_ERR_SIZE), tile_pts among the pointers
+ * (MIA_ERR_NULL), n_tiles == 0 for a non-empty range MIA_ERR_SIZE; outside the cover, with gamma > 0 or the option "tile" = 0
+ * MIA_ERR_UNSUPPORTED; union_blocks above the capacity MIA_ERR_SIZE.
+ * mia_letkf_patch_f64_cover: mia_letkf_dense_f64_cover's answer (host only, no device work).
+ * mia_letkf_tile_union_census: validates a map and counts the largest union of a tile's lists, one wavefront per tile.
+ * out2 (device, 2 int32): [0] = 0 or a sum of MIA_TILEMAP_*, [1] = the largest number of distinct observation indices in
+ * the lists of one tile (0 with count_unions = 0, which leaves the validation).  Lists are read for valid entries only, at
+ * most min(p_max, p_cap, 256) entries of each.  ws: device, at least 4 (n_points + 2) bytes, 4-byte aligned; the entry
+ * zeroes it.  n_tiles == 0 for n_points > 0 is answered MIA_TILEMAP_MISSING without a launch being possible, so it returns
+ * MIA_ERR_SIZE. */
+#define MIA_TILEMAP_RANGE 1   /* an entry outside [-1, n_points) */
+#define MIA_TILEMAP_TWICE 2   /* a point occurs more than once */
+#define MIA_TILEMAP_MISSING 4 /* a point of [0, n_points) does not occur */
+int mia_letkf_analysis_patch_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
+                                 const double* rec, int64_t P,
+                                 const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w,
+                                 int p_cap, int p_max, double inf_factor, double gamma,
+                                 double* Xa, int64_t ldo, int64_t o0, int32_t* flags, int32_t* retry_count,
+                                 const int32_t* tile_pts, int64_t n_tiles, int union_blocks, void* stream);
+int mia_letkf_patch_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P);
+int mia_letkf_tile_union_census(const int32_t* tile_pts, int64_t n_tiles, int64_t n_points,
+                                const int32_t* nbr_cnt, const int32_t* nbr_idx, int p_cap, int p_max, int count_unions,
+                                int32_t* out2, void* ws, size_t ws_bytes, void* stream);
+
 /* The analysis of mia_letkf_analysis_dense_f64 for DENSE local networks of ensembles up to 128 members
  * (csrc/letkf_stream64.hip; what it replaces per point: the gather and sqrt(rho) scaling of interface/wrapper.py:86-98, the
  * decomposition and weights of core/etkf.py:57-103, the transform of interface/base.py:257-278).  The same mathematics,

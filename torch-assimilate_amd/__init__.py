@@ -9,7 +9,7 @@ from ._cabi import MiaError, EXPORTED_SYMBOLS  # noqa: F401
 __version__ = "0.1.0"
 
 _LAZY = {
-    "LetkfEngine": "engine", "NeighbourLists": "engine",
+    "LetkfEngine": "engine", "NeighbourLists": "engine", "mesh_tiles": "engine",
     "GaspariCohn": "localization", "EuclideanMetric": "localization", "AbsoluteDistance": "localization",
     "PeriodicMetric": "localization",
     "ETKFModule": "core", "KETKFModule": "core",

@@ -61,6 +61,10 @@ _PROTOS = {
     "mia_letkf_analysis_dense_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
                                       vp, i64, i64, vp, vp, vp], i32),
     "mia_letkf_dense_f64_cover": ([i32, i32, i32, i64, i64, i64, i64], i32),
+    "mia_letkf_analysis_patch_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
+                                      vp, i64, i64, vp, vp, vp, i64, i32, vp], i32),
+    "mia_letkf_patch_f64_cover": ([i32, i32, i32, i64, i64, i64, i64], i32),
+    "mia_letkf_tile_union_census": ([vp, i64, i64, vp, vp, i32, i32, i32, vp, vp, sz, vp], i32),
     "mia_letkf_analysis_stream_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
                                        vp, i64, i64, vp, vp, vp], i32),
     "mia_letkf_stream_f64_cover": ([i32, i32, i32, i64, i64, i64, i64], i32),

@@ -327,6 +327,47 @@ extern "C" int mia_letkf_dense_f64_cover(int m, int k, int p_max, int64_t ldx, i
   if (P < 0) return 0;
   return dense64_route_covers(m, k, p_max, ldx, ldo, n_points) ? 1 : 0;
 }
+// the dense route with a tile map and a caller-sized record image (letkf_patch64.hip): the same validation with the map's
+// arguments among the sizes and pointers, then the one kernel of the route
+extern "C" int mia_letkf_analysis_patch_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
+                                            const double* rec, int64_t P, const int32_t* nbr_cnt,
+                                            const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                                            double inf_factor, double gamma, double* Xa, int64_t ldo, int64_t o0,
+                                            int32_t* flags, int32_t* retry_count, const int32_t* tile_pts, int64_t n_tiles,
+                                            int union_blocks, void* stream) {
+  (void)hipGetLastError();
+  if (g1 < g0 || g0 < 0 || m < 1 || k < 2 || P < 0 || p_cap < 1 || p_max < 0 || n_tiles < 0 || union_blocks < 1) return MIA_ERR_SIZE;
+  if (!(inf_factor > 0.0)) return MIA_ERR_SIZE;
+  if (gamma > 0.0) return MIA_ERR_UNSUPPORTED;       // the float64 RBF filter stays on mia_letkf_analysis_packed_f64
+  const int64_t ng = g1 - g0;
+  if (ng == 0) return MIA_OK;
+  if (!X || !Xa || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count || !tile_pts) return MIA_ERR_NULL;
+  if (ldx < g1 || ldo < o0 + ng || n_tiles == 0) return MIA_ERR_SIZE;
+  if (p_max > p_cap) p_max = p_cap;
+  if (P > 0 && !rec) return MIA_ERR_NULL;
+  return patch64_analysis_launch(X, ldx, m, k, g0, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, Xa, ldo, o0,
+                                 flags, retry_count, tile_pts, n_tiles, union_blocks, (hipStream_t)stream);
+}
+extern "C" int mia_letkf_patch_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P) {
+  if (P < 0) return 0;
+  return dense64_route_covers(m, k, p_max, ldx, ldo, n_points) ? 1 : 0;
+}
+extern "C" int mia_letkf_tile_union_census(const int32_t* tile_pts, int64_t n_tiles, int64_t n_points, const int32_t* nbr_cnt,
+                                           const int32_t* nbr_idx, int p_cap, int p_max, int count_unions, int32_t* out2,
+                                           void* ws, size_t ws_bytes, void* stream) {
+  (void)hipGetLastError();
+  if (n_tiles < 0 || n_points < 0 || p_cap < 1 || p_max < 0) return MIA_ERR_SIZE;
+  if (n_points > 0 && n_tiles == 0) return MIA_ERR_SIZE;
+  if (!out2 || !ws || (n_tiles > 0 && !tile_pts) || (count_unions && n_tiles > 0 && (!nbr_cnt || !nbr_idx))) return MIA_ERR_NULL;
+  if (ws_bytes / sizeof(int32_t) < (size_t)n_points + 2) return MIA_ERR_WORKSPACE;
+  if (((uintptr_t)ws) & 3) return MIA_ERR_ALIGN;
+  if (n_tiles == 0) {                                 // (an empty range with an empty map: nothing wrong, no union)
+    MIA_HIP_TRY(hipMemsetAsync(out2, 0, 2 * sizeof(int32_t), (hipStream_t)stream));
+    return MIA_OK;
+  }
+  return tile_union_census_launch(tile_pts, n_tiles, n_points, nbr_cnt, nbr_idx, p_cap, p_max, count_unions ? 1 : 0, out2,
+                                  (int32_t*)ws, (hipStream_t)stream);
+}
 // float64 on tiles for dense local networks of up to 128 members, the union's records streamed (letkf_stream64.hip): the same
 // validation, then the one kernel of the route
 extern "C" int mia_letkf_analysis_stream_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,

@@ -14,7 +14,7 @@ import torch
 
 from . import _cabi
 
-__all__ = ["LetkfEngine", "NeighbourLists", "ObsIndex"]
+__all__ = ["LetkfEngine", "NeighbourLists", "ObsIndex", "mesh_tiles"]
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -22,6 +22,36 @@ def _ptr(t: Optional[torch.Tensor]):
 
 
 MIA_FLAG_NOCONV = 2     # include/mia_letkf.h
+MIA_TILEMAP_FAULTS = ((1, "an entry outside [-1, n)"), (2, "a point that occurs more than once"),
+                      (4, "a point that does not occur"))     # MIA_TILEMAP_* (include/mia_letkf.h)
+
+
+def mesh_tiles(mesh_shape, g0: int = 0, g1: Optional[int] = None, patch=(4, 4)) -> torch.Tensor:
+    """Tile map of a row-major ``(ny, nx)`` mesh for ``LetkfEngine.analysis(..., tile_points=...)``: one tile of sixteen slots
+    per ``patch`` (4 x 4, 2 x 8 or 8 x 2 points: rows x columns) restricted to the points ``[g0, g1)`` of the mesh, int32
+    ``(n_tiles, 16)`` on the host.  Slots are row-major inside the patch; an entry is the point's index relative to ``g0``, or
+    -1 where the patch leaves the mesh or the shard.  Patches without a point of the shard are left out; tiles follow the
+    patches row by row, so consecutive tiles are neighbours and share observations."""
+    ny, nx = (int(v) for v in mesh_shape)
+    py, px = (int(v) for v in patch)
+    if ny < 1 or nx < 1:
+        raise ValueError("mesh_shape must be (ny, nx) with positive sizes")
+    if py < 1 or px < 1 or py * px != 16:
+        raise ValueError("patch must have sixteen points: (4, 4), (2, 8), (8, 2), ...")
+    G = ny * nx
+    g1 = G if g1 is None else int(g1)
+    g0 = int(g0)
+    if not 0 <= g0 <= g1 <= G:
+        raise ValueError("[g0, g1) must lie inside the mesh")
+    if g0 == g1:
+        return torch.empty((0, 16), dtype=torch.int32)
+    ty, tx = (ny + py - 1) // py, (nx + px - 1) // px
+    row = torch.arange(ty)[:, None, None, None] * py + torch.arange(py)[None, None, :, None]      # (ty, 1, py, 1)
+    col = torch.arange(tx)[None, :, None, None] * px + torch.arange(px)[None, None, None, :]      # (1, tx, 1, px)
+    pt = (row * nx + col).reshape(ty * tx, 16)
+    ok = ((row < ny) & (col < nx)).reshape(ty * tx, 16) & (pt >= g0) & (pt < g1)
+    tiles = torch.where(ok, pt - g0, torch.full_like(pt, -1))
+    return tiles[ok.any(dim=1)].to(torch.int32).contiguous()
 
 
 def _read_solve_flags(flags: torch.Tensor) -> int:
@@ -47,6 +77,7 @@ class NeighbourLists:
     g1: int
     stats: Optional[torch.Tensor] = None   # device [max count, #truncated]; set when the read-back was deferred
     observed_p_max: Optional[int] = None
+    tile_census: Optional[dict] = None     # id(tile map) -> (the map, its device copy, largest union or None): LetkfEngine.analysis
 
     def confirm(self) -> bool:
         """Deferred check of an assumed ``p_max`` (host sync): True when every list fitted."""
@@ -668,6 +699,71 @@ class LetkfEngine:
     KERN64_AUTO_MAX_ROWS = 1
     KERN64_AUTO_MAX_P = 21
 
+    # method="auto" hands a float64 shape with p_max > k to the dense route under a tile map (csrc/letkf_patch64.hip) only when
+    # the caller gives ``tile_points``, and then only for ONE state row, PATCH64_AUTO_MIN_K <= k (<= 64: the cover),
+    # PATCH64_AUTO_DEN * p_max <= PATCH64_AUTO_NUM * k and a largest union (the census' count) that fits the record image, so that
+    # every tile runs in one pass.  Measured on MI355X (tools/time_patch64.py, profiles/patch64_time.json), 316 x 316
+    # meshes in 4 x 4 patches, against the Jacobi kernel, census (0.15 - 0.24 ms) inside the call, median ms:
+    #   k 40 p 101 (DESIGN 9's failing row: dense64 on strips 61.7, 1.1x):  3.35x (67.63 / 20.18)     8 state rows: 0.67x (74.1 / 111.4) LOSES
+    #   k 20 p  45:  4.30x (9.53 / 2.22)      k 64 p 101: 10.97x (240.5 / 21.9)      k 40 p 76, observations at every 2nd point: 12.5x (70.2 / 5.61)
+    # Every one-row case passes the factor 2 beyond both spreads (all below 0.2 ms); with eight rows the route loses, because a
+    # further row costs 13.0 ms here and 0.93 ms on the Jacobi kernel -- at two rows the factor would be near 2.06, which is not
+    # a margin, and nothing between 1 and 8 rows was measured.  So: one row, from the smallest measured ensemble (20; the KT = 1
+    # instantiation was not timed) and up to the largest measured p_max / k (101 / 40).  Outside, with a map, "auto" goes on to
+    # dense64's own rule and the Jacobi kernel as before; method="patch64" names the route everywhere the kernel covers.  The
+    # rule cannot see whether a map is a good one (tiles of neighbouring points): the union condition is what stands in for it
+    PATCH64_AUTO_MIN_K = 20
+    PATCH64_AUTO_NUM, PATCH64_AUTO_DEN = 101, 40
+    PATCH64_AUTO_MAX_ROWS = 1
+
+    def _patch64_auto(self, m: int, k: int, p_max: int) -> bool:
+        return (m <= self.PATCH64_AUTO_MAX_ROWS and k >= self.PATCH64_AUTO_MIN_K
+                and self.PATCH64_AUTO_DEN * p_max <= self.PATCH64_AUTO_NUM * k)
+
+    @staticmethod
+    def _dense64_capacity_blocks(k: int) -> int:
+        """Restates dense64_capacity_blocks / patch64_capacity_blocks (csrc): sixteen-slot blocks of the record image that fit
+        the LDS at this ensemble size."""
+        ks = ((k + 1 + 3) // 4 * 4) | 1
+        ub = 16
+        while ub > 0 and ((16 * ub * ks + 16 * (16 * ub + 1)) * 8 + 16 * ub * 4 + 15) // 16 * 16 > LetkfEngine.JACOBI_MAX_LDS:
+            ub -= 1
+        return ub
+
+    def _patch64_map(self, nbrs: NeighbourLists, tile_points: torch.Tensor, union_blocks: Optional[int], k: int):
+        """The device copy of a tile map and the blocks of the record image for it.  The map is validated by
+        tile_union_census_kernel (every tile) and, with ``union_blocks=None``, the largest union of a tile counted; both come
+        back in one 8-byte read.  The result is kept on ``nbrs`` under the map's identity, so a cycled filter pays once per
+        geometry.  ValueError for a map that is not a partition of the shard's points, before any analysis launch.  Returns
+        (map on the device, blocks, whether every tile fits the image in one pass -- True when the caller named the blocks)."""
+        n = nbrs.g1 - nbrs.g0
+        if (not isinstance(tile_points, torch.Tensor) or tile_points.dtype != torch.int32 or tile_points.dim() != 2
+                or tile_points.shape[1] != 16):
+            raise ValueError("tile_points must be an int32 tensor (n_tiles, 16)")
+        cap = self._dense64_capacity_blocks(k)
+        if union_blocks is not None and not 1 <= int(union_blocks) <= cap:
+            raise ValueError("union_blocks must lie in 1 .. %d at k = %d" % (cap, k))
+        if nbrs.tile_census is None:
+            nbrs.tile_census = {}
+        ent = nbrs.tile_census.get(id(tile_points))
+        if ent is None or ent[0] is not tile_points or (union_blocks is None and ent[2] is None):
+            if tile_points.shape[0] == 0:
+                raise ValueError("invalid tile map: a point that does not occur (the map is empty)")
+            tp = tile_points.to(self.device).contiguous() if ent is None or ent[0] is not tile_points else ent[1]
+            out2 = torch.empty(2, dtype=torch.int32, device=self.device)
+            ws = self._workspace("tile_census", 4 * (n + 2))
+            _cabi.check(self.lib.mia_letkf_tile_union_census(_ptr(tp), tp.shape[0], n, _ptr(nbrs.cnt), _ptr(nbrs.idx), nbrs.p_cap,
+                                                             nbrs.p_max, 1 if union_blocks is None else 0, _ptr(out2), _ptr(ws),
+                                                             ws.numel() * ws.element_size(), self._stream()),
+                        "mia_letkf_tile_union_census")
+            err, umax = (int(v) for v in out2.tolist())      # host sync (8 bytes)
+            if err:
+                raise ValueError("invalid tile map: " + ", ".join(t for b, t in MIA_TILEMAP_FAULTS if err & b))
+            ent = (tile_points, tp, umax if union_blocks is None else None)
+            nbrs.tile_census[id(tile_points)] = ent
+        ub = int(union_blocks) if union_blocks is not None else min(max((ent[2] + 15) // 16, 1), cap)
+        return ent[1], ub, union_blocks is not None or ent[2] <= 16 * cap
+
     def _kern64_auto(self, m: int, k: int, p_max: int) -> bool:
         return k >= self.KERN64_AUTO_MIN_K and m <= self.KERN64_AUTO_MAX_ROWS and p_max <= self.KERN64_AUTO_MAX_P
 
@@ -676,7 +772,8 @@ class LetkfEngine:
                  rbf_gamma: Optional[float] = None, out: Optional[torch.Tensor] = None, out_offset: int = 0,
                  return_flags: bool = False, rec: Optional[torch.Tensor] = None, method: str = "auto",
                  defer_retry: bool = False, retry: Optional[torch.Tensor] = None,
-                 flags: Optional[torch.Tensor] = None, kernel_program=None, kernel_psd: bool = False):
+                 flags: Optional[torch.Tensor] = None, kernel_program=None, kernel_psd: bool = False,
+                 tile_points: Optional[torch.Tensor] = None, union_blocks: Optional[int] = None):
         """X (m, k, G) prior ensemble (grid fastest), Yb (k, P), d (P,) [or their packed records
         ``rec`` from :meth:`pack_obs`]: analysis of the shard described by ``nbrs``.
         Returns Xa (m, k, n) [, W (n, k, k)] [, flags (n,)].
@@ -686,7 +783,13 @@ class LetkfEngine:
         state rows, no weights), with the eigensolver redoing the grid points it declines; "matfun64" =
         the same route in float64 on tiles of sixteen points (2 <= k <= 64, p_max <= k, plain ETKF core,
         no weights); "dense64" = its primal form for dense local networks (2 <= k <= 64, k < p_max <= 256 slots, same
-        conditions); "wide64" = matfun64's analysis with a tile's union split over two or four wavefronts (2 <= k <= 128,
+        conditions); "patch64" = dense64's analysis with the sixteen points of a tile taken from ``tile_points`` (int32
+        (n_tiles, 16): indices into the shard's points, -1 = empty slot, every point exactly once -- :func:`mesh_tiles` makes the
+        4 x 4 patches of a 2-D mesh, any other partition is legal; an invalid map raises ValueError before the analysis is
+        launched) and the record image sized for the largest union of a tile (``union_blocks=None``: counted on the GPU once per
+        map and kept on ``nbrs``; an int names the sixteen-slot blocks and leaves the count, not the validation); same cover and
+        conditions as dense64, the same bits, csrc/letkf_patch64.hip; "auto" takes it only when ``tile_points`` is given and
+        only under PATCH64_AUTO_* (one state row, 20 <= k, p_max <= 2.525 k, unions that fit the image), and without ``tile_points`` every call is what it was; "wide64" = matfun64's analysis with a tile's union split over two or four wavefronts (2 <= k <= 128,
         p_max <= k, same conditions; what ensembles of 65 .. 128 members run); "stream64" = dense64's analysis with the union's
         records streamed through a ring in LDS instead of a resident image (2 <= k <= 128, k < p_max <= 256, same conditions;
         what dense networks of 65 .. 128 members run -- "auto" takes it from STREAM64_AUTO_MIN_K members on wherever the Jacobi
@@ -733,8 +836,11 @@ class LetkfEngine:
             self._keep_rec = rec      # (a record buffer packed during HIP-graph capture must outlive the capture)
         if rec.dtype != dtype or rec.shape[1] != (k + 1 + 3) // 4 * 4:
             raise ValueError("packed records do not match the state's dtype / ensemble size")
-        if method not in ("auto", "eig", "matfun", "matfun64", "dense64", "wide64", "stream64", "rbf64", "kern64"):
-            raise ValueError("method must be 'auto', 'eig', 'matfun', 'matfun64', 'dense64', 'wide64', 'stream64', 'rbf64' or 'kern64'")
+        if method not in ("auto", "eig", "matfun", "matfun64", "dense64", "patch64", "wide64", "stream64", "rbf64", "kern64"):
+            raise ValueError("method must be 'auto', 'eig', 'matfun', 'matfun64', 'dense64', 'patch64', 'wide64', 'stream64', "
+                             "'rbf64' or 'kern64'")
+        if method == "patch64" and tile_points is None:
+            raise ValueError("the patch64 route needs tile_points (see mesh_tiles)")
         # float64 RBF-kernelised filter on tiles (csrc/lketkf_tile64.hip): 2 <= k <= 40, lists of at most 64 observations, no weights
         can_rbf64 = dtype == torch.float64 and not return_weights and rbf_gamma is not None and kernel_program is None
         if method == "rbf64" and not can_rbf64:
@@ -827,7 +933,7 @@ class LetkfEngine:
         # four in this order (the dense one up to p_max = 2.4 k, the wide one under WIDE64_AUTO_*, the streamed one under
         # STREAM64_AUTO_*) and falls back to the Jacobi kernel elsewhere; "matfun64", "dense64", "wide64" and "stream64" name
         # one route and raise there instead.
-        tile64_methods = ("matfun64", "dense64", "wide64", "stream64")
+        tile64_methods = ("matfun64", "dense64", "patch64", "wide64", "stream64")
         can_matfun64 = dtype == torch.float64 and not return_weights and rbf_gamma is None
         if method in tile64_methods and not can_matfun64:
             raise ValueError("the %s route needs float64, the plain ETKF core and cannot return the weights" % method)
@@ -839,6 +945,15 @@ class LetkfEngine:
             rc, name = -3, "mia_letkf_analysis_matfun_f64"
             if method in ("auto", "matfun64"):
                 rc = self.lib.mia_letkf_analysis_matfun_f64(*args, _ptr(flags), _ptr(retry), self._stream())
+            patch_ok = tile_points is not None and (method == "patch64" or (
+                method == "auto" and self._patch64_auto(m, k, nbrs.p_max)))
+            if rc == -3 and patch_ok:
+                name = "mia_letkf_analysis_patch_f64"
+                if self.lib.mia_letkf_patch_f64_cover(m, k, nbrs.p_max, G, ldo, n, P) == 1:
+                    tp, ub, fits = self._patch64_map(nbrs, tile_points, union_blocks, k)
+                    if fits or method == "patch64":      # ("auto": a map whose tiles would run in parts is left to the rules below)
+                        rc = self.lib.mia_letkf_analysis_patch_f64(*args, _ptr(flags), _ptr(retry), _ptr(tp), tp.shape[0], ub,
+                                                                   self._stream())
             dense_ok = method == "dense64" or (method == "auto" and self.DENSE64_AUTO_DEN * nbrs.p_max <= self.DENSE64_AUTO_NUM * k and
                                                m <= self.DENSE64_AUTO_MAX_ROWS)
             if rc == -3 and dense_ok:
@@ -858,7 +973,7 @@ class LetkfEngine:
                 _cabi.check(rc, name)
                 use_matfun = True
 
-                def finish():
+                def finish(_alive=(X, rec, out, nbrs)):   # (args holds addresses: a deferred redo must find the arrays alive)
                     n_retry = int(retry.item())          # host sync (8 bytes)
                     if n_retry:
                         _cabi.check(self.lib.mia_letkf_analysis_retry_f64(*args, _ptr(flags), self._stream()),

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from ._cabi import MiaError
-from .engine import LetkfEngine, warn_if_noconv
+from .engine import LetkfEngine, mesh_tiles, warn_if_noconv
 from .kernels import kernel_is_psd, kernel_route
 from .localization import GaspariCohn
 
@@ -191,12 +191,31 @@ class LETKF(ETKF):
     def __init__(self, localization: Optional[GaspariCohn] = None, inf_factor: float = 1.0,
                  smoother: bool = False, gpu: bool = True, pre_transform=None, post_transform=None,
                  chunksize: int = 10, weight_save_path=None, forward_model=None,
-                 dtype: torch.dtype = torch.float64, engine: Optional[LetkfEngine] = None):
+                 dtype: torch.dtype = torch.float64, engine: Optional[LetkfEngine] = None, mesh_shape=None):
         super().__init__(inf_factor=inf_factor, smoother=smoother, gpu=gpu, pre_transform=pre_transform,
                          post_transform=post_transform, weight_save_path=weight_save_path,
                          forward_model=forward_model, dtype=dtype, engine=engine)
         self.localization = localization
         self.chunksize = chunksize          # dask chunking of the reference; the GPU path does not chunk
+        # (ny, nx) of a row-major 2-D mesh the grid points form: the float64 analysis then hands the engine a tile map of
+        # 4 x 4 patches (engine.mesh_tiles), which the dense route takes under LetkfEngine.PATCH64_AUTO_*; the result is the
+        # same bit for bit.  Ignored (with a warning) when ny * nx is not the number of grid points; the weights paths, the
+        # kernelised filter and float32 never look at it
+        self.mesh_shape = None if mesh_shape is None else (int(mesh_shape[0]), int(mesh_shape[1]))
+        self._mesh_maps = {}
+
+    def _mesh_map(self, x, nb):
+        """The tile map of the shard's points on ``mesh_shape`` (built once per (g0, g1)), or None."""
+        if self.mesh_shape is None or x.dtype != torch.float64:
+            return None
+        if self.mesh_shape[0] * self.mesh_shape[1] != x.shape[-1]:
+            warnings.warn("mesh_shape %r does not have the state's %d grid points: ignored" % (self.mesh_shape, x.shape[-1]),
+                          RuntimeWarning)
+            return None
+        key = (nb.g0, nb.g1)
+        if key not in self._mesh_maps:
+            self._mesh_maps[key] = mesh_tiles(self.mesh_shape, nb.g0, nb.g1).to(self.engine.device)
+        return self._mesh_maps[key]
 
     @property
     def chunks(self):
@@ -450,7 +469,10 @@ class LETKF(ETKF):
         if res is not None:
             xa, flags = res
         else:
-            xa, flags = self.engine.analysis(st3, ybd, dd, nb, self.inf_factor, return_flags=True, **self._kernel_args())
+            ka = self._kernel_args()
+            if ka.get("rbf_gamma") is None and ka.get("kernel_program") is None:      # (the plain ETKF core: the kernelised
+                ka = dict(ka, tile_points=self._mesh_map(st3, nb))                    #  filter has no route that takes a map)
+            xa, flags = self.engine.analysis(st3, ybd, dd, nb, self.inf_factor, return_flags=True, **ka)
         bad = int((flags & 0xff).max().item()) if flags.numel() else 0
         if bad & 1:
             raise RuntimeError("LETKF kernel: local observation list overflow (engine bug: lists are sized from counts)")
