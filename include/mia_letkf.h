@@ -562,6 +562,38 @@ int mia_letkf_weights_wide_f64(const double* X /* may be NULL */, int64_t ldx, i
                                int32_t* flags, int32_t* retry_count, void* stream);
 int mia_letkf_weights_wide_f64_cover(int k, int p_max, int64_t n_points, int64_t P);
 
+/* The WEIGHTS of mia_letkf_weights_matfun_f64 for DENSE local networks, p_max > k, of ensembles up to 128 members
+ * (csrc/letkf_stream64w.hip; what it replaces per point: the gather and sqrt(rho) scaling of interface/wrapper.py:86-98, the
+ * decomposition and weights of core/etkf.py:57-103, the sum of interface/letkf.py:127-146).  The frame of
+ * mia_letkf_analysis_stream_f64 -- union, the records streamed through a ring of two sixteen-slot blocks, rhs, streamed
+ * Gershgorin bound, primal coefficient table (target exp(-26), margin 2, degree cap 127), degree and decline of every point
+ * are its own, bit for bit -- with one pass of the Chebyshev recurrence per MEMBER c < k on the unit vector e_c, which yields
+ * row c of the sixteen points' weights: W[g][c][j] = (psi(C_g) e_c) . rhs_g / reg + f0 (phi(C_g) e_c)_j.  Every sum over the
+ * union is one chain of v_mfma_f64_16x16x4_f64 in ascending slot order, so a point's bits do not depend on its tile, the
+ * shard boundary or the halving of a tile.
+ * mia_letkf_weights_stream_f64: argument list and validation order of mia_letkf_weights_matfun_f64 (X and Xa may be NULL,
+ * m >= 1 is checked all the same; W, flags and retry_count are required).  Shapes: 2 <= k <= 128 (k <= 64 is accepted so
+ * that the route can be compared with the Jacobi kernel), k < p_max <= 256, gamma <= 0; everything else -- p_max <= k
+ * included, which is mia_letkf_weights_matfun_f64's and mia_letkf_weights_wide_f64's -- returns MIA_ERR_UNSUPPORTED before
+ * any launch, as do the option "tile" = 0 and a coefficient table that cannot be had (stream being captured).  Declined points
+ * (degree above the cap 127): MIA_FLAG_RETRY, counted in *retry_count (device int32, zeroed by the caller), their k x k block
+ * of W untouched; mia_letkf_weights_retry_f64 redoes them on the Jacobi kernel, which holds a point's matrices in LDS and
+ * answers MIA_ERR_UNSUPPORTED from 97 members on: a declined point then fails AFTER every other point has been written -- a
+ * data-dependent limit, the one mia_letkf_analysis_stream_f64 has with mia_letkf_analysis_retry_f64.  A point without
+ * observations gets sqrt(inf_factor) I exactly and flag 0 (written directly: the truncated series at C = 0 is only about 1);
+ * the Chebyshev degree of every other written point is in bits 8-15 of its flag; MIA_FLAG_NONFINITE stays with the points
+ * that list a non-finite record; a list longer than p_max: MIA_FLAG_OVERFLOW and NaN weights for that point only.
+ * mia_letkf_weights_stream_f64_cover: 1 when the shape is inside the route (2 <= k <= 128, k < p_max <= 256, 16 k^2 8 < 2^31
+ * for the 32-bit offsets inside a tile's weights, the LDS of the launch, at most 65536 * 65535 tiles, n_points >= 0,
+ * P >= 0), 0 when not (host only, no device work). */
+int mia_letkf_weights_stream_f64(const double* X /* may be NULL */, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
+                                 const double* rec, int64_t P,
+                                 const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w,
+                                 int p_cap, int p_max, double inf_factor, double gamma,
+                                 double* Xa /* may be NULL */, int64_t ldo, int64_t o0, double* W /* [g1-g0][k][k] */,
+                                 int32_t* flags, int32_t* retry_count, void* stream);
+int mia_letkf_weights_stream_f64_cover(int k, int p_max, int64_t n_points, int64_t P);
+
 /* The float64 RBF-kernelised analysis on tiles (csrc/lketkf_tile64.hip): KETKFModule._estimate_weights (core/ketkf.py:65-94)
  * with RBFKernel(gamma) / GaussKernel (kernels/rbf.py:75-81,110-111) under wrapper_localization (interface/wrapper.py:86-98)
  * and the transform of interface/base.py:257-278, sixteen grid points per workgroup of four wavefronts, without an

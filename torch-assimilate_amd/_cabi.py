@@ -87,6 +87,9 @@ _PROTOS = {
     "mia_letkf_weights_wide_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
                                     vp, i64, i64, vp, vp, vp, vp], i32),
     "mia_letkf_weights_wide_f64_cover": ([i32, i32, i64, i64], i32),
+    "mia_letkf_weights_stream_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
+                                      vp, i64, i64, vp, vp, vp, vp], i32),
+    "mia_letkf_weights_stream_f64_cover": ([i32, i32, i64, i64], i32),
     "mia_letkf_weights_matfun_f32": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f32, f32,
                                       vp, i64, i64, vp, vp, vp, vp], i32),
     "mia_letkf_weights_retry_f32": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f32, f32,

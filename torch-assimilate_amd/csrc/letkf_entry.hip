@@ -548,6 +548,30 @@ extern "C" int mia_letkf_weights_wide_f64_cover(int k, int p_max, int64_t n_poin
   if (P < 0) return 0;
   return weights_wide64_route_covers(k, p_max, n_points) ? 1 : 0;
 }
+// float64 weights on tiles for dense local networks of up to 128 members (letkf_stream64w.hip): mia_letkf_weights_matfun_f64's
+// validation in its order, then the one kernel of the route
+extern "C" int mia_letkf_weights_stream_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
+                                            const double* rec, int64_t P, const int32_t* nbr_cnt,
+                                            const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                                            double inf_factor, double gamma, double* Xa, int64_t ldo, int64_t o0, double* W,
+                                            int32_t* flags, int32_t* retry_count, void* stream) {
+  (void)hipGetLastError();
+  if (g1 < g0 || g0 < 0 || m < 1 || k < 2 || P < 0 || p_cap < 1 || p_max < 0) return MIA_ERR_SIZE;
+  if (!(inf_factor > 0.0)) return MIA_ERR_SIZE;
+  if (gamma > 0.0) return MIA_ERR_UNSUPPORTED;       // the float64 RBF filter stays on mia_letkf_analysis_packed_f64
+  const int64_t ng = g1 - g0;
+  if (ng == 0) return MIA_OK;
+  if (!W || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
+  if ((X && ldx < g1) || (Xa && ldo < o0 + ng)) return MIA_ERR_SIZE;
+  if (p_max > p_cap) p_max = p_cap;
+  if (P > 0 && !rec) return MIA_ERR_NULL;
+  return weights_stream64_launch(k, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, W, flags, retry_count,
+                                 (hipStream_t)stream);
+}
+extern "C" int mia_letkf_weights_stream_f64_cover(int k, int p_max, int64_t n_points, int64_t P) {
+  if (P < 0) return 0;
+  return weights_stream64_route_covers(k, p_max, n_points) ? 1 : 0;
+}
 
 extern "C" int mia_letkf_analysis_matfun_fused_f32(const float* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
                                                    const float* rec, int64_t P, const double* grid_xyz, int n_coord,

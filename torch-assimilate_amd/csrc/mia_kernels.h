@@ -154,6 +154,16 @@ int weights_wide64_launch(int k, int64_t ng, const double* rec, const int32_t* n
                           const double* nbr_w, int p_cap, int p_max, double inf_factor, double* W, int32_t* flags,
                           int32_t* retry_count, hipStream_t stream);
 
+// letkf_stream64w.hip: the float64 WEIGHTS [ng][k][k] for dense local networks on letkf_stream64.hip's frame (primal form,
+// 2 <= k <= 128, k < p_max <= 256): one pass of the recurrence per member on e_c, the union's records streamed through the ring.
+// weights_stream64_route_covers: shape test (host only: the LDS of the launch, the launch grid, the 32-bit offsets inside a
+// tile's weights; false for p_max <= k, which is the dual routes'); weights_stream64_launch: MIA_ERR_UNSUPPORTED outside it,
+// with the option tile = 0, and when its coefficient table cannot be had.
+bool weights_stream64_route_covers(int k, int p_max, int64_t ng);
+int weights_stream64_launch(int k, int64_t ng, const double* rec, const int32_t* nbr_cnt, const int32_t* nbr_idx,
+                            const double* nbr_w, int p_cap, int p_max, double inf_factor, double* W, int32_t* flags,
+                            int32_t* retry_count, hipStream_t stream);
+
 // lienks_wide64.hip: lienks_tile64.hip's float64 IEnKS weight update with tau = 1 for ensembles up to 128 members on
 // letkf_wide64w.hip's frame (2 <= k <= 128, p_max <= k): the weights at inflation 1 with the innovations shifted by
 // D^T w_mean, the row blocks of the union split over two or four wavefronts.  lienks_wide64_route_covers: shape test (host

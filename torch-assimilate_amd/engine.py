@@ -1162,6 +1162,91 @@ class LetkfEngine:
             res.append(finish)
         return res[0] if len(res) == 1 else tuple(res)
 
+    # LETKF.estimate_weights_arrays hands float64 weights of DENSE networks (p_max > k, which weights64 and weights_wide64
+    # refuse) to weights_stream64 in two cases.  (1) Wherever the Jacobi kernel cannot hold the shape (_jacobi_primal_fits: from
+    # 97 members on; W adds no LDS to its primal form): there is nothing to compare with, the alternative is MiaError.
+    # (2) Where the Jacobi kernel runs, from WEIGHTS_STREAM64_AUTO_MIN_K members on while WEIGHTS_STREAM64_AUTO_DEN * p_max <=
+    # WEIGHTS_STREAM64_AUTO_NUM * k: the range in which every MEASURED case is at least 2x the Jacobi kernel with W beyond both
+    # spreads, counter read included (tools/time_stream64w.py, profiles/stream64w_time.json).
+    # Measured on MI355X, 1e5 points, Jacobi kernel with W on a build of the parent commit / this route with the counter read,
+    # median ms: k 80 p 93 2.53x (1006.3 / 397.4), but k 65 p 77 1.63x (345.7 / 212.3), k 96 p 107 1.75x (1591.8 / 910.0),
+    # k 80 p 173 0.71x (875.0 / 1228.7), k 96 p 173 0.84x (1363.6 / 1623.9); for information k 64 p 153 0.45x (255.1 / 569.4);
+    # spreads at most 0.4 %.  The one case that passes the factor 2 lies between two that miss it (65 and 96 members at the same
+    # p_max / k), so no range of ensemble sizes can be drawn from it: the constants admit NOTHING where the Jacobi kernel runs,
+    # and the class takes the route from 97 members on only (k 128: 1064.8 ms at p 139 and 1714.2 ms at p 203 per 5e4 points,
+    # where the parent raises MiaError).  weights_stream64 itself stays available everywhere the kernel covers
+    WEIGHTS_STREAM64_AUTO_MIN_K = 129
+    WEIGHTS_STREAM64_AUTO_NUM, WEIGHTS_STREAM64_AUTO_DEN = 0, 1
+
+    def _weights_stream64_auto(self, k: int, p_max: int) -> bool:
+        if k < 2 or k > 128 or p_max <= k or p_max > 256:
+            return False
+        if not self._jacobi_primal_fits(k, p_max):
+            return True
+        return (k >= max(self.WEIGHTS_STREAM64_AUTO_MIN_K, 65)
+                and self.WEIGHTS_STREAM64_AUTO_DEN * p_max <= self.WEIGHTS_STREAM64_AUTO_NUM * k)
+
+    def weights_stream64(self, Yb: Optional[torch.Tensor], d: Optional[torch.Tensor], nbrs: NeighbourLists,
+                         inf_factor: float = 1.0, rec: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                         return_flags: bool = False, defer_retry: bool = False, rbf_gamma: Optional[float] = None):
+        """:meth:`weights_wide64` for DENSE local networks (mia_letkf_weights_stream_f64, csrc/letkf_stream64w.hip): the same
+        float64 weights W (n, k, k) where a point sees more observations than there are members, 2 <= k <= 128,
+        k < p_max <= 256, plain ETKF core, the union's records streamed as by ``analysis(method="stream64")``; the same
+        arguments and the same answers -- W [, flags (n,)] [, finish], or None where the entry answers MIA_ERR_UNSUPPORTED (any
+        other shape, p_max <= k included, float32 input, ``rbf_gamma``, option tile = 0).  Points the kernel declines are redone
+        by the Jacobi kernel (mia_letkf_weights_retry_f64) behind the 8-byte read of the decline counter; with ``defer_retry``
+        that read is left to the caller, who must invoke the trailing callable (it returns the number of points redone).  The
+        Jacobi kernel cannot hold a dense point from 97 members on: a declined point there makes the redo raise MiaError AFTER
+        every other point has been written -- data-dependent, as ``analysis(method="stream64")`` documents for the analysis.
+        A point without observations gets sqrt(inf_factor) I exactly and flag 0."""
+        if rec is None:
+            if Yb.dim() != 2 or Yb.dtype != torch.float64:
+                return None
+            rec = self.pack_obs(Yb, d, torch.float64)
+        if rec.dtype != torch.float64 or rec.dim() != 2 or rec.shape[1] < 3:
+            return None
+        kp = rec.shape[1]
+        k = int(Yb.shape[0]) if Yb is not None else (int(out.shape[-1]) if out is not None else None)
+        if k is None:
+            raise ValueError("weights_stream64 from packed records alone needs out= (n, k, k) for the ensemble size")
+        if kp != (k + 1 + 3) // 4 * 4:
+            raise ValueError("packed records do not match the ensemble size")
+        n = nbrs.g1 - nbrs.g0
+        if out is None:
+            out = torch.empty((n, k, k), dtype=torch.float64, device=self.device)
+        elif out.shape != (n, k, k) or out.dtype != torch.float64 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float64 tensor (n, k, k)")
+        W = out
+        flags = torch.empty(n, dtype=torch.int32, device=self.device)
+        retry = torch.zeros(1, dtype=torch.int32, device=self.device)
+        gamma = float(rbf_gamma) if rbf_gamma is not None else 0.0
+
+        def args(X, Xa):      # (a closure over rec, the lists and W: a deferred retry finds them alive)
+            return (_ptr(X), nbrs.g1, 1, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0], _ptr(nbrs.cnt), _ptr(nbrs.idx),
+                    _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max, float(inf_factor), gamma, _ptr(Xa), n, 0, _ptr(W), _ptr(flags))
+        rc = self.lib.mia_letkf_weights_stream_f64(*args(None, None), _ptr(retry), self._stream())
+        if rc == -3:
+            return None
+        _cabi.check(rc, "mia_letkf_weights_stream_f64")
+
+        def finish():
+            n_retry = int(retry.item())          # host sync (8 bytes)
+            if n_retry:
+                # the Jacobi kernel computes an analysis next to the weights: a one-row zero state and its output, from the
+                # workspace, and only now that a point needs them
+                x0 = self._workspace("weights64_x0", 8 * k * max(nbrs.g1, 1)).view(torch.float64)[:k * nbrs.g1].zero_()
+                xa = self._workspace("weights64_xa", 8 * k * max(n, 1)).view(torch.float64)
+                _cabi.check(self.lib.mia_letkf_weights_retry_f64(*args(x0, xa), self._stream()), "mia_letkf_weights_retry_f64")
+            return n_retry
+        if not defer_retry:
+            finish()
+        res = [W]
+        if return_flags:
+            res.append(flags)
+        if defer_retry:
+            res.append(finish)
+        return res[0] if len(res) == 1 else tuple(res)
+
     # ------------------------------------------------------------------- IEnKS
     # ienks_update(method="auto") hands float64 updates with tau = 1 to the tile kernel (csrc/lienks_tile64.hip) only from this
     # ensemble size on: the project's rule for WEIGHTS64_AUTO_MIN_K -- the smallest measured k at which the route, counter read

@@ -279,13 +279,19 @@ class LETKF(ETKF):
         W = self._weights_on_wide64(yb, d, nb)
         if W is not None:
             return W
+        W = self._weights_on_stream64(yb, d, nb)
+        if W is not None:
+            return W
         try:
             _, W = self.engine.analysis(x, yb, d, nb, self.inf_factor, return_weights=True, **self._kernel_args())
         except MiaError as err:
-            # the Jacobi kernel cannot hold the shape (about 70 local observations): below the gate the wide kernel still can
+            # the Jacobi kernel cannot hold the shape (about 70 local observations): below the gate the wide kernel still can,
+            # and the streamed one where a point sees more observations than there are members
             if err.status != -3:
                 raise
             W = self._weights_on_wide64(yb, d, nb, gated=False)
+            if W is None:
+                W = self._weights_on_stream64(yb, d, nb, gated=False)
             if W is None:
                 raise
         return W
@@ -353,6 +359,21 @@ class LETKF(ETKF):
                 or nb.g1 - nb.g0 <= 0 or (gated and yb.shape[0] < self.engine.WEIGHTS_WIDE64_AUTO_MIN_K)):
             return None
         return self.engine.weights_wide64(yb, d, nb, self.inf_factor)
+
+    def _weights_on_stream64(self, yb, d, nb, gated=True):
+        """The float64 weights of DENSE local networks (engine.weights_stream64, csrc/letkf_stream64w.hip) where that route
+        applies: the default dtype, the plain ETKF core, k <= 128, k < p_max <= 256 and -- ``gated`` --
+        LetkfEngine._weights_stream64_auto(k, p_max): wherever the Jacobi kernel cannot hold the shape (from 97 members on)
+        and elsewhere only inside the measured WEIGHTS_STREAM64_AUTO_*; ungated it serves where the Jacobi kernel answered
+        MIA_ERR_UNSUPPORTED.  From the per-point lists, so with every localisation.  Declined points are redone with weights
+        by the Jacobi kernel inside the engine call: from 97 members on it cannot hold such a point and that redo raises
+        MiaError after the other points are written -- data-dependent, as for the analysis of these networks.  None: the
+        caller takes ``engine.analysis(return_weights=True)``."""
+        ka = self._kernel_args()
+        if (yb.dtype != torch.float64 or ka.get("rbf_gamma") is not None or ka.get("kernel_program") is not None
+                or nb.g1 - nb.g0 <= 0 or (gated and not self.engine._weights_stream64_auto(int(yb.shape[0]), int(nb.p_max)))):
+            return None
+        return self.engine.weights_stream64(yb, d, nb, self.inf_factor)
 
     def _analysis_by_step_driver(self, x, yb, d, grid_coords, obs_coords, g0, g1):
         """The whole analysis as ONE call of the native step driver (sharded.ShardedLetkf on one rank: observation index, the
