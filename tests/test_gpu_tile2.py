@@ -367,6 +367,7 @@ def test_strong_observations_are_redone_in_float64(eng, k, c, sy, sx):
     X, Yb, D = dev(state), dev(yb), dev(d)
     nb = eng.localize(grid, obs, [c])
     assert nb.p_max <= k
+    # (the reference here is the Jacobi kernel itself; its independent check against 50 digits is tests/test_gpu_wide_spectra.py)
     ref = eng.analysis(X.double(), Yb.double(), D.double(), nb, 1.1, method="eig").cpu().numpy()
     tiles = eng.localize_tiles(grid, obs, [c], nb.p_max, extra_blocks=1)
     assert tiles.stats.tolist()[1] == 0
