@@ -836,6 +836,29 @@ int mia_lienks_update_wide_f64(const double* W_in, int64_t w_stride, int k, int6
                                const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
                                double epsilon, double* W_out, int32_t* flags, int32_t* retry_count, void* stream);
 int mia_lienks_update_wide_f64_cover(int k, int p_max, int64_t n_points, int64_t P);
+/* mia_lienks_update_matfun_f64 for DENSE local networks, p_max > k, of ensembles up to 128 members
+ * (csrc/lienks_stream64.hip): core/ienks.py:108-126 with tau = 1 in primal form, Wp' = phi(C), w_mean' = psi(C) rhs / (k - 1)
+ * with C = D D^T (k x k), rhs = D (d_l + D^T w_mean), D = Yl (transform variant at Wp = I) or Yl / epsilon (bundle variant):
+ * the frame of mia_letkf_weights_stream_f64 -- union, the union's records streamed through a ring of two sixteen-slot blocks,
+ * streamed Gershgorin bound, primal table row, degree and decline of every point, one pass of the recurrence per member -- at
+ * inflation 1, with the row means of W_in as the start vector of one more product pair in the rhs pass and the 1 / epsilon
+ * scaling of the bundle variant as in mia_lienks_update_matfun_f64.  Every sum over the union is one chain of
+ * v_mfma_f64_16x16x4_f64 in ascending slot order and the row means are summed in an order that depends on (i, j) alone, so a
+ * point's bits do not depend on its tile or the shard boundary.
+ * mia_lienks_update_stream_f64: argument list, validation order and conventions of mia_lienks_update_matfun_f64 (a point
+ * without observations gets W_in back with flag 0, the transform variant's decline away from the prior --
+ * max |W_in - w_mean 1^T - I| <= 1e-14 --, flags, decline counter, degree in bits 8-15).  Shapes: 2 <= k <= 128,
+ * k < p_max <= 256; everything else (p_max <= k included) returns MIA_ERR_UNSUPPORTED before any launch and before anything
+ * is dereferenced, as do the option "tile" = 0 and a coefficient table that cannot be had (stream being captured).  Declined
+ * points are redone by mia_lienks_update_retry_f64; where the general kernel cannot hold a declined point's shape (most dense
+ * shapes from 80 members on) that redo fails with MIA_ERR_UNSUPPORTED AFTER every other point has been written -- a
+ * data-dependent limit, as with mia_letkf_weights_stream_f64.  The kernel's name is reported through mia_last_analysis_kernel.
+ * mia_lienks_update_stream_f64_cover: mia_letkf_weights_stream_f64_cover's arithmetic, host only, no device work. */
+int mia_lienks_update_stream_f64(const double* W_in, int64_t w_stride, int k, int64_t g0, int64_t g1,
+                                 const double* rec, int64_t P,
+                                 const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                                 double epsilon, double* W_out, int32_t* flags, int32_t* retry_count, void* stream);
+int mia_lienks_update_stream_f64_cover(int k, int p_max, int64_t n_points, int64_t P);
 
 /* ------------------------------------------------------------------------------------
  * Observation-space preparation, the step immediately upstream of the analysis

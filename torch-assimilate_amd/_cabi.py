@@ -142,6 +142,8 @@ _PROTOS = {
     "mia_lienks_update_f64_cover": ([i32, i32, i64, i64], i32),
     "mia_lienks_update_wide_f64": ([vp, i64, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, vp, vp, vp, vp], i32),
     "mia_lienks_update_wide_f64_cover": ([i32, i32, i64, i64], i32),
+    "mia_lienks_update_stream_f64": ([vp, i64, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, vp, vp, vp, vp], i32),
+    "mia_lienks_update_stream_f64_cover": ([i32, i32, i64, i64], i32),
     "mia_obs_space_uncorr_f32": ([vp, i64, vp, vp, i32, i64, vp, i64, vp, vp, vp], i32),
     "mia_obs_space_uncorr_f64": ([vp, i64, vp, vp, i32, i64, vp, i64, vp, vp, vp], i32),
     "mia_obs_space_corr_workspace_bytes": ([i32, i64, i32, C.POINTER(sz)], i32),

@@ -1,0 +1,700 @@
+// The localised IEnKS weight update with tau = 1 in FLOAT64 for DENSE local networks (p_max > k) of ensembles up to 128
+// members, sixteen grid points per wavefront, every contraction on the matrix cores (v_mfma_f64_16x16x4_f64), without an
+// eigensolver: what IEnKSTransformModule / IEnKSBundleModule.forward (core/ienks.py:108-141, 167-173) return on the localised
+// block under LocalizedIEnKS*.inner_loop (interface/lienks.py:75-118), where a point sees more observations than there are
+// members.  With tau = 1, reg = k - 1, D = Yl (transform variant, while Wp = I) or D = Yl / eps (bundle
+// variant) and C = D D^T (k x k), core/ienks.py:108-126 in primal form is
+//
+//     Wp'     = phi(C),                    phi(t) = 1 / sqrt(1 + t / reg)
+//     w_mean' = psi(C) rhs / reg,          psi(t) = 1 / (1 + t / reg),      rhs = D (d_l + D^T w_mean)
+//     W'      = w_mean' 1^T + Wp',         w_mean_i = (sum_j W_in[i][j] - 1) / k
+//
+// i.e. the LETKF weights at inflation 1 with the innovations shifted by D^T w_mean.
+//
+// The frame is letkf_stream64w.hip's, statement for statement: per-point lists of any metric, union by rank
+// extraction, the union's records streamed through a ring of two sixteen-slot blocks in LDS with its stage / chain / fold /
+// turn discipline, rhs in LDS, the streamed Gershgorin bound, the primal table with its degree, decline and MIA_FLAG_RETRY
+// count, halving of oversized tiles, the point-by-point pass after a non-finite record, MIA_FLAG_OVERFLOW with NaN into the
+// point's block, the XCD tile map, one pass of the recurrence per MEMBER c < k on e_c, the stores (64-bit wave-uniform base
+// plus 32-bit lane offset).  (A copy, not a template switch: the weights kernel's code object stays what it was.)  With
+// C_g = Yw^T diag(rho_g [/ eps^2]) Yw:
+//
+//     W'[g][c][j] = wm_c + (phi(C_g) e_c)_j,        wm_c = (psi(C_g) e_c) . rhs_g / reg
+//
+// Lane roles follow v_mfma_f64_16x16x4_f64 as in letkf_tile64.hip: lane (lr, h) = (lane & 15, lane >> 4) supplies A[lr][h]
+// and B[h][lr]; of a result block it holds column lr (= grid point lr), rows h + 4 r in register r.  A k-vector of the
+// sixteen points is KT result blocks (member 16 tm + h + 4 r in register r): register q of block tm IS the B operand of
+// step (tm, q) of the first product, the scaled block of T the B operand of steps (tb, q) of the second.  Summation order
+// is canonical: slot = RANK of the observation index inside the union, blocks and steps ascend, every sum over the union is
+// ONE chain of matrix instructions through its accumulator, so a point's bits depend on neither tile nor shard.  The ring
+// and the rules of the run-time loops (builtins only) are described in letkf_stream64w.hip.
+//
+// What differs is lienks_wide64.hip's, placed into this frame:
+//
+//     w_mean   per point (or once, for ONE shared matrix: w_stride = 0), in lienks64_row_means' order: lane lr adds columns
+//              lr, lr + 16, ..., then a butterfly over the sixteen lanes of a row -- an order that depends on (i, j) alone.
+//              It lands in the k-vector layout above (4 KT registers, live through the rhs pass only)
+//     rhs      one trip of the file's own product pair with the start vector w_mean: T = Yw w_mean is the first thin
+//              product on the staged block, s = rho [/ eps^2] (d dshift + T) per slot (dshift = 1, or eps for the bundle
+//              variant), then the fold.  T comes out in the layout s needs: slot 4 q + h in register q, column = point
+//     sqrt(rho) enters Dl as sqrt(rho) / eps (bundle): bound, table row and degree are those of the scaled C
+//
+// A point without observations gets its W_in back bit for bit, flag 0 (core/ienks.py:135), copied by the whole wavefront,
+// and takes no part in the tile; a tile without an active point returns before the union.  Transform variant: a point with
+// observations whose Wp is not the identity (kStreamPriorTol below) is declined whole like a point whose degree exceeds the
+// table's cap: MIA_FLAG_RETRY, counted once, W_out untouched; the general kernel redoes them (mia_lienks_update_retry_f64)
+// where it holds the shape.
+#include "mia_cheb_table64.h"
+
+namespace mia {
+
+// lienks_tile64.hip's threshold: a point of the transform variant is "at the prior" when
+// max_ij |W_in[i][j] - w_mean_i - [i == j]| <= kStreamPriorTol.  An accepted deviation perturbs D = Wp^-1 Yl by at most k delta
+// relative: 128 * 1e-14 = 1.3e-12 at the largest k of the route, two orders below the 1e-10 contract.
+constexpr double kStreamPriorTol = 1e-14;
+
+struct LienksStream64Params {
+  int k; int kp;
+  int64_t ng;
+  const double* Win; int64_t w_stride;     // [ng][k][k], or one [k][k] for all points when w_stride == 0
+  const double* rec;
+  const int32_t* cnt; const int32_t* idx; const double* w; int p_cap; int p_max;
+  int ub;                                                    // sixteen-slot blocks of the slot table of the launch
+  int transform;                           // 1: transform variant (D = Yl while Wp = I), 0: bundle variant (D = Yl / eps)
+  double dscale, dshift;                   // 1 / eps and eps (bundle), 1 and 1 (transform)
+  double reg, inv_reg, cs_phi, cs_psi;
+  double* W; int32_t* flags; int32_t* retry_count;
+  int dmax;
+  const Tab64Hdr* tab_hdr; const double2* tab_c;
+};
+
+// Row means of one point's incoming weights, w_mean_i = (sum_j W[i][j] - 1) / k (_split_weights, core/ienks.py:46-54), for
+// the four rows i = 16 tm + 4 q + h of member block tm, in lienks64_row_means' summation order: the sixteen lanes (lr) of lane
+// group h share row i, lane lr adds columns lr, lr + 16, ... ascending, then the butterfly; all sixteen end up with the mean.
+// take: this lane keeps the means in wm4 (0 for rows beyond k: they meet zero A operands in the product).  Four rows a call:
+// 4 KT loads in flight, and the caller's loop over points keeps it at that.
+template <int KT>
+__device__ __forceinline__ void lienks_stream64_row_means(const double* win, int k, int tm, int lr, int h, bool take,
+                                                          d4t& wm4) {
+  double s[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    // (a wave-uniform 64-bit row group plus ONE 32-bit lane offset h k + lr, as the stores below: clamped row and column
+    //  indices, or a 64-bit address per row, would be registers for the compiler to carry from in front of every loop.  Only
+    //  the last row and column blocks are ragged; what lies beyond k is not read.)
+    const bool rok = tm < KT - 1 || 16 * tm + 4 * q + h < k;
+    const char* row = reinterpret_cast<const char*>(win + (16 * tm + 4 * q) * k);      // wave-uniform
+    const unsigned loff = (unsigned)(h * k + lr) * 8u;                                  // 32-bit lane offset in bytes
+    s[q] = 0.0;
+#pragma unroll
+    for (int jj = 0; jj < KT; ++jj) {
+      double v = 0.0;
+      if (rok && (jj < KT - 1 || lr + 16 * jj < k)) v = *reinterpret_cast<const double*>(row + (loff + 128u * jj));
+      s[q] += v;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const bool rok = tm < KT - 1 || 16 * tm + 4 * q + h < k;
+    s[q] += __shfl_xor(s[q], 1, 64);
+    s[q] += __shfl_xor(s[q], 2, 64);
+    s[q] += __shfl_xor(s[q], 4, 64);
+    s[q] += __shfl_xor(s[q], 8, 64);
+    const double wm = rok ? (s[q] - 1.0) / double(k) : 0.0;
+    wm4[q] = take ? wm : wm4[q];
+  }
+}
+
+// max_ij |W[i][j] - w_mean_i - [i == j]| over the elements this lane sees (NaN where an element is not a number), the means
+// in the order above: the prior test of the transform variant.  Four rows a trip, one per lane group.
+template <int KT>
+__device__ __forceinline__ double lienks_stream64_prior_dev(const double* win, int k, int lr, int h) {
+  double dev = 0.0;
+#pragma clang loop unroll(disable)
+  for (int i0 = 0; i0 < k; i0 += 4) {
+    const int i = i0 + h;
+    const bool rok = i < k;
+    const char* row = reinterpret_cast<const char*>(win + i0 * k);                     // wave-uniform
+    const unsigned loff = (unsigned)(h * k + lr) * 8u;                                  // 32-bit lane offset in bytes
+    double wv[KT];
+    double s = 0.0;
+#pragma unroll
+    for (int jj = 0; jj < KT; ++jj) {
+      double v = 0.0;
+      if (rok && (jj < KT - 1 || lr + 16 * jj < k)) v = *reinterpret_cast<const double*>(row + (loff + 128u * jj));
+      wv[jj] = v;
+      s += v;
+    }
+    s += __shfl_xor(s, 1, 64);
+    s += __shfl_xor(s, 2, 64);
+    s += __shfl_xor(s, 4, 64);
+    s += __shfl_xor(s, 8, 64);
+    const double wm = (s - 1.0) / double(k);
+#pragma unroll
+    for (int jj = 0; jj < KT; ++jj) {
+      const int j = lr + 16 * jj;
+      const double e = fabs(wv[jj] - wm - (i == j ? 1.0 : 0.0));
+      if (rok && j < k) dev = (e > dev || e != e) ? e : dev;
+    }
+  }
+  return dev;
+}
+
+// KT = ceil(k / 16).  One wavefront per workgroup; its LDS bounds how many share a compute unit.
+template <int KT>
+__global__ __launch_bounds__(64, 1) void lienks_stream64_kernel(LienksStream64Params P) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int lane = threadIdx.x;
+  const int k = P.k, kp = P.kp, pm = P.p_max;
+  const int UMAX = 16 * P.ub, DS = UMAX + 1;
+  const int KS = kp | 1;                                     // odd row pitch (in doubles) of a staged block
+  constexpr int NC = KT + 1;                                 // column trips of a staged row: kp <= 16 KT + 4
+  double* Ring = reinterpret_cast<double*>(smem_raw);        // [2][16][KS] two sixteen-slot blocks of union records
+  double* Rl = Ring + 2 * 16 * KS;                           // [4 KT][64]  rhs of the tile, every lane its own registers' worth
+  double* Dl = Rl + 4 * KT * 64;                             // [16][DS]    sqrt(rho) of (point, slot), 0 = not local
+  int* ukey = reinterpret_cast<int*>(Dl + 16 * DS);          // [UMAX]      observation index of a slot, ascending; -1 = none
+  unsigned* Kl = reinterpret_cast<unsigned*>(Dl);            // [16][nl]    index + 1 of the lists' entries while the union is formed
+
+  // XCD-aware block -> tile map: blocks b, b + 8, ... share an XCD (and its L2) and take consecutive tiles, whose
+  // records overlap
+  const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+  const int64_t ntile = (P.ng + 15) >> 4;
+  if (bid >= ntile) return;
+  const int64_t q8 = ntile >> 3, r8 = ntile & 7, xcd = bid & 7;
+  const int64_t tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int64_t p0 = tile << 4;                              // first point of the tile (index into the launch's ng points)
+  const int npts = P.ng - p0 < 16 ? (int)(P.ng - p0) : 16;
+  const int lr = lane & 15, h = lane >> 4, lp = lane >> 2, sub = lane & 3;
+  const unsigned kk8 = (unsigned)(k * k) * 8u;               // bytes of one point's weights
+
+  // ---- the tile's neighbour lists stay in memory: lane (lp, sub) walks entries sub, sub + 4, ... of point lp
+  int nl = pm < P.p_cap ? pm : P.p_cap;
+  nl = nl < UMAX ? nl : UMAX;
+  const int64_t lrow = p0 + (lp < npts ? lp : 0);            // (lists, flags and weights count from the shard's g0)
+  const int32_t* ib = P.idx + lrow * P.p_cap;
+  const double* wb = P.w + lrow * P.p_cap;
+  int lcnt = P.cnt[lrow];
+  const bool shared_w = P.w_stride == 0;
+  unsigned long long skipmask;       // bit 4 p: point p takes no part in the tile (overflow, no observation, declined here)
+  {
+    const bool pbad = lp < npts && (lcnt > pm || lcnt > P.p_cap || lcnt > UMAX);   // loud failure, never truncate
+    if (pbad) {
+      if (sub == 0) P.flags[p0 + lp] = MIA_FLAG_OVERFLOW;
+      const double nanv = __builtin_nan("");
+      double* wp = P.W + (p0 + lp) * (int64_t)(k * k);
+      for (int it = sub; it < k * k; it += 4) wp[it] = nanv;
+    }
+    if (lp >= npts || pbad) lcnt = 0;
+    // ---- no local observation: the weights go back as they came (core/ienks.py:135), the whole wavefront copying a point
+    const unsigned long long emask = __ballot(lp < npts && !pbad && lcnt == 0);
+    skipmask = __ballot(pbad) | emask;
+    for (int pt = 0; pt < npts; ++pt) {
+      if (!((emask >> (4 * pt)) & 1ull)) continue;
+      const double* win = P.Win + (p0 + pt) * P.w_stride;
+      double* wout = P.W + (p0 + pt) * (int64_t)(k * k);
+      for (int it = lane; it < k * k; it += 64) wout[it] = win[it];
+      if (lane == 0) P.flags[p0 + pt] = 0;
+    }
+    // ---- transform variant: D = Wp^-1 Yl is Yl only at the prior; any other point with observations is the general kernel's
+    if (P.transform) {
+      unsigned np = 0u;                                      // bit p: point p is not at the prior
+      const int nscan = shared_w ? 1 : npts;
+      for (int pt = 0; pt < nscan; ++pt) {
+        if (!shared_w && ((skipmask >> (4 * pt)) & 1ull)) continue;
+        const double dev = lienks_stream64_prior_dev<KT>(P.Win + (p0 + pt) * P.w_stride, k, lr, h);
+        if (__any(!(dev <= kStreamPriorTol))) np |= shared_w ? 0xffffu : (1u << pt);
+      }
+      const bool pnot = lp < npts && lcnt > 0 && ((np >> lp) & 1u);
+      if (pnot && sub == 0) {
+        P.flags[p0 + lp] = MIA_FLAG_RETRY;
+        atomicAdd(P.retry_count, 1);
+      }
+      if (pnot) lcnt = 0;
+      skipmask |= __ballot(pnot);
+    }
+    if (!__any(lcnt > 0)) return;                            // nothing left to update in this tile
+  }
+
+  // ---- the ring: stage() asks memory for block tb of the union (rows 4 j + h, columns lr + 16 i of this lane), commit()
+  //      writes the staged registers to one half.  Rows beyond the union (key -1) are zeros and touch no memory
+  int UB = 1;
+  int cur = 0;                                               // the half that holds the block of the trip
+  double st[4][NC];
+  auto stage = [&](int tb) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int key = ukey[16 * tb + 4 * j + h];
+      const double* src = P.rec + ((int64_t)(key < 0 ? 0 : key) * kp + lr);
+#pragma unroll
+      for (int i = 0; i < NC; ++i) {
+        double v = 0.0;
+        if (key >= 0 && (i < KT - 1 || lr + 16 * i < kp)) v = src[16 * i];
+        st[j][i] = v;
+      }
+    }
+  };
+  auto commit = [&](int half, double& fin) {                 // fin stays 0 while every value is finite (inf * 0 = NaN)
+    double* dst = Ring + half * 16 * KS + h * KS + lr;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int i = 0; i < NC; ++i) {
+        fin = fma(st[j][i], 0.0, fin);
+        if (i < KT - 1 || lr + 16 * i < kp) dst[4 * j * KS + 16 * i] = st[j][i];
+      }
+  };
+
+  int lo = 0;
+  bool single = false;                                       // a non-finite record was met: the rest of the tile goes point by point
+#pragma clang loop unroll(disable)
+  while (lo < npts) {
+    const bool colok = lr < npts && !((skipmask >> (4 * lr)) & 1ull);
+    const double* Dcol = Dl + lr * DS + h;                    // + 16 t + 4 r: slot 16 t + h + 4 r of column lr
+    // A operands out of the current half.  First product / Gram: record row lr of the block, member 16 tm + 4 q + h; second
+    // product: record row 4 q + h, member 16 tj + lr.  Innovation and pad columns are not members (only the last block is ragged).
+    auto a_in = [&](int tm, int q) -> double {
+      const int mem = 16 * tm + 4 * q + h;
+      const bool ok = tm < KT - 1 || mem < k;
+      const double v = Ring[cur * 16 * KS + lr * KS + (ok ? mem : 0)];
+      return ok ? v : 0.0;
+    };
+    auto a_out = [&](int q, int tj) -> double {
+      const int mem = 16 * tj + lr;
+      const bool ok = tj < KT - 1 || mem < k;
+      const double v = Ring[cur * 16 * KS + (4 * q + h) * KS + (ok ? mem : 0)];
+      return ok ? v : 0.0;
+    };
+    // The A operands of four matrix instructions are read from LDS while the four before them run, and the scheduler is
+    // held to that order: left alone it reads a trip's 8 KT operands ahead of its first instruction, which the 40 KT
+    // registers of the recurrence vectors and the staged block leave no room for above 80 members.
+    // T (or Gram) block of the trip: steps (tm, q) ascending through ONE accumulator; b[tm][q] = the B operands
+    auto chain = [&](const auto& b) -> d4t {
+      d4t acc = {0., 0., 0., 0.};
+      double an[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) an[q] = a_in(0, q);
+#pragma unroll
+      for (int tm = 0; tm < KT; ++tm) {
+        double ac[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) ac[q] = an[q];
+        if (tm + 1 < KT) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) an[q] = a_in(tm + 1, q);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc = MIA_MFMA64(ac[q], b[tm][q], acc);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      return acc;
+    };
+    // y += Yw^T (s o .) over the block of the trip: the second product's steps (tb, q), B = the scaled block; step
+    // e = KT q + tj, four steps per group
+    auto fold = [&](const double (&s)[4], d4t (&y)[KT]) {
+      double an[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) an[i] = a_out(i / KT, i % KT);
+#pragma unroll
+      for (int g = 0; g < KT; ++g) {
+        double ac[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ac[i] = an[i];
+        if (g + 1 < KT) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) an[i] = a_out((4 * g + 4 + i) / KT, (4 * g + 4 + i) % KT);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) y[(4 * g + i) % KT] = MIA_MFMA64(ac[i], s[(4 * g + i) / KT], y[(4 * g + i) % KT]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    };
+    // the end of a trip: the staged block into the other half, which becomes the current one
+    auto turn = [&](double& fin) {
+      commit(cur ^ 1, fin);
+      __syncthreads();
+      cur ^= 1;
+    };
+    // ---- union of the lists of points [lo, hi): slot = RANK of the observation index, found by repeated extraction of
+    //      the smallest remaining key (one sweep over the keys in LDS and one DPP reduction per slot); shrink the range
+    //      until the union fits
+    int n = single ? 1 : 16, hi, U;
+    bool act;
+    for (;;) {
+      hi = lo + n < npts ? lo + n : npts;
+      act = lp >= lo && lp < hi;
+      for (int pos = sub; pos < nl; pos += 4) {
+        int e = -1;
+        if (act && pos < lcnt) e = ib[pos];
+        Kl[lp * nl + pos] = e >= 0 ? (unsigned)e + 1u : 0u;
+      }
+      for (int i = lane; i < UMAX; i += 64) ukey[i] = -1;
+      __syncthreads();
+      U = 0;
+      unsigned last = 0u;
+      const int e0 = lo * nl, e1 = hi * nl;
+#pragma clang loop unroll(disable)
+      for (;;) {
+        unsigned best = 0u;                       // ~(smallest key above `last`), 0 = none left
+        for (int e = e0 + lane; e < e1; e += 64) {
+          const unsigned key1 = Kl[e];
+          const unsigned cand = key1 > last ? ~key1 : 0u;
+          best = cand > best ? cand : best;
+        }
+        best = tile64_wave_max_u32(best);
+        if (best == 0u) break;
+        last = ~best;
+        if (U < UMAX && lane == 0) ukey[U] = (int)(last - 1u);
+        ++U;
+        if (U > UMAX) break;
+      }
+      if (U > UMAX) { __syncthreads(); n >>= 1; continue; }     // (n = 1 always fits: a single list has at most UMAX entries)
+      __syncthreads();
+      UB = (U + 15) >> 4;
+      UB = UB < 1 ? 1 : UB;                                      // blocks in use; slots up to 16 UB are staged
+      // ---- sqrt(rho) of (point, slot): the slot of an entry is the place of its index in the sorted slot table
+      for (int i = lane; i < 16 * DS; i += 64) Dl[i] = 0.0;     // (over the keys: every lane is past the barrier behind their last read)
+      __syncthreads();
+      if (act)
+        for (int pos = sub; pos < lcnt; pos += 4) {
+          const int key = ib[pos];
+          if (key < 0) continue;
+          int a = 0, b = U;
+          while (a < b) {
+            const int mid = (a + b) >> 1;
+            if (ukey[mid] < key) a = mid + 1; else b = mid;
+          }
+          Dl[lp * DS + a] = wb[pos] * P.dscale;
+        }
+      // ---- w_mean of the points of this pass: wmean[tm][q] = w_mean[point lr][member 16 tm + 4 q + h], the B operand of
+      //      the shift (0 for points that take no part).  Closed before the first matrix instruction of the pass.
+      d4t wmean[KT];
+#pragma unroll
+      for (int tm = 0; tm < KT; ++tm) {
+        d4t wm4 = {0., 0., 0., 0.};
+        const int nscan = shared_w ? 1 : hi;
+#pragma clang loop unroll(disable)
+        for (int pt = shared_w ? 0 : lo; pt < nscan; ++pt) {
+          if (!shared_w && ((skipmask >> (4 * pt)) & 1ull)) continue;
+          // (lo and hi come out of the union's wave reductions: the same in every lane, but only this tells the compiler so,
+          //  and with it that the matrix' address is a scalar)
+          const int ptu = __builtin_amdgcn_readfirstlane(pt);
+          lienks_stream64_row_means<KT>(P.Win + (p0 + ptu) * P.w_stride, k, tm, lr, h, shared_w || lr == pt, wm4);
+        }
+        wmean[tm] = wm4;
+      }
+      // ---- block 0 into the ring
+      double fin = 0.0;
+      stage(0);
+      commit(cur, fin);
+      __syncthreads();
+      // ---- rhs_g = Yw^T (rho_g o d), once per tile (d = column k of the records); this first pass over the union also
+      //      looks at every record (blocks 1 .. UB - 1 and block 0 again pass through commit)
+      d4t rhs[KT];
+#pragma unroll
+      for (int tj = 0; tj < KT; ++tj) rhs[tj] = d4t{0., 0., 0., 0.};
+      {
+        int tb = 0;
+#pragma clang loop unroll(disable)
+        do {
+          stage(tb + 1 < UB ? tb + 1 : 0);
+          __builtin_amdgcn_sched_barrier(0);
+          const d4t Tb = chain(wmean);            // T = Yw w_mean: slot 4 q + h of the block in register q, column = point
+          double s[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const double dv = Dcol[16 * tb + 4 * q];
+            s[q] = (dv * dv) * (Ring[cur * 16 * KS + (4 * q + h) * KS + k] * P.dshift + Tb[q]);
+          }
+          fold(s, rhs);
+          turn(fin);
+        } while (++tb < UB);
+      }
+      // A non-finite record would reach EVERY column of the tile through the shared products (NaN * 0 = NaN), also the
+      // points that do not see that observation.  Such a tile is analysed point by point: the union is then the point's
+      // own list and the damage stays where the reference has it.
+      if (__any(fin != fin) && hi - lo > 1) { __syncthreads(); n = 1; single = true; continue; }
+#pragma unroll
+      for (int tj = 0; tj < KT; ++tj)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Rl[(4 * tj + r) * 64 + lane] = rhs[tj][r];
+      break;
+    }
+    const bool colact = colok && lr >= lo && lr < hi;
+    double nofin = 0.0;                                       // (the later passes do not look at the records again)
+    // ---- Gershgorin bound of every point, streamed: L_g = max_a w_a sum_b |G_ab| w_b.  Row block t is read from memory as
+    //      B operands (slot 16 t + lr, member 16 tm + 4 q + h); every Gram block (tk, t) is formed (4 KT instructions),
+    //      folded into the row sums (4) and dropped
+    double L = 0.0;
+    {
+      int t = 0;
+#pragma clang loop unroll(disable)
+      do {
+        double at[KT][4];
+        {
+          const int key = ukey[16 * t + lr];
+          const double* src = P.rec + ((int64_t)(key < 0 ? 0 : key) * kp + h);
+#pragma unroll
+          for (int tm = 0; tm < KT; ++tm)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              double v = 0.0;
+              if (key >= 0 && (tm < KT - 1 || 16 * tm + 4 * q + h < k)) v = src[16 * tm + 4 * q];
+              at[tm][q] = v;
+            }
+        }
+        d4t R = {0., 0., 0., 0.};
+        int tk = 0;
+#pragma clang loop unroll(disable)
+        do {
+          stage(tk + 1 < UB ? tk + 1 : 0);
+          __builtin_amdgcn_sched_barrier(0);
+          const d4t Gb = chain(at);
+          double dk[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) dk[q] = Dcol[16 * tk + 4 * q];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) R = MIA_MFMA64(fabs(Gb[q]), dk[q], R);
+          turn(nofin);
+        } while (++tk < UB);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const double v = Dcol[16 * t + 4 * r] * R[r];
+          L = (v > L || v != v) ? v : L;
+        }
+      } while (++t < UB);
+    }
+    // ---- degree and interval of every point from the table
+    double alpha;
+    int deg, tab_idx, pflag = 0;
+    bool decl;
+    {
+      L = tile64_max_h(L);
+      L = fmax(L, 1e-300 * P.reg) * (1.0 + 1e-12);
+      if (!(L == L) || !(fabs(L) < 1e300)) { pflag |= MIA_FLAG_NONFINITE; L = P.reg; }
+      tab_idx = (int)ceil(double(kTabPerOctave) * log2(L * P.inv_reg)) + kTabIdx0;
+      tab_idx = tab_idx < 0 ? 0 : (tab_idx > kTabN - 1 ? kTabN - 1 : tab_idx);      // (the last entries decline: T = 2^8)
+      const Tab64Hdr hd = P.tab_hdr[tab_idx];
+      deg = hd.deg;
+      decl = colact && (deg > P.dmax || deg > kTab64Deg - 1);
+      alpha = (deg > kTab64Deg - 1) ? 0.0 : hd.two_over_T * P.inv_reg;             // (a declined column carries bounded junk)
+      if (decl && h == 0) {
+        P.flags[p0 + lr] = MIA_FLAG_RETRY;
+        atomicAdd(P.retry_count, 1);
+      }
+    }
+    // (a column without observations has its W_in back already: it is not active and asks for no step)
+    const int degmax = (int)tile64_wave_max_u32((colact && !decl) ? (unsigned)deg : 0u);
+    const double2* ctab = P.tab_c + (size_t)tab_idx * kTab64Deg;
+    auto coef = [&](int j) -> double2 {                              // (zero beyond a point's own degree)
+      const double2 c = ctab[j < kTab64Deg ? j : kTab64Deg - 1];
+      return double2{c.x * P.cs_phi, c.y * P.cs_psi};
+    };
+
+#pragma clang loop unroll(disable)
+    for (int c = 0; c < k; ++c) {
+      // (lane roles through opaque copies, as in letkf_tile64.hip: what is invariant in this loop -- the member numbers of the
+      // start vector, the 4 KT offsets of the output, their predicates -- would otherwise be hoisted and held in registers
+      // across the recurrence, which has none to spare)
+      int hv = h, lrv = lr;
+      asm volatile("" : "+v"(hv), "+v"(lrv));
+      d4t va[KT], vb[KT], aphi[KT], apsi[KT];
+      // ---- the recurrence on the 16 columns at once: v_0 = e_c on live columns (member c < k always exists), v_1 = alpha C v_0 - v_0,
+      //      v_{j+1} = 2 (alpha C v_j - v_j) - v_{j-1}
+#pragma unroll
+      for (int tm = 0; tm < KT; ++tm)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) va[tm][q] = (colact && 16 * tm + 4 * q + hv == c) ? 1.0 : 0.0;
+      // acc += sc C u = Yw^T (sc rho o (Yw u)), one sixteen-slot block of the union per trip; sc = alpha or 2 alpha of the
+      // column.  The caller has put the recurrence's other terms into acc: the step needs no vector of its own for C u,
+      // which at 128 members is the 64 registers that decide between spilling and not
+      auto product = [&](const d4t (&u)[KT], d4t (&acc)[KT], const double sc) {
+        int tb = 0;
+#pragma clang loop unroll(disable)
+        do {
+          stage(tb + 1 < UB ? tb + 1 : 0);
+          __builtin_amdgcn_sched_barrier(0);
+          const d4t Tb = chain(u);
+          double s[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const double dv = Dcol[16 * tb + 4 * q];
+            s[q] = (sc * (dv * dv)) * Tb[q];
+          }
+          fold(s, acc);
+          turn(nofin);
+        } while (++tb < UB);
+      };
+      // vnew = 2 alpha C vcur - 2 vcur - vold, accumulated over vold; the two functions accumulate c_j vnew
+      auto advance = [&](d4t (&vold)[KT], const d4t (&vcur)[KT], const double2 cj) {
+#pragma unroll
+        for (int t = 0; t < KT; ++t) vold[t] = -2.0 * vcur[t] - vold[t];
+        product(vcur, vold, 2.0 * alpha);
+#pragma unroll
+        for (int t = 0; t < KT; ++t) {
+          aphi[t] = cj.x * vold[t] + aphi[t];
+          apsi[t] = cj.y * vold[t] + apsi[t];
+        }
+      };
+      {
+        const double2 c0 = coef(0), c1 = coef(1);
+#pragma unroll
+        for (int t = 0; t < KT; ++t) vb[t] = -va[t];
+        product(va, vb, alpha);                 // vb = v_1 = alpha C v_0 - v_0
+#pragma unroll
+        for (int t = 0; t < KT; ++t) {
+          aphi[t] = c0.x * va[t] + c1.x * vb[t];
+          apsi[t] = c0.y * va[t] + c1.y * vb[t];
+        }
+      }
+      int j = 2;
+      double2 cj = coef(2), cj1 = coef(3);
+#pragma clang loop unroll(disable)
+      for (; j + 1 <= degmax; j += 2) {
+        const double2 nj = coef(j + 2), nj1 = coef(j + 3);       // requested one trip ahead
+        advance(va, vb, cj);          // va = v_j
+        advance(vb, va, cj1);         // vb = v_{j+1}
+        cj = nj; cj1 = nj1;
+      }
+      if (j <= degmax) advance(va, vb, cj);
+      // ---- wm_c = (psi(C) e_c) . rhs / reg: members in the lane's registers first, then the four lane groups
+      double zs = 0.0;
+#pragma unroll
+      for (int tm = 0; tm < KT; ++tm)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) zs = fma(apsi[tm][r], Rl[(4 * tm + r) * 64 + lane], zs);
+      const double wm = tile64_add_h(zs);
+      // row c of the sixteen points' weights: wave-uniform 64-bit base (tile, row c) + 32-bit lane offset (point lr, column j)
+      char* obase = reinterpret_cast<char*>(P.W + (p0 * k + c) * (int64_t)k);
+      const unsigned olane = (unsigned)lrv * kk8 + (unsigned)hv * 8u;
+      const bool wr = colact && !decl;
+#pragma unroll
+      for (int tj = 0; tj < KT; ++tj)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int mem = 16 * tj + hv + 4 * r;
+          const double o = aphi[tj][r] + wm;
+          if (!(fabs(o) <= 1e300) && mem < k) pflag |= MIA_FLAG_NONFINITE;
+          if (wr && mem < k) *reinterpret_cast<double*>(obase + (olane + (unsigned)(16 * tj + 4 * r) * 8u)) = o;
+        }
+    }
+    {
+      if (!(colact && !decl)) pflag = 0;          // (columns that are not written do not report)
+      const unsigned long long fb = __ballot(pflag != 0);
+      const bool anyf = ((fb >> lr) & 0x0001000100010001ull) != 0ull;
+      if (h == 0 && colact && !decl) P.flags[p0 + lr] = (anyf ? MIA_FLAG_NONFINITE : 0) | (deg << 8);
+    }
+    lo = hi;
+    __syncthreads();
+  }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------
+constexpr int kLienksStream64MaxBlocks = 16;                    // 256 slots, at every ensemble size of the route
+constexpr int kLienksStream64MaxK = 128;
+
+// letkf_stream64w.hip's formula to the byte (w_mean and T live in registers): ring [2][16][kp | 1] + rhs [4 KT][64] +
+// sqrt(rho) [16][16 ub + 1] doubles, slot table [16 ub] ints
+static size_t lienks_stream64_lds_bytes(int ub, int k) {
+  const int umax = 16 * ub, kp = (k + 1 + 3) & ~3, kt = (k + 15) >> 4;
+  return align_up(((size_t)2 * 16 * (kp | 1) + (size_t)4 * kt * 64 + 16 * (size_t)(umax + 1)) * sizeof(double) +
+                  (size_t)umax * sizeof(int), 16);
+}
+// the blocks a launch takes: the longest list plus what sixteen consecutive points of a regular network add (one
+// observation per point at stride 1).  Fewer slots = more workgroups per compute unit; a tile that needs more is halved.
+static int lienks_stream64_blocks(int p_max) {
+  const int want = (p_max + 16 + 15) >> 4;
+  return want < kLienksStream64MaxBlocks ? want : kLienksStream64MaxBlocks;
+}
+
+// weights_stream64_route_covers' arithmetic
+static bool lienks_stream64_route_covers(int k, int p_max, int64_t ng) {
+  if (k < 2 || k > kLienksStream64MaxK || p_max <= k || ng < 0) return false;           // p_max <= k: the dual routes
+  if (p_max > 16 * kLienksStream64MaxBlocks) return false;
+  // a pass addresses W as wave-uniform base (tile, row) + 32-bit byte offset inside the tile's sixteen matrices
+  if ((int64_t)16 * k * k * 8 >= ((int64_t)1 << 31)) return false;
+  if (lienks_stream64_lds_bytes(lienks_stream64_blocks(p_max), k) > kMaxDynamicLds) return false;
+  return ((ng + 15) >> 4) <= (int64_t)65536 * 65535;
+}
+
+template <int KT>
+static int lienks_stream64_launch_t(const LienksStream64Params& dp, hipStream_t stream) {
+  const size_t lds = lienks_stream64_lds_bytes(dp.ub, dp.k);
+  if (lds > kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
+  auto kern = lienks_stream64_kernel<KT>;
+  if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const int64_t ntile = (dp.ng + 15) >> 4;
+  const int64_t gx = ntile < 65536 ? ntile : 65536;
+  const int64_t gy = (ntile + gx - 1) / gx;
+  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
+  kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(64), lds, stream>>>(dp);
+  note_analysis_kernel("lienks_stream64_kernel<%d>", KT);
+  MIA_LAUNCH_CHECK();
+  return MIA_OK;
+}
+
+static int lienks_stream64_launch(const double* W_in, int64_t w_stride, int k, int64_t ng, const double* rec,
+                                  const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                                  double epsilon, double* W_out, int32_t* flags, int32_t* retry_count, hipStream_t stream) {
+  if (!option(MIA_OPT_TILE) || !W_in || !W_out || !flags || !retry_count) return MIA_ERR_UNSUPPORTED;
+  if (w_stride != 0 && w_stride != (int64_t)k * k) return MIA_ERR_UNSUPPORTED;
+  if (!lienks_stream64_route_covers(k, p_max, ng)) return MIA_ERR_UNSUPPORTED;
+  const CoefTable64* tab = cheb_coef_table64(stream, kTab64Primal);
+  if (!tab) return MIA_ERR_UNSUPPORTED;
+  LienksStream64Params dp;
+  dp.k = k; dp.kp = (k + 1 + 3) & ~3;
+  dp.ng = ng; dp.Win = W_in; dp.w_stride = w_stride; dp.rec = rec;
+  dp.cnt = nbr_cnt; dp.idx = nbr_idx; dp.w = nbr_w; dp.p_cap = p_cap; dp.p_max = p_max;
+  dp.ub = lienks_stream64_blocks(p_max);
+  dp.transform = epsilon > 0.0 ? 0 : 1;
+  dp.dscale = epsilon > 0.0 ? 1.0 / epsilon : 1.0;
+  dp.dshift = epsilon > 0.0 ? epsilon : 1.0;
+  // the constants of weights_stream64_launch at inf_factor = 1: reg = k - 1, f0 = 1
+  const double rg = (double)(k - 1), km = (double)(k - 1);
+  dp.reg = rg;
+  dp.inv_reg = 1.0 / rg;
+  dp.cs_phi = sqrt(km / rg);                                  // f0
+  dp.cs_psi = 1.0 / rg;
+  dp.W = W_out; dp.flags = flags; dp.retry_count = retry_count;
+  dp.dmax = kTab64Deg - 1;
+  dp.tab_hdr = tab->hdr; dp.tab_c = tab->c;
+  switch ((k + 15) >> 4) {
+    case 1: return lienks_stream64_launch_t<1>(dp, stream);
+    case 2: return lienks_stream64_launch_t<2>(dp, stream);
+    case 3: return lienks_stream64_launch_t<3>(dp, stream);
+    case 4: return lienks_stream64_launch_t<4>(dp, stream);
+    case 5: return lienks_stream64_launch_t<5>(dp, stream);
+    case 6: return lienks_stream64_launch_t<6>(dp, stream);
+    case 7: return lienks_stream64_launch_t<7>(dp, stream);
+    case 8: return lienks_stream64_launch_t<8>(dp, stream);
+  }
+  return MIA_ERR_UNSUPPORTED;
+}
+
+}  // namespace mia
+
+using namespace mia;
+
+// tau = 1 in float64 on tiles for dense local networks of up to 128 members: mia_lienks_update_matfun_f64's validation in its
+// order, then the option and the cover -- nothing is dereferenced before them -- then the one kernel of the route
+extern "C" int mia_lienks_update_stream_f64(const double* W_in, int64_t w_stride, int k, int64_t g0, int64_t g1,
+                                            const double* rec, int64_t P, const int32_t* nbr_cnt, const int32_t* nbr_idx,
+                                            const double* nbr_w, int p_cap, int p_max, double epsilon, double* W_out,
+                                            int32_t* flags, int32_t* retry_count, void* stream) {
+  (void)hipGetLastError();
+  if (g1 < g0 || g0 < 0 || k < 2 || P < 0 || p_cap < 1 || p_max < 0) return MIA_ERR_SIZE;
+  if (w_stride != 0 && w_stride != (int64_t)k * k) return MIA_ERR_SIZE;
+  const int64_t ng = g1 - g0;
+  if (ng == 0) return MIA_OK;
+  if (!W_in || !W_out || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
+  if (P > 0 && !rec) return MIA_ERR_NULL;
+  if (p_max > p_cap) p_max = p_cap;
+  return lienks_stream64_launch(W_in, w_stride, k, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, epsilon, W_out, flags,
+                                retry_count, (hipStream_t)stream);
+}
+extern "C" int mia_lienks_update_stream_f64_cover(int k, int p_max, int64_t n_points, int64_t P) {
+  if (P < 0) return 0;
+  return lienks_stream64_route_covers(k, p_max, n_points) ? 1 : 0;
+}
+

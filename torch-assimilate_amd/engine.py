@@ -1270,6 +1270,58 @@ class LetkfEngine:
     # whatever this gate says.  Below 65 members lienks_update64_kernel keeps "auto" (k 64 p 57: 83.4 / 81.1 ms against 57.9 /
     # 56.6 ms here, 1.44x / 1.43x, equal bits -- a factor below the rule's 2); method="wide64" names the kernel everywhere it covers
     IENKS_WIDE64_AUTO_MIN_K = 65
+    # The IEnKS classes (ienks.py) hand float64 updates with tau = 1 of DENSE networks (p_max > k, which the two tile kernels
+    # above refuse) to method="stream64" (csrc/lienks_stream64.hip) in two cases.  (a) Wherever the general kernel cannot hold
+    # the shape (_ienks_general_fits: with p_max = k + 1 the bundle variant from 80 members on, the transform variant from 69):
+    # there is nothing to compare with, the alternative is MiaError.  (b) Where the general kernel runs, from
+    # IENKS_STREAM64_AUTO_MIN_K members on while IENKS_STREAM64_AUTO_DEN * p_max <= IENKS_STREAM64_AUTO_NUM * k: the range in
+    # which every MEASURED case is at least 2x the general kernel in the variants it holds, beyond both spreads, counter read
+    # included (tools/time_ienks_stream64.py, profiles/ienks_stream64_time.json).
+    # Measured on MI355X, 1e5 points, general kernel / this route with the counter read, median ms, bundle (per-point weights) and
+    # transform (shared prior): k 65 p 77 3.06x (623.8 / 203.6) and 3.66x (743.1 / 202.8), k 72 p 77 bundle 2.74x (777.7 / 283.8;
+    # the general kernel refuses the transform variant there); worst round against best round the same figures, spreads at most
+    # 1.9 ms.  For information k 40 p 77: bundle 0.95x (95.5 / 100.9), transform 2.20x (221.0 / 100.4) -- below 65 members the
+    # bundle variant loses, so the range starts at the smallest measured k from which every measured case passes, 65, and ends at
+    # the largest measured p_max / k that passed, 77 / 65 (longer lists cost this kernel more than the general one: 2.19's k 80
+    # p 173 was 0.71x the Jacobi kernel).  It is narrow by itself: with p_max = k + 1 the general kernel holds the bundle variant
+    # up to 79 members and the transform variant up to 68.  NOT measured: any ensemble size between 65 and 72 or 72 and 79, any
+    # p_max other than 77.  Where the general kernel refuses the shape (absolute times, same columns): k 80 p 93 382.6 / 381.6,
+    # k 80 p 173 bundle 1178.4, k 96 p 107 bundle 881.9 ms per 1e5 points; k 128 p 139 1010.8 / 1009.0, k 128 p 203 bundle 1623.7 ms
+    # per 5e4 points.  method="stream64" names the kernel everywhere it covers.
+    # ienks_update(method="auto") itself is unchanged: the hand-over lives in the classes, as for estimate_weights_arrays
+    IENKS_STREAM64_AUTO_MIN_K = 65
+    IENKS_STREAM64_AUTO_NUM, IENKS_STREAM64_AUTO_DEN = 77, 65
+
+    @staticmethod
+    def _ienks_general_lds_bytes(k: int, p_max: int, tau: float, bundle: bool) -> int:
+        """Restates the dynamic LDS of ienks_update_kernel<double, 256> as ienks_update_impl sizes it (csrc/ienks.hip)."""
+        n, kp = (k + 1) & ~1, (k + 1 + 3) & ~3
+        lda = n + 1
+        nd = ((max(p_max, 1) + 1) & ~1) if (float(tau) == 1.0 and p_max <= k) else 0
+        rows = nd if nd > 0 else max(p_max, 1)
+        pl = (p_max + 3) & ~1
+        e = 2 * n * lda + (1 if bundle else 2) * rows * kp + 5 * n + pl
+        nbk = n // 2
+        b = 8 * e + 4 * pl + 16 + 2 * ((nbk * (nbk - 1) // 2 + 7) & ~7) + 4 * ((n + 1) & ~1) + 8 * (256 // 64 * 2)
+        return (b + 15) // 16 * 16
+
+    @staticmethod
+    def _ienks_general_fits(k: int, p_max: int, tau: float, bundle: bool) -> bool:
+        """Whether the general float64 kernel can hold a point of this shape: where it cannot, mia_lienks_update_f64 answers
+        MIA_ERR_UNSUPPORTED (k 72 p_max 77: bundle 136 384 bytes fits, transform 183 200 does not)."""
+        return LetkfEngine._ienks_general_lds_bytes(k, p_max, tau, bundle) <= LetkfEngine.JACOBI_MAX_LDS
+
+    def _ienks_stream64_auto(self, k: int, p_max: int, bundle: bool, shared: bool) -> bool:
+        """Whether the classes name method="stream64" for a float64 update with tau = 1 (checked by the caller, like the
+        entry's cover): ``bundle`` = bundle variant, ``shared`` = ONE (k, k) weight matrix for all points."""
+        if k < 2 or k > 128 or p_max <= k or p_max > 256:
+            return False
+        if not (bundle or shared):        # per-point transform weights have Wp != I: the launch would be declined whole
+            return False
+        if not self._ienks_general_fits(k, p_max, 1.0, bundle):
+            return True
+        return (k >= self.IENKS_STREAM64_AUTO_MIN_K
+                and self.IENKS_STREAM64_AUTO_DEN * p_max <= self.IENKS_STREAM64_AUTO_NUM * k)
 
     def ienks_update(self, weights: torch.Tensor, Yb: Optional[torch.Tensor], d: Optional[torch.Tensor],
                      nbrs: NeighbourLists, tau: float = 1.0, epsilon: Optional[float] = None,
@@ -1286,16 +1338,18 @@ class LetkfEngine:
         variant condition, through the wide tile kernel of csrc/lienks_wide64.hip where mia_lienks_update_wide_f64_cover says
         yes (2 <= k <= 128, p_max <= k) and k >= IENKS_WIDE64_AUTO_MIN_K -- and, whatever that gate says, where the general
         kernel answers MIA_ERR_UNSUPPORTED because its LDS cannot hold the shape.  "tile64" / "wide64": those kernels by name
-        (ValueError outside float64, tau = 1 and the kernel's cover); "eig": general kernel.  Points a tile kernel declines are
+        (ValueError outside float64, tau = 1 and the kernel's cover); "stream64": the tile kernel for DENSE local networks
+        (csrc/lienks_stream64.hip, 2 <= k <= 128 and k < p_max <= 256; the same ValueErrors), which "auto" never takes at this
+        level -- the IEnKS classes name it where :meth:`_ienks_stream64_auto` says so; "eig": general kernel.  Points a tile kernel declines are
         redone by the general kernel (mia_lienks_update_retry_f64) behind the 8-byte read of the decline counter; where the
         general kernel cannot hold a declined point's shape that redo raises MiaError AFTER every other point has been
-        written -- data-dependent, as ``weights_wide64`` documents.  With ``defer_retry`` (methods "tile64" and "wide64" only)
+        written -- data-dependent, as ``weights_wide64`` documents.  With ``defer_retry`` (the named tile methods only)
         the read is left to the caller, who must invoke the trailing callable of the result (it returns the number of points
         redone).  ``out``: a contiguous (n, k, k) tensor of the weights' dtype to write into."""
-        if method not in ("auto", "eig", "tile64", "wide64"):
-            raise ValueError("method must be 'auto', 'eig', 'tile64' or 'wide64'")
-        if defer_retry and method not in ("tile64", "wide64"):
-            raise ValueError("defer_retry needs method='tile64' or 'wide64'")
+        if method not in ("auto", "eig", "tile64", "wide64", "stream64"):
+            raise ValueError("method must be 'auto', 'eig', 'tile64', 'wide64' or 'stream64'")
+        if defer_retry and method not in ("tile64", "wide64", "stream64"):
+            raise ValueError("defer_retry needs method='tile64', 'wide64' or 'stream64'")
         weights = torch.as_tensor(weights)
         dtype = weights.dtype if weights.dtype in (torch.float32, torch.float64) else torch.float64
         weights = weights.to(device=self.device, dtype=dtype).contiguous()
@@ -1334,6 +1388,14 @@ class LetkfEngine:
                 raise ValueError("method='wide64' needs tau = 1 (tau = %g)" % float(tau))
             if not self.lib.mia_lienks_update_wide_f64_cover(k, min(nbrs.p_max, nbrs.p_cap), n, rec.shape[0]):
                 raise ValueError("method='wide64' covers 2 <= k <= 128 and p_max <= k (k = %d, p_max = %d)" % (k, nbrs.p_max))
+        if method == "stream64":
+            if dtype != torch.float64:
+                raise ValueError("method='stream64' needs float64 weights (float32 has its own route under 'auto')")
+            if float(tau) != 1.0:
+                raise ValueError("method='stream64' needs tau = 1 (tau = %g)" % float(tau))
+            if not self.lib.mia_lienks_update_stream_f64_cover(k, min(nbrs.p_max, nbrs.p_cap), n, rec.shape[0]):
+                raise ValueError("method='stream64' covers 2 <= k <= 128 and k < p_max <= 256 (k = %d, p_max = %d)"
+                                 % (k, nbrs.p_max))
         if dtype == torch.float32 and float(tau) == 1.0 and n > 0 and method != "eig":
             # tau = 1 through the eigensolver-free weights kernel; -3 = shape outside it (primal route, order > 32)
             retry = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -1356,6 +1418,8 @@ class LetkfEngine:
             entry = "mia_lienks_update_matfun_f64"
         elif method == "wide64":
             entry = "mia_lienks_update_wide_f64"
+        elif method == "stream64":
+            entry = "mia_lienks_update_stream_f64"
         elif method == "auto" and f64_tau1 and variant_ok:
             if k >= self.IENKS64_AUTO_MIN_K and self.lib.mia_lienks_update_f64_cover(
                     k, min(nbrs.p_max, nbrs.p_cap), n, rec.shape[0]):
@@ -1394,7 +1458,7 @@ class LetkfEngine:
             res = tile_route(entry)
             if res is not None:
                 return res
-            if method in ("tile64", "wide64"):
+            if method in ("tile64", "wide64", "stream64"):
                 raise ValueError("method='%s': the tile kernel is not available (option tile = 0, or the stream is being "
                                  "captured before the coefficient table exists)" % method)
         sfx = "f32" if dtype == torch.float32 else "f64"

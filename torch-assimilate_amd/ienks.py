@@ -15,6 +15,7 @@ weights, the transforms, the normalisation and the update stay on the GPU.
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Callable, Optional, Sequence
 
 import numpy as np
@@ -28,8 +29,32 @@ __all__ = ["IEnKSTransformModule", "IEnKSBundleModule", "IEnKSTransform", "IEnKS
            "LocalizedIEnKSTransform", "LocalizedIEnKSBundle"]
 
 
+def _ienks_method(eng: LetkfEngine, dtype, k: int, nbrs, tau: float, epsilon: Optional[float], shared: bool,
+                  block: bool = False) -> str:
+    """The ``method`` the classes pass to ``LetkfEngine.ienks_update``: "stream64" (csrc/lienks_stream64.hip) for float64
+    updates with tau = 1 of dense networks (more local observations than members) where the kernel's cover and
+    ``LetkfEngine._ienks_stream64_auto`` say yes, "auto" everywhere else.  ``block``: the one-block form of the modules -- one
+    tile with one point, taken only where the general kernel cannot hold the shape."""
+    if dtype != torch.float64 or float(tau) != 1.0 or nbrs.g1 <= nbrs.g0:
+        return "auto"
+    p_max = min(nbrs.p_max, nbrs.p_cap)
+    bundle = epsilon is not None
+    if not eng._ienks_stream64_auto(k, p_max, bundle, shared):
+        return "auto"
+    if block and eng._ienks_general_fits(k, p_max, 1.0, bundle):
+        return "auto"
+    if not eng.lib.mia_lienks_update_stream_f64_cover(k, p_max, nbrs.g1 - nbrs.g0, max(p_max, 1)):
+        return "auto"
+    tile = C.c_int(1)
+    eng.lib.mia_get_option(b"tile", C.byref(tile))
+    return "stream64" if tile.value else "auto"          # (option tile = 0 switches every tile route off: as before)
+
+
 class IEnKSTransformModule(ETKFModule):
-    """core/ienks.py:29-141."""
+    """core/ienks.py:29-141.  In float64 with tau = 1 a block of more observations than members (up to 256, up to 128
+    members) that the general kernel cannot hold goes through the dense tile kernel (csrc/lienks_stream64.hip), as one tile
+    with one point: the bundle variant always, the transform variant while Wp = I (anything else is declined to the general
+    kernel, which then raises MiaError)."""
     epsilon: Optional[float] = None
 
     def __init__(self, tau: float = 1.0, engine: Optional[LetkfEngine] = None):
@@ -57,7 +82,8 @@ class IEnKSTransformModule(ETKFModule):
         if p == 0:
             cand = cand - 1
         nbrs = eng.localize_from_dist(torch.zeros((1, 1, cap), dtype=torch.float64, device=eng.device), cand, [1.0])
-        return eng.ienks_update(w, perts, obs, nbrs, self.tau, self.epsilon)[0]
+        return eng.ienks_update(w, perts, obs, nbrs, self.tau, self.epsilon,
+                                method=_ienks_method(eng, dtype, k, nbrs, self.tau, self.epsilon, True, block=True))[0]
 
     forward = __call__
 
@@ -83,8 +109,12 @@ class LocalizedIEnKSTransform(LETKF):
     float64 tile kernel (csrc/lienks_tile64.hip) from ``LetkfEngine.IENKS64_AUTO_MIN_K`` members on, where the shape is covered
     (k <= 64, no more local observations than members); for 65 .. 128 members it runs on the wide tile kernel
     (csrc/lienks_wide64.hip) from ``LetkfEngine.IENKS_WIDE64_AUTO_MIN_K`` members on, and wherever the general kernel cannot
-    hold the shape.  Every later iteration has Wp != I and stays on the general kernel, which above 64 members holds only short
-    observation lists (e.g. not k = 80 with 63): there the second iteration raises MiaError."""
+    hold the shape.  Where a grid point sees MORE observations than there are members (up to 256, up to 128 members) it runs on
+    the dense tile kernel (csrc/lienks_stream64.hip) wherever the general kernel cannot hold the shape (with one observation
+    more than members: from 69 members on) and inside ``LetkfEngine.IENKS_STREAM64_AUTO_*`` (from 65 members on with at most
+    77 / 65 k local observations, the measured range in which the route is at least 2x the general kernel).
+    Every later iteration has Wp != I and stays on the general kernel, which above 64 members holds only short observation
+    lists (e.g. not k = 80 with 63): there the second iteration raises MiaError."""
     _epsilon: Optional[float] = None
 
     def __init__(self, forward_model: Callable, localization=None, tau: float = 1.0, max_iter: int = 10,
@@ -140,7 +170,10 @@ class LocalizedIEnKSTransform(LETKF):
                 else IEnKSTransformModule(self.tau, self.engine)
             return mod(self._dev(weights), self._dev(yb), self._dev(d))
         nb = self._lists(grid_coords, obs_coords, 0, None, grid_info, obs_info)
-        return self.engine.ienks_update(self._dev(weights), self._dev(yb), self._dev(d), nb, self.tau, self._epsilon)
+        w = self._dev(weights)
+        dtype = w.dtype if w.dtype in (torch.float32, torch.float64) else torch.float64
+        method = _ienks_method(self.engine, dtype, w.shape[-1], nb, self.tau, self._epsilon, w.dim() == 2)
+        return self.engine.ienks_update(w, self._dev(yb), self._dev(d), nb, self.tau, self._epsilon, method=method)
 
     def update_state_arrays(self, state, observe: Callable, grid_coords=None, obs_coords=None,
                             pseudo_state=None) -> torch.Tensor:
@@ -175,7 +208,12 @@ class LocalizedIEnKSBundle(LocalizedIEnKSTransform):
     ``LetkfEngine.IENKS64_AUTO_MIN_K`` members on, where the shape is covered (k <= 64, no more local observations than members);
     for 65 .. 128 members on the wide tile kernel (csrc/lienks_wide64.hip) from ``LetkfEngine.IENKS_WIDE64_AUTO_MIN_K`` members
     on, and wherever the general kernel cannot hold the shape (e.g. k = 96 with 81 or k = 128 with 62 local observations).
-    tau < 1, more local observations than members and more than 128 members stay on the general kernel."""
+    Where a grid point sees MORE observations than there are members (up to 256) every iteration runs on the dense tile kernel
+    (csrc/lienks_stream64.hip) wherever the general kernel cannot hold the shape (with one observation more than members: from
+    80 members on, e.g. k = 96 with 107 or k = 128 with 203) and inside ``LetkfEngine.IENKS_STREAM64_AUTO_*`` (from 65 members
+    on with at most 77 / 65 k local observations, the measured range in which the route is at least 2x the general kernel); the
+    unlocalised ``IEnKSBundle`` takes the kernel with its one block only where the general kernel cannot hold it.  tau < 1, more than 256 local
+    observations and more than 128 members stay on the general kernel."""
 
     def __init__(self, forward_model: Callable, localization=None, tau: float = 1.0, epsilon: float = 1e-4,
                  max_iter: int = 10, smoother: bool = False, gpu: bool = True, pre_transform=None,
