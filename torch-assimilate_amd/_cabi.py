@@ -17,6 +17,30 @@ class KernelOp(C.Structure):
     _fields_ = [("op", C.c_int32), ("reserved", C.c_int32), ("value", C.c_double)]
 
 
+# the signatures the tile routes share (include/mia_letkf.h), named once.  ``f`` = the working precision's scalar type
+_LISTS = [vp, vp, vp, i32, i32]                                       # nbr_cnt, nbr_idx, nbr_w, p_cap, p_max
+_SHARD = [vp, i64, i32, i32, i64, i64, vp, i64] + _LISTS             # X, ldx, m, k, g0, g1, rec, P, the lists
+
+
+def _analysis_entry(f):        # ..., inf_factor, gamma, Xa, ldo, o0, flags, retry_count, stream (packed entries and the weights redo: W, flags, stream)
+    return (_SHARD + [f, f, vp, i64, i64, vp, vp, vp], i32)
+
+
+def _analysis_redo(f):         # ..., inf_factor, gamma, Xa, ldo, o0, flags, stream
+    return (_SHARD + [f, f, vp, i64, i64, vp, vp], i32)
+
+
+def _weights_entry(f):         # ..., inf_factor, gamma, Xa, ldo, o0, W, flags, retry_count, stream
+    return (_SHARD + [f, f, vp, i64, i64, vp, vp, vp, vp], i32)
+
+
+def _ienks_tile_entry(f):      # W_in, w_stride, k, g0, g1, rec, P, the lists, epsilon, W_out, flags, retry_count, stream
+    return ([vp, i64, i32, i64, i64, vp, i64] + _LISTS + [f, vp, vp, vp, vp], i32)
+
+
+_COVER7 = ([i32, i32, i32, i64, i64, i64, i64], i32)                  # m, k, p_max, ldx, ldo, n_points, P
+_COVER4 = ([i32, i32, i64, i64], i32)                                 # k, p_max, n_points, P
+
 _PROTOS = {
     "mia_version": ([], i32),
     "mia_status_string": ([i32], C.c_char_p),
@@ -47,53 +71,38 @@ _PROTOS = {
                                 vp, i64, i64, vp, vp, vp, sz, vp], i32),
     "mia_letkf_pack_obs_f32": ([vp, vp, i32, i64, vp, vp], i32),
     "mia_letkf_pack_obs_f64": ([vp, vp, i32, i64, vp, vp], i32),
-    "mia_letkf_analysis_packed_f32": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f32, f32,
-                                       vp, i64, i64, vp, vp, vp], i32),
-    "mia_letkf_analysis_packed_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
-                                       vp, i64, i64, vp, vp, vp], i32),
-    "mia_letkf_analysis_matfun_f32": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f32, f32,
-                                       vp, i64, i64, vp, vp, vp], i32),
-    "mia_letkf_analysis_matfun_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
-                                       vp, i64, i64, vp, vp, vp], i32),
-    "mia_letkf_analysis_retry_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
-                                      vp, i64, i64, vp, vp], i32),
-    "mia_letkf_matfun_f64_cover": ([i32, i32, i32, i64, i64, i64, i64], i32),
-    "mia_letkf_analysis_dense_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
-                                      vp, i64, i64, vp, vp, vp], i32),
-    "mia_letkf_dense_f64_cover": ([i32, i32, i32, i64, i64, i64, i64], i32),
+    "mia_letkf_analysis_packed_f32": _analysis_entry(f32),
+    "mia_letkf_analysis_packed_f64": _analysis_entry(f64),
+    "mia_letkf_analysis_matfun_f32": _analysis_entry(f32),
+    "mia_letkf_analysis_matfun_f64": _analysis_entry(f64),
+    "mia_letkf_analysis_retry_f64": _analysis_redo(f64),
+    "mia_letkf_matfun_f64_cover": _COVER7,
+    "mia_letkf_analysis_dense_f64": _analysis_entry(f64),
+    "mia_letkf_dense_f64_cover": _COVER7,
     "mia_letkf_analysis_patch_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
                                       vp, i64, i64, vp, vp, vp, i64, i32, vp], i32),
-    "mia_letkf_patch_f64_cover": ([i32, i32, i32, i64, i64, i64, i64], i32),
+    "mia_letkf_patch_f64_cover": _COVER7,
     "mia_letkf_tile_union_census": ([vp, i64, i64, vp, vp, i32, i32, i32, vp, vp, sz, vp], i32),
-    "mia_letkf_analysis_stream_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
-                                       vp, i64, i64, vp, vp, vp], i32),
-    "mia_letkf_stream_f64_cover": ([i32, i32, i32, i64, i64, i64, i64], i32),
-    "mia_letkf_analysis_wide_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
-                                     vp, i64, i64, vp, vp, vp], i32),
-    "mia_letkf_wide_f64_cover": ([i32, i32, i32, i64, i64, i64, i64], i32),
-    "mia_lketkf_rbf_analysis_matfun_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
-                                            vp, i64, i64, vp, vp, vp], i32),
-    "mia_lketkf_rbf_f64_cover": ([i32, i32, i32, i64, i64, i64, i64], i32),
+    "mia_letkf_analysis_stream_f64": _analysis_entry(f64),
+    "mia_letkf_stream_f64_cover": _COVER7,
+    "mia_letkf_analysis_wide_f64": _analysis_entry(f64),
+    "mia_letkf_wide_f64_cover": _COVER7,
+    "mia_lketkf_rbf_analysis_matfun_f64": _analysis_entry(f64),
+    "mia_lketkf_rbf_f64_cover": _COVER7,
     "mia_lketkf_kernel_analysis_matfun_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64,
                                                C.POINTER(KernelOp), i32, vp, i64, i64, vp, vp, vp], i32),
     "mia_lketkf_kernel_analysis_retry_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64,
                                               C.POINTER(KernelOp), i32, vp, i64, i64, vp, vp], i32),
-    "mia_lketkf_kernel_f64_cover": ([i32, i32, i32, i64, i64, i64, i64], i32),
-    "mia_letkf_weights_matfun_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
-                                      vp, i64, i64, vp, vp, vp, vp], i32),
-    "mia_letkf_weights_retry_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
-                                     vp, i64, i64, vp, vp, vp], i32),
-    "mia_letkf_weights_f64_cover": ([i32, i32, i64, i64], i32),
-    "mia_letkf_weights_wide_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
-                                    vp, i64, i64, vp, vp, vp, vp], i32),
-    "mia_letkf_weights_wide_f64_cover": ([i32, i32, i64, i64], i32),
-    "mia_letkf_weights_stream_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
-                                      vp, i64, i64, vp, vp, vp, vp], i32),
-    "mia_letkf_weights_stream_f64_cover": ([i32, i32, i64, i64], i32),
-    "mia_letkf_weights_matfun_f32": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f32, f32,
-                                      vp, i64, i64, vp, vp, vp, vp], i32),
-    "mia_letkf_weights_retry_f32": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f32, f32,
-                                     vp, i64, i64, vp, vp, vp], i32),
+    "mia_lketkf_kernel_f64_cover": _COVER7,
+    "mia_letkf_weights_matfun_f64": _weights_entry(f64),
+    "mia_letkf_weights_retry_f64": _analysis_entry(f64),
+    "mia_letkf_weights_f64_cover": _COVER4,
+    "mia_letkf_weights_wide_f64": _weights_entry(f64),
+    "mia_letkf_weights_wide_f64_cover": _COVER4,
+    "mia_letkf_weights_stream_f64": _weights_entry(f64),
+    "mia_letkf_weights_stream_f64_cover": _COVER4,
+    "mia_letkf_weights_matfun_f32": _weights_entry(f32),
+    "mia_letkf_weights_retry_f32": _analysis_entry(f32),
     "mia_letkf_index_build_f64": ([vp, i64, i32, C.POINTER(C.c_int32), C.POINTER(f64), i32, vp, sz, vp], i32),
     # cyclic coordinates (PeriodicMetric): the period, host [n_coord], follows coord_group / gc_c / n_r
     "mia_letkf_index_build_periodic_f64": ([vp, i64, i32, C.POINTER(C.c_int32), C.POINTER(f64), C.POINTER(f64), i32, vp, sz, vp],
@@ -115,8 +124,7 @@ _PROTOS = {
     "mia_lketkf_rbf_analysis_tiles_f32": ([vp, i64, i32, i32, i64, i64, vp, vp, i64, vp, i32, i32, f32, f32, vp, i64, i64,
                                            vp, vp, vp], i32),
     "mia_letkf_weights_tiles_f32": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, i32, i32, f32, vp, i64, i64, vp, vp, vp, vp], i32),
-    "mia_letkf_analysis_retry_f32": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f32, f32,
-                                      vp, i64, i64, vp, vp], i32),
+    "mia_letkf_analysis_retry_f32": _analysis_redo(f32),
     "mia_lketkf_rbf_analysis_f32": ([vp, i64, i32, i32, i64, i64, vp, vp, i64, vp, vp, vp, i32, i32, f32, f32,
                                      vp, i64, i64, vp, vp, vp, sz, vp], i32),
     "mia_lketkf_rbf_analysis_f64": ([vp, i64, i32, i32, i64, i64, vp, vp, i64, vp, vp, vp, i32, i32, f64, f64,
@@ -135,15 +143,15 @@ _PROTOS = {
     "mia_apply_local_weights_f64": ([vp, i64, i32, i32, i64, i64, vp, vp, i64, i64, vp], i32),
     "mia_lienks_update_f32": ([vp, i64, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp], i32),
     "mia_lienks_update_f64": ([vp, i64, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64, vp, vp, vp], i32),
-    "mia_lienks_update_matfun_f32": ([vp, i64, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f32, vp, vp, vp, vp], i32),
+    "mia_lienks_update_matfun_f32": _ienks_tile_entry(f32),
     "mia_lienks_update_retry_f32": ([vp, i64, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f32, f32, vp, vp, vp], i32),
-    "mia_lienks_update_matfun_f64": ([vp, i64, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, vp, vp, vp, vp], i32),
+    "mia_lienks_update_matfun_f64": _ienks_tile_entry(f64),
     "mia_lienks_update_retry_f64": ([vp, i64, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64, vp, vp, vp], i32),
-    "mia_lienks_update_f64_cover": ([i32, i32, i64, i64], i32),
-    "mia_lienks_update_wide_f64": ([vp, i64, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, vp, vp, vp, vp], i32),
-    "mia_lienks_update_wide_f64_cover": ([i32, i32, i64, i64], i32),
-    "mia_lienks_update_stream_f64": ([vp, i64, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, vp, vp, vp, vp], i32),
-    "mia_lienks_update_stream_f64_cover": ([i32, i32, i64, i64], i32),
+    "mia_lienks_update_f64_cover": _COVER4,
+    "mia_lienks_update_wide_f64": _ienks_tile_entry(f64),
+    "mia_lienks_update_wide_f64_cover": _COVER4,
+    "mia_lienks_update_stream_f64": _ienks_tile_entry(f64),
+    "mia_lienks_update_stream_f64_cover": _COVER4,
     "mia_obs_space_uncorr_f32": ([vp, i64, vp, vp, i32, i64, vp, i64, vp, vp, vp], i32),
     "mia_obs_space_uncorr_f64": ([vp, i64, vp, vp, i32, i64, vp, i64, vp, vp, vp], i32),
     "mia_obs_space_corr_workspace_bytes": ([i32, i64, i32, C.POINTER(sz)], i32),

@@ -397,6 +397,23 @@ static int apply_local_weights_impl(const T* X, int64_t ldx, int m, int k, int64
   return MIA_OK;
 }
 
+// What an entry of an IEnKS tile route checks before its launch, in this order: sizes, the weight stride, empty shard, NULL
+// pointers, NULL records, clamp of p_max -- nothing is dereferenced.  kLaunch (no status: those are <= 0): the entry goes on
+// to its launch, with *p_max clamped to p_cap; anything else is what the entry returns.
+constexpr int kLaunch = 1;
+template <typename T>
+static int ienks_tile_entry_checks(const T* W_in, int64_t w_stride, int k, int64_t g0, int64_t g1, const T* rec, int64_t P,
+                                   const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int* p_max,
+                                   const T* W_out, const int32_t* flags, const int32_t* retry_count) {
+  if (g1 < g0 || g0 < 0 || k < 2 || P < 0 || p_cap < 1 || *p_max < 0) return MIA_ERR_SIZE;
+  if (w_stride != 0 && w_stride != (int64_t)k * k) return MIA_ERR_SIZE;
+  if (g1 == g0) return MIA_OK;
+  if (!W_in || !W_out || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
+  if (P > 0 && !rec) return MIA_ERR_NULL;
+  if (*p_max > p_cap) *p_max = p_cap;
+  return kLaunch;
+}
+
 }  // namespace mia
 
 using namespace mia;
@@ -415,13 +432,10 @@ extern "C" int mia_lienks_update_matfun_f32(const float* W_in, int64_t w_stride,
                                             const double* nbr_w, int p_cap, int p_max, float epsilon, float* W_out,
                                             int32_t* flags, int32_t* retry_count, void* stream) {
   (void)hipGetLastError();
-  if (g1 < g0 || g0 < 0 || k < 2 || P < 0 || p_cap < 1 || p_max < 0) return MIA_ERR_SIZE;
-  if (w_stride != 0 && w_stride != (int64_t)k * k) return MIA_ERR_SIZE;
+  const int rc = ienks_tile_entry_checks(W_in, w_stride, k, g0, g1, rec, P, nbr_cnt, nbr_idx, nbr_w, p_cap, &p_max, W_out, flags,
+                                         retry_count);
+  if (rc != kLaunch) return rc;
   const int64_t ng = g1 - g0;
-  if (ng == 0) return MIA_OK;
-  if (!W_in || !W_out || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
-  if (P > 0 && !rec) return MIA_ERR_NULL;
-  if (p_max > p_cap) p_max = p_cap;
   const IenksOpts opt{epsilon > 0.0f ? 2 : 1, W_in, w_stride, epsilon > 0.0f ? 1.0f / epsilon : 1.0f};
   // (X = W_out as a harmless non-NULL placeholder: no state row is transformed, m = 0)
   return cheb_analysis_launch(W_out, ng, 0, k, 0, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, 1.0f, 0, 0.0f, W_out, ng, 0,
@@ -453,14 +467,10 @@ extern "C" int mia_lienks_update_matfun_f64(const double* W_in, int64_t w_stride
                                             const double* nbr_w, int p_cap, int p_max, double epsilon, double* W_out,
                                             int32_t* flags, int32_t* retry_count, void* stream) {
   (void)hipGetLastError();
-  if (g1 < g0 || g0 < 0 || k < 2 || P < 0 || p_cap < 1 || p_max < 0) return MIA_ERR_SIZE;
-  if (w_stride != 0 && w_stride != (int64_t)k * k) return MIA_ERR_SIZE;
-  const int64_t ng = g1 - g0;
-  if (ng == 0) return MIA_OK;
-  if (!W_in || !W_out || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
-  if (P > 0 && !rec) return MIA_ERR_NULL;
-  if (p_max > p_cap) p_max = p_cap;
-  return lienks64_launch(W_in, w_stride, k, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, epsilon, W_out, flags, retry_count,
+  const int rc = ienks_tile_entry_checks(W_in, w_stride, k, g0, g1, rec, P, nbr_cnt, nbr_idx, nbr_w, p_cap, &p_max, W_out, flags,
+                                         retry_count);
+  if (rc != kLaunch) return rc;
+  return lienks64_launch(W_in, w_stride, k, g1 - g0, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, epsilon, W_out, flags, retry_count,
                          (hipStream_t)stream);
 }
 extern "C" int mia_lienks_update_retry_f64(const double* W_in, int64_t w_stride, int k, int64_t g0, int64_t g1,
@@ -482,19 +492,32 @@ extern "C" int mia_lienks_update_wide_f64(const double* W_in, int64_t w_stride, 
                                           const double* nbr_w, int p_cap, int p_max, double epsilon, double* W_out,
                                           int32_t* flags, int32_t* retry_count, void* stream) {
   (void)hipGetLastError();
-  if (g1 < g0 || g0 < 0 || k < 2 || P < 0 || p_cap < 1 || p_max < 0) return MIA_ERR_SIZE;
-  if (w_stride != 0 && w_stride != (int64_t)k * k) return MIA_ERR_SIZE;
-  const int64_t ng = g1 - g0;
-  if (ng == 0) return MIA_OK;
-  if (!W_in || !W_out || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
-  if (P > 0 && !rec) return MIA_ERR_NULL;
-  if (p_max > p_cap) p_max = p_cap;
-  return lienks_wide64_launch(W_in, w_stride, k, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, epsilon, W_out, flags,
+  const int rc = ienks_tile_entry_checks(W_in, w_stride, k, g0, g1, rec, P, nbr_cnt, nbr_idx, nbr_w, p_cap, &p_max, W_out, flags,
+                                         retry_count);
+  if (rc != kLaunch) return rc;
+  return lienks_wide64_launch(W_in, w_stride, k, g1 - g0, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, epsilon, W_out, flags,
                               retry_count, (hipStream_t)stream);
 }
 extern "C" int mia_lienks_update_wide_f64_cover(int k, int p_max, int64_t n_points, int64_t P) {
   if (P < 0) return 0;
   return lienks_wide64_route_covers(k, p_max, n_points) ? 1 : 0;
+}
+// tau = 1 in float64 on tiles for dense local networks of up to 128 members (lienks_stream64.hip): the same checks, then the
+// option and the cover, then the one kernel of the route
+extern "C" int mia_lienks_update_stream_f64(const double* W_in, int64_t w_stride, int k, int64_t g0, int64_t g1,
+                                            const double* rec, int64_t P, const int32_t* nbr_cnt, const int32_t* nbr_idx,
+                                            const double* nbr_w, int p_cap, int p_max, double epsilon, double* W_out,
+                                            int32_t* flags, int32_t* retry_count, void* stream) {
+  (void)hipGetLastError();
+  const int rc = ienks_tile_entry_checks(W_in, w_stride, k, g0, g1, rec, P, nbr_cnt, nbr_idx, nbr_w, p_cap, &p_max, W_out, flags,
+                                         retry_count);
+  if (rc != kLaunch) return rc;
+  return lienks_stream64_launch(W_in, w_stride, k, g1 - g0, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, epsilon, W_out, flags,
+                                retry_count, (hipStream_t)stream);
+}
+extern "C" int mia_lienks_update_stream_f64_cover(int k, int p_max, int64_t n_points, int64_t P) {
+  if (P < 0) return 0;
+  return lienks_stream64_route_covers(k, p_max, n_points) ? 1 : 0;
 }
 extern "C" int mia_apply_local_weights_f32(const float* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
                                            const float* W, float* Xa, int64_t ldo, int64_t o0, void* stream) {

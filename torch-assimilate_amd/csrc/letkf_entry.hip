@@ -116,6 +116,45 @@ static int analysis_impl(const T* X, int64_t ldx, int m, int k, int64_t g0, int6
                                  inf_factor, kernel_mode, gamma, Xa, ldo, o0, W_opt, flags_opt, stream);
 }
 
+// What an entry of a tile route checks before its launch, in this order: sizes, inflation, the gamma rule, empty shard, NULL
+// pointers, leading dimensions, clamp of p_max, NULL records.  kLaunch (no status: those are <= 0): the entry goes on to its
+// launch, with *p_max clamped to p_cap; anything else is what the entry returns.  The variations between the entries:
+//   rule   kGammaRefused   the plain-core routes answer MIA_ERR_UNSUPPORTED for gamma > 0 (the RBF filter is not theirs)
+//          kGammaRequired  the RBF route answers MIA_ERR_SIZE without gamma > 0, as mia_lketkf_rbf_analysis_packed_f64
+//          kProgram        the kernel-expression route checks prog / n_ops in that place
+//          kStateOptional  the float64 weights entries write W and flags only: X and Xa may be NULL, and their leading
+//                          dimensions are then not looked at
+//          0               the float32 twins: gamma selects the core
+//   also   one more pointer that must not be NULL: W of the weights entries, the tile map of patch64 (else: flags again)
+//   n_tiles, union_blocks  patch64's extra sizes
+enum : unsigned { kGammaRefused = 1, kGammaRequired = 2, kProgram = 4, kStateOptional = 8 };
+constexpr int kLaunch = 1;
+
+template <typename T>
+static int tile_entry_checks(unsigned rule, const T* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1, const T* rec, int64_t P,
+                             const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int* p_max,
+                             T inf_factor, T gamma, const T* Xa, int64_t ldo, int64_t o0, const void* also, const int32_t* flags,
+                             const int32_t* retry_count, const mia_kernel_op_t* prog = nullptr, int n_ops = 0,
+                             int64_t n_tiles = 1, int union_blocks = 1) {
+  if (g1 < g0 || g0 < 0 || m < 1 || k < 2 || P < 0 || p_cap < 1 || *p_max < 0 || n_tiles < 0 || union_blocks < 1) return MIA_ERR_SIZE;
+  if (!(inf_factor > T(0))) return MIA_ERR_SIZE;
+  if ((rule & kGammaRefused) && gamma > T(0)) return MIA_ERR_UNSUPPORTED;
+  if ((rule & kGammaRequired) && !(gamma > T(0))) return MIA_ERR_SIZE;
+  if (rule & kProgram) {
+    const int rc = kernel_program_check(prog, n_ops);
+    if (rc != MIA_OK) return rc;
+  }
+  const int64_t ng = g1 - g0;
+  if (ng == 0) return MIA_OK;
+  const bool opt = (rule & kStateOptional) != 0;
+  if ((!opt && (!X || !Xa)) || !also || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
+  if (opt ? ((X && ldx < g1) || (Xa && ldo < o0 + ng)) : (ldx < g1 || ldo < o0 + ng)) return MIA_ERR_SIZE;
+  if (n_tiles == 0) return MIA_ERR_SIZE;
+  if (*p_max > p_cap) *p_max = p_cap;
+  if (P > 0 && !rec) return MIA_ERR_NULL;
+  return kLaunch;
+}
+
 }  // namespace mia
 
 using namespace mia;
@@ -234,15 +273,10 @@ extern "C" int mia_letkf_analysis_matfun_f32(const float* X, int64_t ldx, int m,
                                              float inf_factor, float gamma, float* Xa, int64_t ldo, int64_t o0,
                                              int32_t* flags, int32_t* retry_count, void* stream) {
   (void)hipGetLastError();
-  if (g1 < g0 || g0 < 0 || m < 1 || k < 2 || P < 0 || p_cap < 1 || p_max < 0) return MIA_ERR_SIZE;
-  if (!(inf_factor > 0.0f)) return MIA_ERR_SIZE;
-  const int64_t ng = g1 - g0;
-  if (ng == 0) return MIA_OK;
-  if (!X || !Xa || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
-  if (ldx < g1 || ldo < o0 + ng) return MIA_ERR_SIZE;
-  if (p_max > p_cap) p_max = p_cap;
-  if (P > 0 && !rec) return MIA_ERR_NULL;
-  return cheb_analysis_launch(X, ldx, m, k, g0, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor,
+  const int rc = tile_entry_checks(0, X, ldx, m, k, g0, g1, rec, P, nbr_cnt, nbr_idx, nbr_w, p_cap, &p_max, inf_factor,
+                                   gamma, Xa, ldo, o0, flags, flags, retry_count);
+  if (rc != kLaunch) return rc;
+  return cheb_analysis_launch(X, ldx, m, k, g0, g1 - g0, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor,
                               gamma > 0.0f ? 1 : 0, gamma, Xa, ldo, o0, flags, retry_count, nullptr, nullptr,
                               (hipStream_t)stream);
 }
@@ -252,15 +286,10 @@ extern "C" int mia_letkf_weights_matfun_f32(const float* X, int64_t ldx, int m, 
                                             float inf_factor, float gamma, float* Xa, int64_t ldo, int64_t o0, float* W,
                                             int32_t* flags, int32_t* retry_count, void* stream) {
   (void)hipGetLastError();
-  if (g1 < g0 || g0 < 0 || m < 1 || k < 2 || P < 0 || p_cap < 1 || p_max < 0) return MIA_ERR_SIZE;
-  if (!(inf_factor > 0.0f)) return MIA_ERR_SIZE;
-  const int64_t ng = g1 - g0;
-  if (ng == 0) return MIA_OK;
-  if (!X || !Xa || !W || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
-  if (ldx < g1 || ldo < o0 + ng) return MIA_ERR_SIZE;
-  if (p_max > p_cap) p_max = p_cap;
-  if (P > 0 && !rec) return MIA_ERR_NULL;
-  return cheb_analysis_launch(X, ldx, m, k, g0, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor,
+  const int rc = tile_entry_checks(0, X, ldx, m, k, g0, g1, rec, P, nbr_cnt, nbr_idx, nbr_w, p_cap, &p_max, inf_factor,
+                                   gamma, Xa, ldo, o0, W, flags, retry_count);
+  if (rc != kLaunch) return rc;
+  return cheb_analysis_launch(X, ldx, m, k, g0, g1 - g0, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor,
                               gamma > 0.0f ? 1 : 0, gamma, Xa, ldo, o0, flags, retry_count, nullptr, nullptr,
                               (hipStream_t)stream, 0, 0, nullptr, W);
 }
@@ -292,16 +321,10 @@ extern "C" int mia_letkf_analysis_matfun_f64(const double* X, int64_t ldx, int m
                                              double inf_factor, double gamma, double* Xa, int64_t ldo, int64_t o0,
                                              int32_t* flags, int32_t* retry_count, void* stream) {
   (void)hipGetLastError();
-  if (g1 < g0 || g0 < 0 || m < 1 || k < 2 || P < 0 || p_cap < 1 || p_max < 0) return MIA_ERR_SIZE;
-  if (!(inf_factor > 0.0)) return MIA_ERR_SIZE;
-  if (gamma > 0.0) return MIA_ERR_UNSUPPORTED;       // the float64 RBF filter stays on mia_letkf_analysis_packed_f64
-  const int64_t ng = g1 - g0;
-  if (ng == 0) return MIA_OK;
-  if (!X || !Xa || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
-  if (ldx < g1 || ldo < o0 + ng) return MIA_ERR_SIZE;
-  if (p_max > p_cap) p_max = p_cap;
-  if (P > 0 && !rec) return MIA_ERR_NULL;
-  return tile64_analysis_launch(X, ldx, m, k, g0, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, Xa, ldo, o0,
+  const int rc = tile_entry_checks(kGammaRefused, X, ldx, m, k, g0, g1, rec, P, nbr_cnt, nbr_idx, nbr_w, p_cap, &p_max, inf_factor,
+                                   gamma, Xa, ldo, o0, flags, flags, retry_count);
+  if (rc != kLaunch) return rc;
+  return tile64_analysis_launch(X, ldx, m, k, g0, g1 - g0, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, Xa, ldo, o0,
                                 flags, retry_count, (hipStream_t)stream);
 }
 // float64 on tiles for dense local networks, p_max > k (letkf_dense64.hip): the same validation, then the one kernel of the route
@@ -311,16 +334,10 @@ extern "C" int mia_letkf_analysis_dense_f64(const double* X, int64_t ldx, int m,
                                             double inf_factor, double gamma, double* Xa, int64_t ldo, int64_t o0,
                                             int32_t* flags, int32_t* retry_count, void* stream) {
   (void)hipGetLastError();
-  if (g1 < g0 || g0 < 0 || m < 1 || k < 2 || P < 0 || p_cap < 1 || p_max < 0) return MIA_ERR_SIZE;
-  if (!(inf_factor > 0.0)) return MIA_ERR_SIZE;
-  if (gamma > 0.0) return MIA_ERR_UNSUPPORTED;       // the float64 RBF filter stays on mia_letkf_analysis_packed_f64
-  const int64_t ng = g1 - g0;
-  if (ng == 0) return MIA_OK;
-  if (!X || !Xa || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
-  if (ldx < g1 || ldo < o0 + ng) return MIA_ERR_SIZE;
-  if (p_max > p_cap) p_max = p_cap;
-  if (P > 0 && !rec) return MIA_ERR_NULL;
-  return dense64_analysis_launch(X, ldx, m, k, g0, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, Xa, ldo, o0,
+  const int rc = tile_entry_checks(kGammaRefused, X, ldx, m, k, g0, g1, rec, P, nbr_cnt, nbr_idx, nbr_w, p_cap, &p_max, inf_factor,
+                                   gamma, Xa, ldo, o0, flags, flags, retry_count);
+  if (rc != kLaunch) return rc;
+  return dense64_analysis_launch(X, ldx, m, k, g0, g1 - g0, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, Xa, ldo, o0,
                                  flags, retry_count, (hipStream_t)stream);
 }
 extern "C" int mia_letkf_dense_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P) {
@@ -336,16 +353,10 @@ extern "C" int mia_letkf_analysis_patch_f64(const double* X, int64_t ldx, int m,
                                             int32_t* flags, int32_t* retry_count, const int32_t* tile_pts, int64_t n_tiles,
                                             int union_blocks, void* stream) {
   (void)hipGetLastError();
-  if (g1 < g0 || g0 < 0 || m < 1 || k < 2 || P < 0 || p_cap < 1 || p_max < 0 || n_tiles < 0 || union_blocks < 1) return MIA_ERR_SIZE;
-  if (!(inf_factor > 0.0)) return MIA_ERR_SIZE;
-  if (gamma > 0.0) return MIA_ERR_UNSUPPORTED;       // the float64 RBF filter stays on mia_letkf_analysis_packed_f64
-  const int64_t ng = g1 - g0;
-  if (ng == 0) return MIA_OK;
-  if (!X || !Xa || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count || !tile_pts) return MIA_ERR_NULL;
-  if (ldx < g1 || ldo < o0 + ng || n_tiles == 0) return MIA_ERR_SIZE;
-  if (p_max > p_cap) p_max = p_cap;
-  if (P > 0 && !rec) return MIA_ERR_NULL;
-  return patch64_analysis_launch(X, ldx, m, k, g0, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, Xa, ldo, o0,
+  const int rc = tile_entry_checks(kGammaRefused, X, ldx, m, k, g0, g1, rec, P, nbr_cnt, nbr_idx, nbr_w, p_cap, &p_max, inf_factor,
+                                   gamma, Xa, ldo, o0, tile_pts, flags, retry_count, nullptr, 0, n_tiles, union_blocks);
+  if (rc != kLaunch) return rc;
+  return patch64_analysis_launch(X, ldx, m, k, g0, g1 - g0, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, Xa, ldo, o0,
                                  flags, retry_count, tile_pts, n_tiles, union_blocks, (hipStream_t)stream);
 }
 extern "C" int mia_letkf_patch_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P) {
@@ -376,16 +387,10 @@ extern "C" int mia_letkf_analysis_stream_f64(const double* X, int64_t ldx, int m
                                              double inf_factor, double gamma, double* Xa, int64_t ldo, int64_t o0,
                                              int32_t* flags, int32_t* retry_count, void* stream) {
   (void)hipGetLastError();
-  if (g1 < g0 || g0 < 0 || m < 1 || k < 2 || P < 0 || p_cap < 1 || p_max < 0) return MIA_ERR_SIZE;
-  if (!(inf_factor > 0.0)) return MIA_ERR_SIZE;
-  if (gamma > 0.0) return MIA_ERR_UNSUPPORTED;       // the float64 RBF filter stays on mia_letkf_analysis_packed_f64
-  const int64_t ng = g1 - g0;
-  if (ng == 0) return MIA_OK;
-  if (!X || !Xa || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
-  if (ldx < g1 || ldo < o0 + ng) return MIA_ERR_SIZE;
-  if (p_max > p_cap) p_max = p_cap;
-  if (P > 0 && !rec) return MIA_ERR_NULL;
-  return stream64_analysis_launch(X, ldx, m, k, g0, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, Xa, ldo, o0,
+  const int rc = tile_entry_checks(kGammaRefused, X, ldx, m, k, g0, g1, rec, P, nbr_cnt, nbr_idx, nbr_w, p_cap, &p_max, inf_factor,
+                                   gamma, Xa, ldo, o0, flags, flags, retry_count);
+  if (rc != kLaunch) return rc;
+  return stream64_analysis_launch(X, ldx, m, k, g0, g1 - g0, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, Xa, ldo, o0,
                                   flags, retry_count, (hipStream_t)stream);
 }
 extern "C" int mia_letkf_stream_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P) {
@@ -399,16 +404,10 @@ extern "C" int mia_letkf_analysis_wide_f64(const double* X, int64_t ldx, int m, 
                                            double inf_factor, double gamma, double* Xa, int64_t ldo, int64_t o0,
                                            int32_t* flags, int32_t* retry_count, void* stream) {
   (void)hipGetLastError();
-  if (g1 < g0 || g0 < 0 || m < 1 || k < 2 || P < 0 || p_cap < 1 || p_max < 0) return MIA_ERR_SIZE;
-  if (!(inf_factor > 0.0)) return MIA_ERR_SIZE;
-  if (gamma > 0.0) return MIA_ERR_UNSUPPORTED;       // the float64 RBF filter stays on mia_letkf_analysis_packed_f64
-  const int64_t ng = g1 - g0;
-  if (ng == 0) return MIA_OK;
-  if (!X || !Xa || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
-  if (ldx < g1 || ldo < o0 + ng) return MIA_ERR_SIZE;
-  if (p_max > p_cap) p_max = p_cap;
-  if (P > 0 && !rec) return MIA_ERR_NULL;
-  return wide64_analysis_launch(X, ldx, m, k, g0, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, Xa, ldo, o0,
+  const int rc = tile_entry_checks(kGammaRefused, X, ldx, m, k, g0, g1, rec, P, nbr_cnt, nbr_idx, nbr_w, p_cap, &p_max, inf_factor,
+                                   gamma, Xa, ldo, o0, flags, flags, retry_count);
+  if (rc != kLaunch) return rc;
+  return wide64_analysis_launch(X, ldx, m, k, g0, g1 - g0, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, Xa, ldo, o0,
                                 flags, retry_count, (hipStream_t)stream);
 }
 extern "C" int mia_letkf_wide_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P) {
@@ -423,16 +422,10 @@ extern "C" int mia_lketkf_rbf_analysis_matfun_f64(const double* X, int64_t ldx, 
                                                   double inf_factor, double gamma, double* Xa, int64_t ldo, int64_t o0,
                                                   int32_t* flags, int32_t* retry_count, void* stream) {
   (void)hipGetLastError();
-  if (g1 < g0 || g0 < 0 || m < 1 || k < 2 || P < 0 || p_cap < 1 || p_max < 0) return MIA_ERR_SIZE;
-  if (!(inf_factor > 0.0)) return MIA_ERR_SIZE;
-  if (!(gamma > 0.0)) return MIA_ERR_SIZE;
-  const int64_t ng = g1 - g0;
-  if (ng == 0) return MIA_OK;
-  if (!X || !Xa || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
-  if (ldx < g1 || ldo < o0 + ng) return MIA_ERR_SIZE;
-  if (p_max > p_cap) p_max = p_cap;
-  if (P > 0 && !rec) return MIA_ERR_NULL;
-  return rbf64_analysis_launch(X, ldx, m, k, g0, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, gamma, Xa, ldo, o0,
+  const int rc = tile_entry_checks(kGammaRequired, X, ldx, m, k, g0, g1, rec, P, nbr_cnt, nbr_idx, nbr_w, p_cap, &p_max, inf_factor,
+                                   gamma, Xa, ldo, o0, flags, flags, retry_count);
+  if (rc != kLaunch) return rc;
+  return rbf64_analysis_launch(X, ldx, m, k, g0, g1 - g0, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, gamma, Xa, ldo, o0,
                                flags, retry_count, (hipStream_t)stream);
 }
 extern "C" int mia_lketkf_rbf_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P) {
@@ -447,17 +440,10 @@ extern "C" int mia_lketkf_kernel_analysis_matfun_f64(const double* X, int64_t ld
                                                      double inf_factor, const mia_kernel_op_t* prog, int n_ops, double* Xa,
                                                      int64_t ldo, int64_t o0, int32_t* flags, int32_t* retry_count, void* stream) {
   (void)hipGetLastError();
-  if (g1 < g0 || g0 < 0 || m < 1 || k < 2 || P < 0 || p_cap < 1 || p_max < 0) return MIA_ERR_SIZE;
-  if (!(inf_factor > 0.0)) return MIA_ERR_SIZE;
-  const int rc = kernel_program_check(prog, n_ops);
-  if (rc != MIA_OK) return rc;
-  const int64_t ng = g1 - g0;
-  if (ng == 0) return MIA_OK;
-  if (!X || !Xa || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
-  if (ldx < g1 || ldo < o0 + ng) return MIA_ERR_SIZE;
-  if (p_max > p_cap) p_max = p_cap;
-  if (P > 0 && !rec) return MIA_ERR_NULL;
-  return kern64_analysis_launch(X, ldx, m, k, g0, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, prog, n_ops, Xa, ldo,
+  const int rc = tile_entry_checks(kProgram, X, ldx, m, k, g0, g1, rec, P, nbr_cnt, nbr_idx, nbr_w, p_cap, &p_max, inf_factor,
+                                   0.0, Xa, ldo, o0, flags, flags, retry_count, prog, n_ops);
+  if (rc != kLaunch) return rc;
+  return kern64_analysis_launch(X, ldx, m, k, g0, g1 - g0, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, prog, n_ops, Xa, ldo,
                                 o0, flags, retry_count, (hipStream_t)stream);
 }
 extern "C" int mia_lketkf_kernel_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P) {
@@ -498,16 +484,10 @@ extern "C" int mia_letkf_weights_matfun_f64(const double* X, int64_t ldx, int m,
                                             double inf_factor, double gamma, double* Xa, int64_t ldo, int64_t o0, double* W,
                                             int32_t* flags, int32_t* retry_count, void* stream) {
   (void)hipGetLastError();
-  if (g1 < g0 || g0 < 0 || m < 1 || k < 2 || P < 0 || p_cap < 1 || p_max < 0) return MIA_ERR_SIZE;
-  if (!(inf_factor > 0.0)) return MIA_ERR_SIZE;
-  if (gamma > 0.0) return MIA_ERR_UNSUPPORTED;       // the float64 RBF filter stays on mia_letkf_analysis_packed_f64
-  const int64_t ng = g1 - g0;
-  if (ng == 0) return MIA_OK;
-  if (!W || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
-  if ((X && ldx < g1) || (Xa && ldo < o0 + ng)) return MIA_ERR_SIZE;
-  if (p_max > p_cap) p_max = p_cap;
-  if (P > 0 && !rec) return MIA_ERR_NULL;
-  return weights64_launch(k, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, W, flags, retry_count,
+  const int rc = tile_entry_checks(kGammaRefused | kStateOptional, X, ldx, m, k, g0, g1, rec, P, nbr_cnt, nbr_idx, nbr_w, p_cap, &p_max, inf_factor,
+                                   gamma, Xa, ldo, o0, W, flags, retry_count);
+  if (rc != kLaunch) return rc;
+  return weights64_launch(k, g1 - g0, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, W, flags, retry_count,
                           (hipStream_t)stream);
 }
 extern "C" int mia_letkf_weights_retry_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
@@ -532,16 +512,10 @@ extern "C" int mia_letkf_weights_wide_f64(const double* X, int64_t ldx, int m, i
                                           double inf_factor, double gamma, double* Xa, int64_t ldo, int64_t o0, double* W,
                                           int32_t* flags, int32_t* retry_count, void* stream) {
   (void)hipGetLastError();
-  if (g1 < g0 || g0 < 0 || m < 1 || k < 2 || P < 0 || p_cap < 1 || p_max < 0) return MIA_ERR_SIZE;
-  if (!(inf_factor > 0.0)) return MIA_ERR_SIZE;
-  if (gamma > 0.0) return MIA_ERR_UNSUPPORTED;       // the float64 RBF filter stays on mia_letkf_analysis_packed_f64
-  const int64_t ng = g1 - g0;
-  if (ng == 0) return MIA_OK;
-  if (!W || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
-  if ((X && ldx < g1) || (Xa && ldo < o0 + ng)) return MIA_ERR_SIZE;
-  if (p_max > p_cap) p_max = p_cap;
-  if (P > 0 && !rec) return MIA_ERR_NULL;
-  return weights_wide64_launch(k, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, W, flags, retry_count,
+  const int rc = tile_entry_checks(kGammaRefused | kStateOptional, X, ldx, m, k, g0, g1, rec, P, nbr_cnt, nbr_idx, nbr_w, p_cap, &p_max, inf_factor,
+                                   gamma, Xa, ldo, o0, W, flags, retry_count);
+  if (rc != kLaunch) return rc;
+  return weights_wide64_launch(k, g1 - g0, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, W, flags, retry_count,
                                (hipStream_t)stream);
 }
 extern "C" int mia_letkf_weights_wide_f64_cover(int k, int p_max, int64_t n_points, int64_t P) {
@@ -556,16 +530,10 @@ extern "C" int mia_letkf_weights_stream_f64(const double* X, int64_t ldx, int m,
                                             double inf_factor, double gamma, double* Xa, int64_t ldo, int64_t o0, double* W,
                                             int32_t* flags, int32_t* retry_count, void* stream) {
   (void)hipGetLastError();
-  if (g1 < g0 || g0 < 0 || m < 1 || k < 2 || P < 0 || p_cap < 1 || p_max < 0) return MIA_ERR_SIZE;
-  if (!(inf_factor > 0.0)) return MIA_ERR_SIZE;
-  if (gamma > 0.0) return MIA_ERR_UNSUPPORTED;       // the float64 RBF filter stays on mia_letkf_analysis_packed_f64
-  const int64_t ng = g1 - g0;
-  if (ng == 0) return MIA_OK;
-  if (!W || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
-  if ((X && ldx < g1) || (Xa && ldo < o0 + ng)) return MIA_ERR_SIZE;
-  if (p_max > p_cap) p_max = p_cap;
-  if (P > 0 && !rec) return MIA_ERR_NULL;
-  return weights_stream64_launch(k, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, W, flags, retry_count,
+  const int rc = tile_entry_checks(kGammaRefused | kStateOptional, X, ldx, m, k, g0, g1, rec, P, nbr_cnt, nbr_idx, nbr_w, p_cap, &p_max, inf_factor,
+                                   gamma, Xa, ldo, o0, W, flags, retry_count);
+  if (rc != kLaunch) return rc;
+  return weights_stream64_launch(k, g1 - g0, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, W, flags, retry_count,
                                  (hipStream_t)stream);
 }
 extern "C" int mia_letkf_weights_stream_f64_cover(int k, int p_max, int64_t n_points, int64_t P) {

@@ -609,7 +609,7 @@ static int lienks_stream64_blocks(int p_max) {
 }
 
 // weights_stream64_route_covers' arithmetic
-static bool lienks_stream64_route_covers(int k, int p_max, int64_t ng) {
+bool lienks_stream64_route_covers(int k, int p_max, int64_t ng) {
   if (k < 2 || k > kLienksStream64MaxK || p_max <= k || ng < 0) return false;           // p_max <= k: the dual routes
   if (p_max > 16 * kLienksStream64MaxBlocks) return false;
   // a pass addresses W as wave-uniform base (tile, row) + 32-bit byte offset inside the tile's sixteen matrices
@@ -634,9 +634,9 @@ static int lienks_stream64_launch_t(const LienksStream64Params& dp, hipStream_t 
   return MIA_OK;
 }
 
-static int lienks_stream64_launch(const double* W_in, int64_t w_stride, int k, int64_t ng, const double* rec,
-                                  const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
-                                  double epsilon, double* W_out, int32_t* flags, int32_t* retry_count, hipStream_t stream) {
+int lienks_stream64_launch(const double* W_in, int64_t w_stride, int k, int64_t ng, const double* rec,
+                           const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                           double epsilon, double* W_out, int32_t* flags, int32_t* retry_count, hipStream_t stream) {
   if (!option(MIA_OPT_TILE) || !W_in || !W_out || !flags || !retry_count) return MIA_ERR_UNSUPPORTED;
   if (w_stride != 0 && w_stride != (int64_t)k * k) return MIA_ERR_UNSUPPORTED;
   if (!lienks_stream64_route_covers(k, p_max, ng)) return MIA_ERR_UNSUPPORTED;
@@ -673,28 +673,3 @@ static int lienks_stream64_launch(const double* W_in, int64_t w_stride, int k, i
 }
 
 }  // namespace mia
-
-using namespace mia;
-
-// tau = 1 in float64 on tiles for dense local networks of up to 128 members: mia_lienks_update_matfun_f64's validation in its
-// order, then the option and the cover -- nothing is dereferenced before them -- then the one kernel of the route
-extern "C" int mia_lienks_update_stream_f64(const double* W_in, int64_t w_stride, int k, int64_t g0, int64_t g1,
-                                            const double* rec, int64_t P, const int32_t* nbr_cnt, const int32_t* nbr_idx,
-                                            const double* nbr_w, int p_cap, int p_max, double epsilon, double* W_out,
-                                            int32_t* flags, int32_t* retry_count, void* stream) {
-  (void)hipGetLastError();
-  if (g1 < g0 || g0 < 0 || k < 2 || P < 0 || p_cap < 1 || p_max < 0) return MIA_ERR_SIZE;
-  if (w_stride != 0 && w_stride != (int64_t)k * k) return MIA_ERR_SIZE;
-  const int64_t ng = g1 - g0;
-  if (ng == 0) return MIA_OK;
-  if (!W_in || !W_out || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
-  if (P > 0 && !rec) return MIA_ERR_NULL;
-  if (p_max > p_cap) p_max = p_cap;
-  return lienks_stream64_launch(W_in, w_stride, k, ng, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, epsilon, W_out, flags,
-                                retry_count, (hipStream_t)stream);
-}
-extern "C" int mia_lienks_update_stream_f64_cover(int k, int p_max, int64_t n_points, int64_t P) {
-  if (P < 0) return 0;
-  return lienks_stream64_route_covers(k, p_max, n_points) ? 1 : 0;
-}
-

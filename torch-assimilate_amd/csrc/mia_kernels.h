@@ -174,6 +174,15 @@ int lienks_wide64_launch(const double* W_in, int64_t w_stride, int k, int64_t ng
                          const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max, double epsilon, double* W_out,
                          int32_t* flags, int32_t* retry_count, hipStream_t stream);
 
+// lienks_stream64.hip: the same update for DENSE local networks on letkf_stream64w.hip's frame (2 <= k <= 128,
+// k < p_max <= 256), the union's records streamed through a ring in LDS.  lienks_stream64_route_covers: shape test (host
+// only; weights_stream64_route_covers' arithmetic); lienks_stream64_launch: MIA_ERR_UNSUPPORTED outside it, with the option
+// tile = 0, and when the float64 coefficient table cannot be had.
+bool lienks_stream64_route_covers(int k, int p_max, int64_t ng);
+int lienks_stream64_launch(const double* W_in, int64_t w_stride, int k, int64_t ng, const double* rec, const int32_t* nbr_cnt,
+                           const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max, double epsilon, double* W_out,
+                           int32_t* flags, int32_t* retry_count, hipStream_t stream);
+
 // lketkf_tile64.hip: the float64 RBF-kernelised analysis on tiles (2 <= k <= 40, lists of at most 64 observations, any number
 // of state rows; no p_max <= k condition): one workgroup of four wavefronts per tile, the pair statistic on the matrix
 // cores, a point's k x k matrix in LDS.  rbf64_route_covers: shape test (host only, the LDS of the chosen instantiation

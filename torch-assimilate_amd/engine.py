@@ -21,6 +21,31 @@ def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _one_of(names) -> str:
+    """'a', 'b' or 'c' for an error message."""
+    return ", ".join(repr(v) for v in names[:-1]) + " or " + repr(names[-1])
+
+
+def _result(out, W, flags, finish, defer_retry):
+    """What a route returns.  ``finish`` (None: no kernel that declines points ran) is the redo behind the decline counter: it
+    runs now unless the caller defers it, and a deferring caller always gets a callable.  Then out [, W] [, flags] [, finish],
+    each where it is not None, unwrapped when it is one object."""
+    if not defer_retry:
+        if finish is not None:
+            finish()
+        if W is None and flags is None:
+            return out
+        finish = None
+    elif finish is None:
+        finish = _nothing_declined
+    res = tuple(v for v in (out, W, flags, finish) if v is not None)
+    return res[0] if len(res) == 1 else res
+
+
+def _nothing_declined() -> int:
+    return 0
+
+
 MIA_FLAG_NOCONV = 2     # include/mia_letkf.h
 MIA_TILEMAP_FAULTS = ((1, "an entry outside [-1, n)"), (2, "a point that occurs more than once"),
                       (4, "a point that does not occur"))     # MIA_TILEMAP_* (include/mia_letkf.h)
@@ -176,6 +201,18 @@ class LetkfEngine:
     def _dev(self, a, dtype):
         t = torch.as_tensor(a)
         return t.to(device=self.device, dtype=dtype).contiguous()
+
+    def _redo_behind_counter(self, retry: torch.Tensor, entry: str, redo_args, alive=()):
+        """The ``finish`` callable of a route whose kernel may decline points: it reads the decline counter ``retry`` (8 bytes,
+        synchronising) and, where points were declined, calls the redo ``entry`` with ``redo_args()`` and the stream; it returns
+        the number of points redone.  The arguments are addresses: ``alive`` holds the arrays behind them until a deferred
+        redo has run."""
+        def finish(_alive=alive):
+            n_retry = int(retry.item())          # host sync (8 bytes)
+            if n_retry:
+                _cabi.check(getattr(self.lib, entry)(*redo_args(), self._stream()), entry)
+            return n_retry
+        return finish
 
     # ------------------------------------------------------------ localisation
     def gaspari_cohn(self, r: torch.Tensor, taper: int = 0) -> torch.Tensor:
@@ -767,6 +804,31 @@ class LetkfEngine:
     def _kern64_auto(self, m: int, k: int, p_max: int) -> bool:
         return k >= self.KERN64_AUTO_MIN_K and m <= self.KERN64_AUTO_MAX_ROWS and p_max <= self.KERN64_AUTO_MAX_P
 
+    def _rbf64_auto(self, m: int, k: int, p_max: int) -> bool:
+        return k >= self.RBF64_AUTO_MIN_K and ((m == 1 and p_max <= self.RBF64_AUTO_MAX_P) or
+                                               (m <= self.RBF64_AUTO_MAX_ROWS and p_max <= self.RBF64_AUTO_MAX_P_ROWS))
+
+    def _matfun64_auto(self, m: int, k: int, p_max: int) -> bool:
+        return True           # (the entry's own cover is the rule: p_max <= k <= 64)
+
+    def _dense64_auto(self, m: int, k: int, p_max: int) -> bool:
+        return self.DENSE64_AUTO_DEN * p_max <= self.DENSE64_AUTO_NUM * k and m <= self.DENSE64_AUTO_MAX_ROWS
+
+    def _wide64_auto(self, m: int, k: int, p_max: int) -> bool:
+        return k >= self.WIDE64_AUTO_MIN_K and m <= self.WIDE64_AUTO_MAX_ROWS
+
+    ANALYSIS_METHODS = ("auto", "eig", "matfun", "matfun64", "dense64", "patch64", "wide64", "stream64", "rbf64", "kern64")
+    # the float64 plain-core tile routes in the order in which "auto" tries them: (method, C entry, its rule under "auto").
+    # A route answers MIA_ERR_UNSUPPORTED (-3) outside its cover and the walk goes on; patch64 is the one row with steps of its
+    # own in front of the entry (the caller's tile map, the cover, the census).  A new route is one row here, its entry in
+    # csrc/letkf_entry.hip and its prototype in _cabi._PROTOS
+    TILE64_ROUTES = (("matfun64", "mia_letkf_analysis_matfun_f64", _matfun64_auto),
+                     ("patch64", "mia_letkf_analysis_patch_f64", _patch64_auto),
+                     ("dense64", "mia_letkf_analysis_dense_f64", _dense64_auto),
+                     ("wide64", "mia_letkf_analysis_wide_f64", _wide64_auto),
+                     ("stream64", "mia_letkf_analysis_stream_f64", _stream64_auto))
+    TILE64_METHODS = tuple(r[0] for r in TILE64_ROUTES)
+
     def analysis(self, X: torch.Tensor, Yb: Optional[torch.Tensor], d: Optional[torch.Tensor],
                  nbrs: NeighbourLists, inf_factor: float = 1.0, return_weights: bool = False,
                  rbf_gamma: Optional[float] = None, out: Optional[torch.Tensor] = None, out_offset: int = 0,
@@ -836,9 +898,8 @@ class LetkfEngine:
             self._keep_rec = rec      # (a record buffer packed during HIP-graph capture must outlive the capture)
         if rec.dtype != dtype or rec.shape[1] != (k + 1 + 3) // 4 * 4:
             raise ValueError("packed records do not match the state's dtype / ensemble size")
-        if method not in ("auto", "eig", "matfun", "matfun64", "dense64", "patch64", "wide64", "stream64", "rbf64", "kern64"):
-            raise ValueError("method must be 'auto', 'eig', 'matfun', 'matfun64', 'dense64', 'patch64', 'wide64', 'stream64', "
-                             "'rbf64' or 'kern64'")
+        if method not in self.ANALYSIS_METHODS:
+            raise ValueError("method must be " + _one_of(self.ANALYSIS_METHODS))
         if method == "patch64" and tile_points is None:
             raise ValueError("the patch64 route needs tile_points (see mesh_tiles)")
         # float64 RBF-kernelised filter on tiles (csrc/lketkf_tile64.hip): 2 <= k <= 40, lists of at most 64 observations, no weights
@@ -865,6 +926,9 @@ class LetkfEngine:
         gamma = float(rbf_gamma) if rbf_gamma is not None else 0.0
         args = (_ptr(X), G, m, k, nbrs.g0, nbrs.g1, _ptr(rec), P, _ptr(nbrs.cnt), _ptr(nbrs.idx),
                 _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max, float(inf_factor), gamma, _ptr(out), ldo, out_offset)
+        alive = (X, rec, out, W, flags, nbrs)      # (args holds addresses: a deferred redo must find the arrays alive)
+
+        flags_out = flags if return_flags else None
         if kernel_program is not None:
             if rbf_gamma is not None:
                 raise ValueError("give rbf_gamma or kernel_program, not both")
@@ -882,150 +946,119 @@ class LetkfEngine:
                     pass
                 else:
                     _cabi.check(rc, "mia_lketkf_kernel_analysis_matfun_f64")
-
-                    def finish(_alive=(X, rec, out, nbrs)):   # (pargs holds addresses: a deferred redo must find the arrays alive)
-                        n_retry = int(retry.item())          # host sync (8 bytes)
-                        if n_retry:
-                            _cabi.check(self.lib.mia_lketkf_kernel_analysis_retry_f64(*pargs, _ptr(flags), self._stream()),
-                                        "mia_lketkf_kernel_analysis_retry_f64")
-                        return n_retry
+                    finish = self._redo_behind_counter(retry, "mia_lketkf_kernel_analysis_retry_f64",
+                                                       lambda: (*pargs, _ptr(flags)), alive)
             if finish is None:
                 fn = getattr(self.lib, "mia_lketkf_kernel_analysis_packed_" + sfx)
                 _cabi.check(fn(*pargs, _ptr(W), _ptr(flags), self._stream()), "mia_lketkf_kernel_analysis_packed_" + sfx)
-            elif not defer_retry:
-                finish()
-            res = [out]
-            if return_weights:
-                res.append(W)
-            if return_flags:
-                res.append(flags)
-            if defer_retry:
-                res.append(finish if finish is not None else (lambda: 0))
-            return res[0] if len(res) == 1 else tuple(res)
+            return _result(out, W, flags_out, finish, defer_retry)
         if (return_weights and dtype == torch.float32 and method != "eig" and n > 0):
             # weights without an eigensolver (dual route, order <= 32); -3 = shape outside that kernel
             if retry is None:
                 retry = torch.zeros(1, dtype=torch.int32, device=self.device)
-            wargs = args        # (..., inf_factor, gamma, Xa, ldo, o0)
-            rc = self.lib.mia_letkf_weights_matfun_f32(*wargs, _ptr(W), _ptr(flags), _ptr(retry), self._stream())
+            rc = self.lib.mia_letkf_weights_matfun_f32(*args, _ptr(W), _ptr(flags), _ptr(retry), self._stream())
             if rc != -3:
                 _cabi.check(rc, "mia_letkf_weights_matfun_f32")
-
-                def finish_w():
-                    n_retry = int(retry.item())          # host sync (8 bytes)
-                    if n_retry:
-                        _cabi.check(self.lib.mia_letkf_weights_retry_f32(*wargs, _ptr(W), _ptr(flags), self._stream()),
-                                    "mia_letkf_weights_retry_f32")
-                    return n_retry
-                if not defer_retry:
-                    finish_w()
-                res = [out, W]
-                if return_flags:
-                    res.append(flags)
-                if defer_retry:
-                    res.append(finish_w)
-                return tuple(res)
+                return _result(out, W, flags_out, self._redo_behind_counter(
+                    retry, "mia_letkf_weights_retry_f32", lambda: (*args, _ptr(W), _ptr(flags)), alive), defer_retry)
         can_matfun = dtype == torch.float32 and not return_weights and n > 0
         if method == "matfun" and not can_matfun:
             raise ValueError("the matfun route needs float32 and cannot return the weights")
         # float64 on tiles (csrc/letkf_tile64.hip: p_max <= k <= 64; csrc/letkf_dense64.hip: p_max > k; csrc/letkf_wide64.hip:
-        # p_max <= k <= 128; csrc/letkf_stream64.hip: k < p_max <= 256, k <= 128): plain ETKF core, no weights.  "auto" tries the
-        # four in this order (the dense one up to p_max = 2.4 k, the wide one under WIDE64_AUTO_*, the streamed one under
-        # STREAM64_AUTO_*) and falls back to the Jacobi kernel elsewhere; "matfun64", "dense64", "wide64" and "stream64" name
-        # one route and raise there instead.
-        tile64_methods = ("matfun64", "dense64", "patch64", "wide64", "stream64")
+        # p_max <= k <= 128; csrc/letkf_stream64.hip: k < p_max <= 256, k <= 128): plain ETKF core, no weights.  "auto" walks
+        # TILE64_ROUTES in its order (the dense route up to p_max = 2.4 k, the wide one under WIDE64_AUTO_*, the streamed one
+        # under STREAM64_AUTO_*, the one with a map under PATCH64_AUTO_*) and falls back to the Jacobi kernel elsewhere; a
+        # route's own name takes that row alone and raises there instead.
         can_matfun64 = dtype == torch.float64 and not return_weights and rbf_gamma is None
-        if method in tile64_methods and not can_matfun64:
+        if method in self.TILE64_METHODS and not can_matfun64:
             raise ValueError("the %s route needs float64, the plain ETKF core and cannot return the weights" % method)
         use_matfun = can_matfun and (method == "matfun" or (method == "auto" and m <= self.MATFUN_MAX_ROWS))
-        finish = None
-        if can_matfun64 and n > 0 and method in ("auto",) + tile64_methods:
+        # the eigensolver-free entry that is tried, its status, and whether -3 (shape outside the kernel, or tile = 0) hands
+        # the shard to the Jacobi kernel below instead of raising
+        name, rc, soft = None, -3, method == "auto"
+        if can_matfun64 and n > 0 and (method == "auto" or method in self.TILE64_METHODS):
             if retry is None:
                 retry = torch.zeros(1, dtype=torch.int32, device=self.device)
-            rc, name = -3, "mia_letkf_analysis_matfun_f64"
-            if method in ("auto", "matfun64"):
-                rc = self.lib.mia_letkf_analysis_matfun_f64(*args, _ptr(flags), _ptr(retry), self._stream())
-            patch_ok = tile_points is not None and (method == "patch64" or (
-                method == "auto" and self._patch64_auto(m, k, nbrs.p_max)))
-            if rc == -3 and patch_ok:
-                name = "mia_letkf_analysis_patch_f64"
-                if self.lib.mia_letkf_patch_f64_cover(m, k, nbrs.p_max, G, ldo, n, P) == 1:
+            name = self.TILE64_ROUTES[0][1]
+            for meth, entry, auto in self.TILE64_ROUTES:
+                if rc != -3:
+                    break
+                if method != meth and not (method == "auto" and auto(self, m, k, nbrs.p_max)):
+                    continue
+                more = ()
+                if meth == "patch64":      # the row with steps of its own: the caller's map, the cover, the census (once per map)
+                    if tile_points is None:
+                        continue
+                    name = entry
+                    if self.lib.mia_letkf_patch_f64_cover(m, k, nbrs.p_max, G, ldo, n, P) != 1:
+                        continue
                     tp, ub, fits = self._patch64_map(nbrs, tile_points, union_blocks, k)
-                    if fits or method == "patch64":      # ("auto": a map whose tiles would run in parts is left to the rules below)
-                        rc = self.lib.mia_letkf_analysis_patch_f64(*args, _ptr(flags), _ptr(retry), _ptr(tp), tp.shape[0], ub,
-                                                                   self._stream())
-            dense_ok = method == "dense64" or (method == "auto" and self.DENSE64_AUTO_DEN * nbrs.p_max <= self.DENSE64_AUTO_NUM * k and
-                                               m <= self.DENSE64_AUTO_MAX_ROWS)
-            if rc == -3 and dense_ok:
-                name = "mia_letkf_analysis_dense_f64"
-                rc = self.lib.mia_letkf_analysis_dense_f64(*args, _ptr(flags), _ptr(retry), self._stream())
-            wide_ok = method == "wide64" or (method == "auto" and k >= self.WIDE64_AUTO_MIN_K and m <= self.WIDE64_AUTO_MAX_ROWS)
-            if rc == -3 and wide_ok:
-                name = "mia_letkf_analysis_wide_f64"
-                rc = self.lib.mia_letkf_analysis_wide_f64(*args, _ptr(flags), _ptr(retry), self._stream())
-            stream_ok = method == "stream64" or (method == "auto" and self._stream64_auto(m, k, nbrs.p_max))
-            if rc == -3 and stream_ok:
-                name = "mia_letkf_analysis_stream_f64"
-                rc = self.lib.mia_letkf_analysis_stream_f64(*args, _ptr(flags), _ptr(retry), self._stream())
-            if rc == -3 and method == "auto":      # shape outside the tile kernels (or tile = 0): the Jacobi kernel below
-                pass
-            else:
-                _cabi.check(rc, name)
-                use_matfun = True
-
-                def finish(_alive=(X, rec, out, nbrs)):   # (args holds addresses: a deferred redo must find the arrays alive)
-                    n_retry = int(retry.item())          # host sync (8 bytes)
-                    if n_retry:
-                        _cabi.check(self.lib.mia_letkf_analysis_retry_f64(*args, _ptr(flags), self._stream()),
-                                    "mia_letkf_analysis_retry_f64")
-                    return n_retry
-        elif can_rbf64 and n > 0 and (method == "rbf64" or (method == "auto" and k >= self.RBF64_AUTO_MIN_K and (
-                (m == 1 and nbrs.p_max <= self.RBF64_AUTO_MAX_P) or
-                (m <= self.RBF64_AUTO_MAX_ROWS and nbrs.p_max <= self.RBF64_AUTO_MAX_P_ROWS)))):
+                    if not fits and method != "patch64":      # ("auto": a map whose tiles would run in parts is left to the rows below)
+                        continue
+                    more = (_ptr(tp), tp.shape[0], ub)
+                name = entry
+                rc = getattr(self.lib, entry)(*args, _ptr(flags), _ptr(retry), *more, self._stream())
+        elif can_rbf64 and n > 0 and (method == "rbf64" or (method == "auto" and self._rbf64_auto(m, k, nbrs.p_max))):
             if retry is None:
                 retry = torch.zeros(1, dtype=torch.int32, device=self.device)
+            name = "mia_lketkf_rbf_analysis_matfun_f64"
             rc = self.lib.mia_lketkf_rbf_analysis_matfun_f64(*args, _ptr(flags), _ptr(retry), self._stream())
-            if rc == -3 and method == "auto":      # shape outside the kernel (or tile = 0): the Jacobi kernel below
-                pass
-            else:
-                _cabi.check(rc, "mia_lketkf_rbf_analysis_matfun_f64")
-                use_matfun = True
-
-                def finish():
-                    n_retry = int(retry.item())          # host sync (8 bytes)
-                    if n_retry:
-                        _cabi.check(self.lib.mia_letkf_analysis_retry_f64(*args, _ptr(flags), self._stream()),
-                                    "mia_letkf_analysis_retry_f64")
-                    return n_retry
         elif use_matfun:
             if retry is None:
                 retry = torch.zeros(1, dtype=torch.int32, device=self.device)
+            name, soft = "mia_letkf_analysis_matfun_f32", True      # (outside the matfun kernels: eigensolver route)
             rc = self.lib.mia_letkf_analysis_matfun_f32(*args, _ptr(flags), _ptr(retry), self._stream())
-            if rc == -3:              # shape outside the matfun kernels: eigensolver route
-                use_matfun = False
-            else:
-                _cabi.check(rc, "mia_letkf_analysis_matfun_f32")
-
-                def finish():
-                    n_retry = int(retry.item())          # host sync (8 bytes)
-                    if n_retry:
-                        _cabi.check(self.lib.mia_letkf_analysis_retry_f32(*args, _ptr(flags), self._stream()),
-                                    "mia_letkf_analysis_retry_f32")
-                    return n_retry
-        if not use_matfun:
+        if name is None or (rc == -3 and soft):
             fn = getattr(self.lib, "mia_letkf_analysis_packed_" + sfx)
             _cabi.check(fn(*args, _ptr(W), _ptr(flags), self._stream()), "mia_letkf_analysis_packed_" + sfx)
-        if finish is not None and not defer_retry:
-            finish()
-            finish = None
-        res = [out]
-        if return_weights:
-            res.append(W)
-        if return_flags:
-            res.append(flags)
-        if defer_retry:
-            res.append(finish if finish is not None else (lambda: 0))
-        return res[0] if len(res) == 1 else tuple(res)
+            return _result(out, W, flags_out, None, defer_retry)
+        _cabi.check(rc, name)
+        return _result(out, W, flags_out, self._redo_behind_counter(
+            retry, "mia_letkf_analysis_retry_" + sfx, lambda: (*args, _ptr(flags)), alive), defer_retry)
+
+    def _weights_tile64(self, entry: str, who: str, Yb, d, nbrs: NeighbourLists, inf_factor, rec, out, return_flags, defer_retry,
+                        rbf_gamma):
+        """The body of :meth:`weights64`, :meth:`weights_wide64` and :meth:`weights_stream64`: the C ``entry`` of the route
+        and the public method's name ``who`` for the messages; arguments and answers as documented there."""
+        if rec is None:
+            if Yb.dim() != 2 or Yb.dtype != torch.float64:
+                return None
+            rec = self.pack_obs(Yb, d, torch.float64)
+        if rec.dtype != torch.float64 or rec.dim() != 2 or rec.shape[1] < 3:
+            return None
+        kp = rec.shape[1]
+        k = int(Yb.shape[0]) if Yb is not None else (int(out.shape[-1]) if out is not None else None)
+        if k is None:
+            raise ValueError(who + " from packed records alone needs out= (n, k, k) for the ensemble size")
+        if kp != (k + 1 + 3) // 4 * 4:
+            raise ValueError("packed records do not match the ensemble size")
+        n = nbrs.g1 - nbrs.g0
+        if out is None:
+            out = torch.empty((n, k, k), dtype=torch.float64, device=self.device)
+        elif out.shape != (n, k, k) or out.dtype != torch.float64 or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float64 tensor (n, k, k)")
+        W = out
+        flags = torch.empty(n, dtype=torch.int32, device=self.device)
+        retry = torch.zeros(1, dtype=torch.int32, device=self.device)
+        gamma = float(rbf_gamma) if rbf_gamma is not None else 0.0
+
+        # the entry and the redo entry take (X, *shard, Xa, *tail): the tile kernel writes W and flags only, X = Xa = NULL
+        shard = (nbrs.g1, 1, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0], _ptr(nbrs.cnt), _ptr(nbrs.idx), _ptr(nbrs.w),
+                 nbrs.p_cap, nbrs.p_max, float(inf_factor), gamma)
+        tail = (n, 0, _ptr(W), _ptr(flags))
+        rc = getattr(self.lib, entry)(None, *shard, None, *tail, _ptr(retry), self._stream())
+        if rc == -3:
+            return None
+        _cabi.check(rc, entry)
+
+        def redo_args():
+            # the Jacobi kernel computes an analysis next to the weights: a one-row zero state and its output, from the
+            # workspace, and only now that a point needs them
+            x0 = self._workspace("weights64_x0", 8 * k * max(nbrs.g1, 1)).view(torch.float64)[:k * nbrs.g1].zero_()
+            xa = self._workspace("weights64_xa", 8 * k * max(n, 1)).view(torch.float64)
+            return (_ptr(x0), *shard, _ptr(xa), *tail)
+        finish = self._redo_behind_counter(retry, "mia_letkf_weights_retry_f64", redo_args, (rec, nbrs, W, flags))
+        return _result(W, None, flags if return_flags else None, finish, defer_retry)
 
     # LETKF.estimate_weights_arrays hands float64 weights to weights64 by default only from this ensemble size on.  Measured on
     # MI355X (tools/time_weights64.py, profiles/weights64_time.json, DESIGN 9), 1e5 points, against the Jacobi kernel with W:
@@ -1044,52 +1077,8 @@ class LetkfEngine:
         option tile = 0): the caller then takes ``analysis(..., return_weights=True)``.  Points the kernel declines are redone
         by the Jacobi kernel (mia_letkf_weights_retry_f64) behind the 8-byte read of the decline counter; with ``defer_retry``
         that read is left to the caller, who must invoke the trailing callable (it returns the number of points redone)."""
-        if rec is None:
-            if Yb.dim() != 2 or Yb.dtype != torch.float64:
-                return None
-            rec = self.pack_obs(Yb, d, torch.float64)
-        if rec.dtype != torch.float64 or rec.dim() != 2 or rec.shape[1] < 3:
-            return None
-        kp = rec.shape[1]
-        k = int(Yb.shape[0]) if Yb is not None else (int(out.shape[-1]) if out is not None else None)
-        if k is None:
-            raise ValueError("weights64 from packed records alone needs out= (n, k, k) for the ensemble size")
-        if kp != (k + 1 + 3) // 4 * 4:
-            raise ValueError("packed records do not match the ensemble size")
-        n = nbrs.g1 - nbrs.g0
-        if out is None:
-            out = torch.empty((n, k, k), dtype=torch.float64, device=self.device)
-        elif out.shape != (n, k, k) or out.dtype != torch.float64 or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float64 tensor (n, k, k)")
-        W = out
-        flags = torch.empty(n, dtype=torch.int32, device=self.device)
-        retry = torch.zeros(1, dtype=torch.int32, device=self.device)
-        gamma = float(rbf_gamma) if rbf_gamma is not None else 0.0
-
-        def args(X, Xa):      # (a closure over rec, the lists and W: a deferred retry finds them alive)
-            return (_ptr(X), nbrs.g1, 1, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0], _ptr(nbrs.cnt), _ptr(nbrs.idx),
-                    _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max, float(inf_factor), gamma, _ptr(Xa), n, 0, _ptr(W), _ptr(flags))
-        rc = self.lib.mia_letkf_weights_matfun_f64(*args(None, None), _ptr(retry), self._stream())
-        if rc == -3:
-            return None
-        _cabi.check(rc, "mia_letkf_weights_matfun_f64")
-
-        def finish():
-            n_retry = int(retry.item())          # host sync (8 bytes)
-            if n_retry:
-                # the Jacobi kernel computes an analysis next to the weights: a one-row zero state and its output, from the workspace
-                x0 = self._workspace("weights64_x0", 8 * k * max(nbrs.g1, 1)).view(torch.float64)[:k * nbrs.g1].zero_()
-                xa = self._workspace("weights64_xa", 8 * k * max(n, 1)).view(torch.float64)
-                _cabi.check(self.lib.mia_letkf_weights_retry_f64(*args(x0, xa), self._stream()), "mia_letkf_weights_retry_f64")
-            return n_retry
-        if not defer_retry:
-            finish()
-        res = [W]
-        if return_flags:
-            res.append(flags)
-        if defer_retry:
-            res.append(finish)
-        return res[0] if len(res) == 1 else tuple(res)
+        return self._weights_tile64("mia_letkf_weights_matfun_f64", "weights64", Yb, d, nbrs, inf_factor, rec, out, return_flags,
+                                    defer_retry, rbf_gamma)
 
     # LETKF.estimate_weights_arrays hands float64 weights of ensembles above weights64's 64 members to weights_wide64 from this
     # ensemble size on (the project's rule: the smallest MEASURED k from which every measured case is at least 2x the Jacobi
@@ -1114,53 +1103,8 @@ class LetkfEngine:
         ``defer_retry`` that read is left to the caller, who must invoke the trailing callable (it returns the number of points
         redone).  The Jacobi kernel holds about 70 local observations: a declined point with more makes the redo raise MiaError
         AFTER every other point has been written -- data-dependent, as ``analysis(method="wide64")`` documents for the analysis."""
-        if rec is None:
-            if Yb.dim() != 2 or Yb.dtype != torch.float64:
-                return None
-            rec = self.pack_obs(Yb, d, torch.float64)
-        if rec.dtype != torch.float64 or rec.dim() != 2 or rec.shape[1] < 3:
-            return None
-        kp = rec.shape[1]
-        k = int(Yb.shape[0]) if Yb is not None else (int(out.shape[-1]) if out is not None else None)
-        if k is None:
-            raise ValueError("weights_wide64 from packed records alone needs out= (n, k, k) for the ensemble size")
-        if kp != (k + 1 + 3) // 4 * 4:
-            raise ValueError("packed records do not match the ensemble size")
-        n = nbrs.g1 - nbrs.g0
-        if out is None:
-            out = torch.empty((n, k, k), dtype=torch.float64, device=self.device)
-        elif out.shape != (n, k, k) or out.dtype != torch.float64 or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float64 tensor (n, k, k)")
-        W = out
-        flags = torch.empty(n, dtype=torch.int32, device=self.device)
-        retry = torch.zeros(1, dtype=torch.int32, device=self.device)
-        gamma = float(rbf_gamma) if rbf_gamma is not None else 0.0
-
-        def args(X, Xa):      # (a closure over rec, the lists and W: a deferred retry finds them alive)
-            return (_ptr(X), nbrs.g1, 1, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0], _ptr(nbrs.cnt), _ptr(nbrs.idx),
-                    _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max, float(inf_factor), gamma, _ptr(Xa), n, 0, _ptr(W), _ptr(flags))
-        rc = self.lib.mia_letkf_weights_wide_f64(*args(None, None), _ptr(retry), self._stream())
-        if rc == -3:
-            return None
-        _cabi.check(rc, "mia_letkf_weights_wide_f64")
-
-        def finish():
-            n_retry = int(retry.item())          # host sync (8 bytes)
-            if n_retry:
-                # the Jacobi kernel computes an analysis next to the weights: a one-row zero state and its output, from the
-                # workspace, and only now that a point needs them
-                x0 = self._workspace("weights64_x0", 8 * k * max(nbrs.g1, 1)).view(torch.float64)[:k * nbrs.g1].zero_()
-                xa = self._workspace("weights64_xa", 8 * k * max(n, 1)).view(torch.float64)
-                _cabi.check(self.lib.mia_letkf_weights_retry_f64(*args(x0, xa), self._stream()), "mia_letkf_weights_retry_f64")
-            return n_retry
-        if not defer_retry:
-            finish()
-        res = [W]
-        if return_flags:
-            res.append(flags)
-        if defer_retry:
-            res.append(finish)
-        return res[0] if len(res) == 1 else tuple(res)
+        return self._weights_tile64("mia_letkf_weights_wide_f64", "weights_wide64", Yb, d, nbrs, inf_factor, rec, out, return_flags,
+                                    defer_retry, rbf_gamma)
 
     # LETKF.estimate_weights_arrays hands float64 weights of DENSE networks (p_max > k, which weights64 and weights_wide64
     # refuse) to weights_stream64 in two cases.  (1) Wherever the Jacobi kernel cannot hold the shape (_jacobi_primal_fits: from
@@ -1199,53 +1143,8 @@ class LetkfEngine:
         Jacobi kernel cannot hold a dense point from 97 members on: a declined point there makes the redo raise MiaError AFTER
         every other point has been written -- data-dependent, as ``analysis(method="stream64")`` documents for the analysis.
         A point without observations gets sqrt(inf_factor) I exactly and flag 0."""
-        if rec is None:
-            if Yb.dim() != 2 or Yb.dtype != torch.float64:
-                return None
-            rec = self.pack_obs(Yb, d, torch.float64)
-        if rec.dtype != torch.float64 or rec.dim() != 2 or rec.shape[1] < 3:
-            return None
-        kp = rec.shape[1]
-        k = int(Yb.shape[0]) if Yb is not None else (int(out.shape[-1]) if out is not None else None)
-        if k is None:
-            raise ValueError("weights_stream64 from packed records alone needs out= (n, k, k) for the ensemble size")
-        if kp != (k + 1 + 3) // 4 * 4:
-            raise ValueError("packed records do not match the ensemble size")
-        n = nbrs.g1 - nbrs.g0
-        if out is None:
-            out = torch.empty((n, k, k), dtype=torch.float64, device=self.device)
-        elif out.shape != (n, k, k) or out.dtype != torch.float64 or not out.is_contiguous():
-            raise ValueError("out must be a contiguous float64 tensor (n, k, k)")
-        W = out
-        flags = torch.empty(n, dtype=torch.int32, device=self.device)
-        retry = torch.zeros(1, dtype=torch.int32, device=self.device)
-        gamma = float(rbf_gamma) if rbf_gamma is not None else 0.0
-
-        def args(X, Xa):      # (a closure over rec, the lists and W: a deferred retry finds them alive)
-            return (_ptr(X), nbrs.g1, 1, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0], _ptr(nbrs.cnt), _ptr(nbrs.idx),
-                    _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max, float(inf_factor), gamma, _ptr(Xa), n, 0, _ptr(W), _ptr(flags))
-        rc = self.lib.mia_letkf_weights_stream_f64(*args(None, None), _ptr(retry), self._stream())
-        if rc == -3:
-            return None
-        _cabi.check(rc, "mia_letkf_weights_stream_f64")
-
-        def finish():
-            n_retry = int(retry.item())          # host sync (8 bytes)
-            if n_retry:
-                # the Jacobi kernel computes an analysis next to the weights: a one-row zero state and its output, from the
-                # workspace, and only now that a point needs them
-                x0 = self._workspace("weights64_x0", 8 * k * max(nbrs.g1, 1)).view(torch.float64)[:k * nbrs.g1].zero_()
-                xa = self._workspace("weights64_xa", 8 * k * max(n, 1)).view(torch.float64)
-                _cabi.check(self.lib.mia_letkf_weights_retry_f64(*args(x0, xa), self._stream()), "mia_letkf_weights_retry_f64")
-            return n_retry
-        if not defer_retry:
-            finish()
-        res = [W]
-        if return_flags:
-            res.append(flags)
-        if defer_retry:
-            res.append(finish)
-        return res[0] if len(res) == 1 else tuple(res)
+        return self._weights_tile64("mia_letkf_weights_stream_f64", "weights_stream64", Yb, d, nbrs, inf_factor, rec, out, return_flags,
+                                    defer_retry, rbf_gamma)
 
     # ------------------------------------------------------------------- IEnKS
     # ienks_update(method="auto") hands float64 updates with tau = 1 to the tile kernel (csrc/lienks_tile64.hip) only from this
@@ -1323,6 +1222,18 @@ class LetkfEngine:
         return (k >= self.IENKS_STREAM64_AUTO_MIN_K
                 and self.IENKS_STREAM64_AUTO_DEN * p_max <= self.IENKS_STREAM64_AUTO_NUM * k)
 
+    # the float64 tile kernels of ienks_update: method -> (C entry, its cover function, the cover in words, the ensemble size
+    # from which "auto" takes it -- None: never at this level).  "auto" tries them in this order
+    IENKS_TILE64_ROUTES = {
+        "tile64": ("mia_lienks_update_matfun_f64", "mia_lienks_update_f64_cover", "2 <= k <= 64 and p_max <= k",
+                   "IENKS64_AUTO_MIN_K"),
+        "wide64": ("mia_lienks_update_wide_f64", "mia_lienks_update_wide_f64_cover", "2 <= k <= 128 and p_max <= k",
+                   "IENKS_WIDE64_AUTO_MIN_K"),
+        "stream64": ("mia_lienks_update_stream_f64", "mia_lienks_update_stream_f64_cover",
+                     "2 <= k <= 128 and k < p_max <= 256", None)}
+    IENKS_TILE64_METHODS = tuple(IENKS_TILE64_ROUTES)
+    IENKS_METHODS = ("auto", "eig") + IENKS_TILE64_METHODS
+
     def ienks_update(self, weights: torch.Tensor, Yb: Optional[torch.Tensor], d: Optional[torch.Tensor],
                      nbrs: NeighbourLists, tau: float = 1.0, epsilon: Optional[float] = None,
                      rec: Optional[torch.Tensor] = None, return_flags: bool = False, method: str = "auto",
@@ -1346,10 +1257,11 @@ class LetkfEngine:
         written -- data-dependent, as ``weights_wide64`` documents.  With ``defer_retry`` (the named tile methods only)
         the read is left to the caller, who must invoke the trailing callable of the result (it returns the number of points
         redone).  ``out``: a contiguous (n, k, k) tensor of the weights' dtype to write into."""
-        if method not in ("auto", "eig", "tile64", "wide64", "stream64"):
-            raise ValueError("method must be 'auto', 'eig', 'tile64', 'wide64' or 'stream64'")
-        if defer_retry and method not in ("tile64", "wide64", "stream64"):
-            raise ValueError("defer_retry needs method='tile64', 'wide64' or 'stream64'")
+        tile_methods = self.IENKS_TILE64_METHODS
+        if method not in self.IENKS_METHODS:
+            raise ValueError("method must be " + _one_of(self.IENKS_METHODS))
+        if defer_retry and method not in tile_methods:
+            raise ValueError("defer_retry needs method=" + _one_of(tile_methods))
         weights = torch.as_tensor(weights)
         dtype = weights.dtype if weights.dtype in (torch.float32, torch.float64) else torch.float64
         weights = weights.to(device=self.device, dtype=dtype).contiguous()
@@ -1372,104 +1284,61 @@ class LetkfEngine:
         elif out.shape != (n, k, k) or out.dtype != dtype or not out.is_contiguous() or out.device != weights.device:
             raise ValueError("out must be a contiguous tensor (n, k, k) of the weights' dtype on the engine's device")
         flags = torch.empty(n, dtype=torch.int32, device=self.device)
-        wstride = k * k if weights.dim() == 3 else 0
+        sfx = "f32" if dtype == torch.float32 else "f64"
         eps_c = float(epsilon) if epsilon is not None else 0.0
-        if method == "tile64":
-            if dtype != torch.float64:
-                raise ValueError("method='tile64' needs float64 weights (float32 has its own route under 'auto')")
-            if float(tau) != 1.0:
-                raise ValueError("method='tile64' needs tau = 1 (tau = %g)" % float(tau))
-            if not self.lib.mia_lienks_update_f64_cover(k, min(nbrs.p_max, nbrs.p_cap), n, rec.shape[0]):
-                raise ValueError("method='tile64' covers 2 <= k <= 64 and p_max <= k (k = %d, p_max = %d)" % (k, nbrs.p_max))
-        if method == "wide64":
-            if dtype != torch.float64:
-                raise ValueError("method='wide64' needs float64 weights (float32 has its own route under 'auto')")
-            if float(tau) != 1.0:
-                raise ValueError("method='wide64' needs tau = 1 (tau = %g)" % float(tau))
-            if not self.lib.mia_lienks_update_wide_f64_cover(k, min(nbrs.p_max, nbrs.p_cap), n, rec.shape[0]):
-                raise ValueError("method='wide64' covers 2 <= k <= 128 and p_max <= k (k = %d, p_max = %d)" % (k, nbrs.p_max))
-        if method == "stream64":
-            if dtype != torch.float64:
-                raise ValueError("method='stream64' needs float64 weights (float32 has its own route under 'auto')")
-            if float(tau) != 1.0:
-                raise ValueError("method='stream64' needs tau = 1 (tau = %g)" % float(tau))
-            if not self.lib.mia_lienks_update_stream_f64_cover(k, min(nbrs.p_max, nbrs.p_cap), n, rec.shape[0]):
-                raise ValueError("method='stream64' covers 2 <= k <= 128 and k < p_max <= 256 (k = %d, p_max = %d)"
-                                 % (k, nbrs.p_max))
-        if dtype == torch.float32 and float(tau) == 1.0 and n > 0 and method != "eig":
-            # tau = 1 through the eigensolver-free weights kernel; -3 = shape outside it (primal route, order > 32)
-            retry = torch.zeros(1, dtype=torch.int32, device=self.device)
-            rc = self.lib.mia_lienks_update_matfun_f32(
-                _ptr(weights), wstride, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0], _ptr(nbrs.cnt), _ptr(nbrs.idx),
-                _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max, eps_c, _ptr(out), _ptr(flags), _ptr(retry), self._stream())
-            if rc != -3:
-                _cabi.check(rc, "mia_lienks_update_matfun_f32")
-                if int(retry.item()):        # host sync (8 bytes): the general kernel redoes the declined points
-                    _cabi.check(self.lib.mia_lienks_update_retry_f32(
-                        _ptr(weights), wstride, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0], _ptr(nbrs.cnt),
-                        _ptr(nbrs.idx), _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max, 1.0, eps_c, _ptr(out), _ptr(flags),
-                        self._stream()), "mia_lienks_update_retry_f32")
-                return (out, flags) if return_flags else out
-        f64_tau1 = dtype == torch.float64 and float(tau) == 1.0 and n > 0
-        # (per-point weights of the transform variant have Wp != I everywhere: a tile launch would be declined whole)
-        variant_ok = epsilon is not None or weights.dim() == 2
-        entry = None
-        if method == "tile64":
-            entry = "mia_lienks_update_matfun_f64"
-        elif method == "wide64":
-            entry = "mia_lienks_update_wide_f64"
-        elif method == "stream64":
-            entry = "mia_lienks_update_stream_f64"
-        elif method == "auto" and f64_tau1 and variant_ok:
-            if k >= self.IENKS64_AUTO_MIN_K and self.lib.mia_lienks_update_f64_cover(
-                    k, min(nbrs.p_max, nbrs.p_cap), n, rec.shape[0]):
-                entry = "mia_lienks_update_matfun_f64"
-            elif k >= self.IENKS_WIDE64_AUTO_MIN_K and self.lib.mia_lienks_update_wide_f64_cover(
-                    k, min(nbrs.p_max, nbrs.p_cap), n, rec.shape[0]):
-                entry = "mia_lienks_update_wide_f64"
+        # every entry's arguments, built once: a tile entry takes (*head, *tail, retry_count, stream), the general kernel and
+        # the redo entries (*head, tau, *tail, stream)
+        head = (_ptr(weights), k * k if weights.dim() == 3 else 0, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0], _ptr(nbrs.cnt),
+                _ptr(nbrs.idx), _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max)
+        tail = (eps_c, _ptr(out), _ptr(flags))
+        cover_args = (k, min(nbrs.p_max, nbrs.p_cap), n, rec.shape[0])
 
         def tile_route(entry):
             """The tile kernel behind ``entry`` and the redo of what it declines; None where the entry answers -3."""
             retry = torch.zeros(1, dtype=torch.int32, device=self.device)
-            rc = getattr(self.lib, entry)(
-                _ptr(weights), wstride, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0], _ptr(nbrs.cnt), _ptr(nbrs.idx),
-                _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max, eps_c, _ptr(out), _ptr(flags), _ptr(retry), self._stream())
+            rc = getattr(self.lib, entry)(*head, *tail, _ptr(retry), self._stream())
             if rc == -3:
                 return None
             _cabi.check(rc, entry)
-
-            def finish():         # (a closure over the weights, rec, the lists and out: a deferred retry finds them alive)
-                n_retry = int(retry.item())        # host sync (8 bytes): the general kernel redoes the declined points
-                if n_retry:
-                    _cabi.check(self.lib.mia_lienks_update_retry_f64(
-                        _ptr(weights), wstride, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0], _ptr(nbrs.cnt),
-                        _ptr(nbrs.idx), _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max, 1.0, eps_c, _ptr(out), _ptr(flags),
-                        self._stream()), "mia_lienks_update_retry_f64")
-                return n_retry
-            if not defer_retry:
-                finish()
-            res = [out]
-            if return_flags:
-                res.append(flags)
-            if defer_retry:
-                res.append(finish)
-            return res[0] if len(res) == 1 else tuple(res)
+            # (the general kernel redoes the declined points)
+            finish = self._redo_behind_counter(retry, "mia_lienks_update_retry_" + sfx, lambda: (*head, 1.0, *tail),
+                                               (weights, rec, nbrs, out, flags))
+            return _result(out, None, flags if return_flags else None, finish, defer_retry)
+        f64_tau1 = dtype == torch.float64 and float(tau) == 1.0 and n > 0
+        # (per-point weights of the transform variant have Wp != I everywhere: a tile launch would be declined whole)
+        variant_ok = epsilon is not None or weights.dim() == 2
+        entry = None
+        if method in tile_methods:
+            if dtype != torch.float64:
+                raise ValueError("method='%s' needs float64 weights (float32 has its own route under 'auto')" % method)
+            if float(tau) != 1.0:
+                raise ValueError("method='%s' needs tau = 1 (tau = %g)" % (method, float(tau)))
+            entry, cover, text, _ = self.IENKS_TILE64_ROUTES[method]
+            if not getattr(self.lib, cover)(*cover_args):
+                raise ValueError("method='%s' covers %s (k = %d, p_max = %d)" % (method, text, k, nbrs.p_max))
+        elif dtype == torch.float32 and float(tau) == 1.0 and n > 0 and method != "eig":
+            # tau = 1 through the eigensolver-free weights kernel; -3 = shape outside it (primal route, order > 32)
+            res = tile_route("mia_lienks_update_matfun_f32")
+            if res is not None:
+                return res
+        elif method == "auto" and f64_tau1 and variant_ok:
+            for name, cover, _, min_k in self.IENKS_TILE64_ROUTES.values():
+                if min_k is not None and k >= getattr(self, min_k) and getattr(self.lib, cover)(*cover_args):
+                    entry = name
+                    break
         if entry is not None:
             res = tile_route(entry)
             if res is not None:
                 return res
-            if method in ("tile64", "wide64", "stream64"):
+            if method in tile_methods:
                 raise ValueError("method='%s': the tile kernel is not available (option tile = 0, or the stream is being "
                                  "captured before the coefficient table exists)" % method)
-        sfx = "f32" if dtype == torch.float32 else "f64"
-        fn = getattr(self.lib, "mia_lienks_update_" + sfx)
-        rc = fn(_ptr(weights), k * k if weights.dim() == 3 else 0, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0],
-                _ptr(nbrs.cnt), _ptr(nbrs.idx), _ptr(nbrs.w), nbrs.p_cap, nbrs.p_max, float(tau),
-                float(epsilon) if epsilon is not None else 0.0, _ptr(out), _ptr(flags), self._stream())
-        if (rc == -3 and method == "auto" and f64_tau1 and variant_ok and entry != "mia_lienks_update_wide_f64" and
-                self.lib.mia_lienks_update_wide_f64_cover(k, min(nbrs.p_max, nbrs.p_cap), n, rec.shape[0])):
+        rc = getattr(self.lib, "mia_lienks_update_" + sfx)(*head, float(tau), *tail, self._stream())
+        wide, wide_cover = self.IENKS_TILE64_ROUTES["wide64"][:2]
+        if (rc == -3 and method == "auto" and f64_tau1 and variant_ok and entry != wide
+                and getattr(self.lib, wide_cover)(*cover_args)):
             # the general kernel cannot hold the shape (its LDS): the wide tile kernel can, whatever the gate says
-            res = tile_route("mia_lienks_update_wide_f64")
+            res = tile_route(wide)
             if res is not None:
                 return res
         _cabi.check(rc, "mia_lienks_update_" + sfx)
