@@ -594,6 +594,36 @@ int mia_letkf_weights_stream_f64(const double* X /* may be NULL */, int64_t ldx,
                                  int32_t* flags, int32_t* retry_count, void* stream);
 int mia_letkf_weights_stream_f64_cover(int k, int p_max, int64_t n_points, int64_t P);
 
+/* The WEIGHTS of mia_letkf_weights_stream_f64 with the sixteen points of a tile taken from a MAP (csrc/letkf_patch64w.hip): the
+ * same kernel body -- union by rank, the ring, rhs, streamed Gershgorin bound, primal table, degree, decline, one pass per
+ * member on e_c -- with mia_letkf_analysis_patch_f64's two changes to the frame.  tile_pts [n_tiles][16] int32: the point of
+ * slot s of tile t as an index into [0, g1 - g0), or -1 for an empty slot; every point of the range must occur exactly once
+ * (mia_letkf_tile_union_census checks it; this entry trusts the map except that an entry outside the range is treated as
+ * empty).  union_blocks: sixteen-slot blocks of the sqrt(rho) and slot tables in LDS, 1 .. 16 at every ensemble size (the
+ * records are streamed, not resident); a tile whose union exceeds it runs in halves of its slots, a single list longer than
+ * 16 union_blocks, p_max or p_cap is MIA_FLAG_OVERFLOW and NaN weights for that point only.  On a row-major 2-D mesh with an
+ * observation per point and radius 3 a 16 x 1 strip has a union of 200 observations against the 128 slots
+ * mia_letkf_weights_stream_f64 takes, a 4 x 4 patch 176 against up to 256 here: one pass per tile.  Every lane writes its
+ * point's k x k block through a 64-bit base of its own, so a tile's points may lie anywhere in W.  Lists, flags and W stay in
+ * natural point order: declined points are redone by mia_letkf_weights_retry_f64 unchanged, with the data-dependent
+ * MIA_ERR_UNSUPPORTED of that kernel from 97 members on.  W and flags are mia_letkf_weights_stream_f64's bit for bit under
+ * any map.  Argument list: mia_letkf_weights_stream_f64's with tile_pts, n_tiles, union_blocks in front of stream.
+ * Validation before any launch in that entry's order, n_tiles < 0 among the sizes (MIA_ERR_SIZE), tile_pts among the pointers
+ * (MIA_ERR_NULL), n_tiles == 0 for a non-empty range MIA_ERR_SIZE; then MIA_ERR_UNSUPPORTED for p_max <= k, p_max > 256, k
+ * outside 2 .. 128, gamma > 0, the option "tile" = 0, union_blocks outside 1 .. 16, a launch whose LDS does not fit and a
+ * coefficient table that cannot be had (stream being captured).
+ * mia_letkf_weights_patch_f64_cover: 1 when the shape is inside the route (2 <= k <= 128, k < p_max <= 256,
+ * 0 <= n_points < 2^31 for the int32 map entries, k^2 8 < 2^31 for the 32-bit offset inside a point's weights, the LDS of
+ * the largest image, P >= 0), 0 when not (host only, no device work). */
+int mia_letkf_weights_patch_f64(const double* X /* may be NULL */, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
+                                const double* rec, int64_t P,
+                                const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w,
+                                int p_cap, int p_max, double inf_factor, double gamma,
+                                double* Xa /* may be NULL */, int64_t ldo, int64_t o0, double* W /* [g1-g0][k][k] */,
+                                int32_t* flags, int32_t* retry_count,
+                                const int32_t* tile_pts, int64_t n_tiles, int union_blocks, void* stream);
+int mia_letkf_weights_patch_f64_cover(int k, int p_max, int64_t n_points, int64_t P);
+
 /* The float64 RBF-kernelised analysis on tiles (csrc/lketkf_tile64.hip): KETKFModule._estimate_weights (core/ketkf.py:65-94)
  * with RBFKernel(gamma) / GaussKernel (kernels/rbf.py:75-81,110-111) under wrapper_localization (interface/wrapper.py:86-98)
  * and the transform of interface/base.py:257-278, sixteen grid points per workgroup of four wavefronts, without an

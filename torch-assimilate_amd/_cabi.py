@@ -101,6 +101,9 @@ _PROTOS = {
     "mia_letkf_weights_wide_f64_cover": _COVER4,
     "mia_letkf_weights_stream_f64": _weights_entry(f64),
     "mia_letkf_weights_stream_f64_cover": _COVER4,
+    "mia_letkf_weights_patch_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
+                                     vp, i64, i64, vp, vp, vp, vp, i64, i32, vp], i32),
+    "mia_letkf_weights_patch_f64_cover": _COVER4,
     "mia_letkf_weights_matfun_f32": _weights_entry(f32),
     "mia_letkf_weights_retry_f32": _analysis_entry(f32),
     "mia_letkf_index_build_f64": ([vp, i64, i32, C.POINTER(C.c_int32), C.POINTER(f64), i32, vp, sz, vp], i32),

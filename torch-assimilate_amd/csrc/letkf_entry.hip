@@ -127,15 +127,17 @@ static int analysis_impl(const T* X, int64_t ldx, int m, int k, int64_t g0, int6
 //          0               the float32 twins: gamma selects the core
 //   also   one more pointer that must not be NULL: W of the weights entries, the tile map of patch64 (else: flags again)
 //   n_tiles, union_blocks  patch64's extra sizes
+//   also2  a second such pointer: the weights entry with a map has both W and the map
 enum : unsigned { kGammaRefused = 1, kGammaRequired = 2, kProgram = 4, kStateOptional = 8 };
 constexpr int kLaunch = 1;
+static const char kNoSecondPointer = 0;
 
 template <typename T>
 static int tile_entry_checks(unsigned rule, const T* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1, const T* rec, int64_t P,
                              const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int* p_max,
                              T inf_factor, T gamma, const T* Xa, int64_t ldo, int64_t o0, const void* also, const int32_t* flags,
                              const int32_t* retry_count, const mia_kernel_op_t* prog = nullptr, int n_ops = 0,
-                             int64_t n_tiles = 1, int union_blocks = 1) {
+                             int64_t n_tiles = 1, int union_blocks = 1, const void* also2 = &kNoSecondPointer) {
   if (g1 < g0 || g0 < 0 || m < 1 || k < 2 || P < 0 || p_cap < 1 || *p_max < 0 || n_tiles < 0 || union_blocks < 1) return MIA_ERR_SIZE;
   if (!(inf_factor > T(0))) return MIA_ERR_SIZE;
   if ((rule & kGammaRefused) && gamma > T(0)) return MIA_ERR_UNSUPPORTED;
@@ -147,7 +149,7 @@ static int tile_entry_checks(unsigned rule, const T* X, int64_t ldx, int m, int 
   const int64_t ng = g1 - g0;
   if (ng == 0) return MIA_OK;
   const bool opt = (rule & kStateOptional) != 0;
-  if ((!opt && (!X || !Xa)) || !also || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
+  if ((!opt && (!X || !Xa)) || !also || !also2 || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
   if (opt ? ((X && ldx < g1) || (Xa && ldo < o0 + ng)) : (ldx < g1 || ldo < o0 + ng)) return MIA_ERR_SIZE;
   if (n_tiles == 0) return MIA_ERR_SIZE;
   if (*p_max > p_cap) *p_max = p_cap;
@@ -539,6 +541,26 @@ extern "C" int mia_letkf_weights_stream_f64(const double* X, int64_t ldx, int m,
 extern "C" int mia_letkf_weights_stream_f64_cover(int k, int p_max, int64_t n_points, int64_t P) {
   if (P < 0) return 0;
   return weights_stream64_route_covers(k, p_max, n_points) ? 1 : 0;
+}
+// letkf_stream64w.hip's weights with a tile map and caller-sized slot tables (letkf_patch64w.hip): the same validation with the
+// map's arguments among the sizes and pointers (as mia_letkf_analysis_patch_f64), then the one kernel of the route.
+// union_blocks outside 1 .. 16 is the launch's answer (MIA_ERR_UNSUPPORTED), not a size error
+extern "C" int mia_letkf_weights_patch_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
+                                           const double* rec, int64_t P, const int32_t* nbr_cnt,
+                                           const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                                           double inf_factor, double gamma, double* Xa, int64_t ldo, int64_t o0, double* W,
+                                           int32_t* flags, int32_t* retry_count, const int32_t* tile_pts, int64_t n_tiles,
+                                           int union_blocks, void* stream) {
+  (void)hipGetLastError();
+  const int rc = tile_entry_checks(kGammaRefused | kStateOptional, X, ldx, m, k, g0, g1, rec, P, nbr_cnt, nbr_idx, nbr_w, p_cap, &p_max, inf_factor,
+                                   gamma, Xa, ldo, o0, W, flags, retry_count, nullptr, 0, n_tiles, 1, tile_pts);
+  if (rc != kLaunch) return rc;
+  return weights_patch64_launch(k, g1 - g0, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, W, flags, retry_count,
+                                tile_pts, n_tiles, union_blocks, (hipStream_t)stream);
+}
+extern "C" int mia_letkf_weights_patch_f64_cover(int k, int p_max, int64_t n_points, int64_t P) {
+  if (P < 0) return 0;
+  return weights_patch64_route_covers(k, p_max, n_points) ? 1 : 0;
 }
 
 extern "C" int mia_letkf_analysis_matfun_fused_f32(const float* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,

@@ -1,0 +1,537 @@
+// letkf_stream64w.hip's WEIGHTS (FLOAT64, dense local networks p_max > k, ensembles up to 128 members, sixteen grid points per
+// wavefront, every contraction a v_mfma_f64_16x16x4_f64, the union's records streamed through a ring of two sixteen-slot blocks)
+// with letkf_patch64.hip's two changes to the FRAME; mathematics, lane roles, summation order, the ring and its
+// stage / chain / fold / turn discipline, the streamed bound, table, decline and the run-time loops are letkf_stream64w.hip's
+// (reference: core/etkf.py:57-103 + interface/letkf.py:127-146) and are not restated here.
+//
+// 1. TILE MAP.  The sixteen points of tile t are tile_pts[16 t + s], s = 0 .. 15: indices into the launch's range [0, ng),
+//    -1 = empty slot.  On a row-major 2-D mesh sixteen CONSECUTIVE points are a 16 x 1 strip whose lists have a union of 200
+//    observations at radius 3 against 176 of a 4 x 4 patch: the strip runs in parts, the patch in one pass.  List row, count,
+//    flag and the point's k x k block of W are addressed through the map.  Live slots need not be a prefix: a dead slot is
+//    clamped to the tile's first live point for loads and every store is predicated.  The range loop runs over SLOTS, starts a
+//    range at a live slot and ends at the last live one.  A tile without a live slot returns before the union; an entry outside
+//    [0, ng) is an empty slot.  Lists and flags stay in natural point order, so the redo of declined points
+//    (letkf_wave_kernel<double>) needs no map.
+// 2. IMAGE SIZED BY THE CALLER.  `ub` sixteen-slot blocks of the sqrt(rho) table and the slot table, 1 <= ub <= 16 at every
+//    ensemble size (the records are not resident); the caller has it from tile_union_census_kernel (letkf_patch64.hip).  A tile
+//    whose union exceeds it runs in halves of its SLOTS, quarters, ...; a single list longer than the image, p_max or p_cap is
+//    MIA_FLAG_OVERFLOW and NaN weights, never a truncated list.
+// 3. THE STORES.  letkf_stream64w.hip addresses W as a wave-uniform base (the tile's first point, row c) + a 32-bit lane offset
+//    point k^2 8 + j 8, which needs a tile's points to be consecutive.  Under a map they lie anywhere in n k^2 8 bytes (more than
+//    2^31 at 1e5 points): every lane owns one column = one point, so it forms a 64-bit base W + tile_pts[slot] k^2 once per
+//    range and keeps the 32-bit part to c k 8 + j 8 < k^2 8 <= 2^17.
+//
+// A point's observations are summed in ascending index order with exact zeros in between whatever else is in the tile, so W
+// and flags are letkf_patch64w_kernel's bit for bit under any map (tests/test_gpu_patch64w.py).
+//
+// The kernel is a copy of letkf_patch64w_kernel with the frame changed, not a shared body (DESIGN 2.18 on letkf_patch64.hip:
+// the map reaches every address the frame forms, and the parent's code object stays what it was).
+#include "mia_cheb_table64.h"
+
+namespace mia {
+
+struct Patch64WParams {
+  int k; int kp;
+  int64_t ng;
+  const double* rec;
+  const int32_t* cnt; const int32_t* idx; const double* w; int p_cap; int p_max;
+  const int32_t* tile_pts; int64_t n_tiles;                  // [n_tiles][16] point of a slot, -1 = none
+  int ub;                                                    // sixteen-slot blocks of the slot table of the launch: the caller's
+  double reg, inv_reg, cs_phi, cs_psi, f_id;                 // f_id = sqrt(inf): the diagonal of a point without observations
+  double* W; int32_t* flags; int32_t* retry_count;
+  int dmax;
+  const Tab64Hdr* tab_hdr; const double2* tab_c;
+};
+
+// KT = ceil(k / 16).  One wavefront per workgroup; its LDS bounds how many share a compute unit.
+template <int KT>
+__global__ __launch_bounds__(64, 1) void letkf_patch64w_kernel(Patch64WParams P) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  const int lane = threadIdx.x;
+  const int k = P.k, kp = P.kp, pm = P.p_max;
+  const int UMAX = 16 * P.ub, DS = UMAX + 1;
+  const int KS = kp | 1;                                     // odd row pitch (in doubles) of a staged block
+  constexpr int NC = KT + 1;                                 // column trips of a staged row: kp <= 16 KT + 4
+  double* Ring = reinterpret_cast<double*>(smem_raw);        // [2][16][KS] two sixteen-slot blocks of union records
+  double* Rl = Ring + 2 * 16 * KS;                           // [4 KT][64]  rhs of the tile, every lane its own registers' worth
+  double* Dl = Rl + 4 * KT * 64;                             // [16][DS]    sqrt(rho) of (point, slot), 0 = not local
+  int* ukey = reinterpret_cast<int*>(Dl + 16 * DS);          // [UMAX]      observation index of a slot, ascending; -1 = none
+  unsigned* Kl = reinterpret_cast<unsigned*>(Dl);            // [16][nl]    index + 1 of the lists' entries while the union is formed
+
+  // XCD-aware block -> tile map: blocks b, b + 8, ... share an XCD (and its L2) and take consecutive tiles, whose
+  // records overlap (consecutive tiles of a patch row)
+  const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
+  const int64_t ntile = P.n_tiles;
+  if (bid >= ntile) return;
+  const int64_t q8 = ntile >> 3, r8 = ntile & 7, xcd = bid & 7;
+  const int64_t tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int lr = lane & 15, h = lane >> 4, lp = lane >> 2, sub = lane & 3;
+
+  // ---- the tile's points: slot lr is this lane's column, slot lp the list it walks.  An entry outside [0, ng) is an empty
+  //      slot (the census refuses such a map; nothing is ever indexed by one)
+  const int32_t* tp = P.tile_pts + tile * 16;
+  int ptc = tp[lr], ptl = tp[lp];
+  ptc = (ptc >= 0 && ptc < P.ng) ? ptc : -1;
+  ptl = (ptl >= 0 && ptl < P.ng) ? ptl : -1;
+  const unsigned livemask = (unsigned)(__ballot(ptc >= 0) & 0xffffull);       // (lanes 0 .. 15 are slots 0 .. 15)
+  if (livemask == 0u) return;
+  const int nslot = 32 - __builtin_clz(livemask);             // one past the last live slot
+  const int pfirst = tp[__builtin_ctz(livemask)];             // a point that exists: what dead slots load from
+  const bool live_c = ptc >= 0, live_l = ptl >= 0;
+  const int colpt = live_c ? ptc : pfirst;
+
+  // ---- the tile's neighbour lists stay in memory: lane (lp, sub) walks entries sub, sub + 4, ... of slot lp's point
+  int nl = pm < P.p_cap ? pm : P.p_cap;
+  nl = nl < UMAX ? nl : UMAX;
+  const int64_t lrow = live_l ? ptl : pfirst;                // (lists, flags and weights count from the shard's g0)
+  const int32_t* ib = P.idx + lrow * P.p_cap;
+  const double* wb = P.w + lrow * P.p_cap;
+  int lcnt = P.cnt[lrow];
+  unsigned long long badmask;
+  {
+    const bool pbad = live_l && (lcnt > pm || lcnt > P.p_cap || lcnt > UMAX);   // loud failure, never truncate
+    if (pbad) {
+      if (sub == 0) P.flags[ptl] = MIA_FLAG_OVERFLOW;
+      const double nanv = __builtin_nan("");
+      double* wp = P.W + (int64_t)ptl * (int64_t)(k * k);
+      for (int it = sub; it < k * k; it += 4) wp[it] = nanv;
+    }
+    if (!live_l || pbad) lcnt = 0;
+    badmask = __ballot(pbad);
+  }
+  // a point without observations: sqrt(inf) I, written directly (lanes 4 lr .. 4 lr + 3 hold slot lr's count)
+  const bool cempty = __shfl(lcnt, 4 * lr, 64) == 0;
+
+  // ---- the ring: stage() asks memory for block tb of the union (rows 4 j + h, columns lr + 16 i of this lane), commit()
+  //      writes the staged registers to one half.  Rows beyond the union (key -1) are zeros and touch no memory
+  int UB = 1;
+  int cur = 0;                                               // the half that holds the block of the trip
+  double st[4][NC];
+  auto stage = [&](int tb) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int key = ukey[16 * tb + 4 * j + h];
+      const double* src = P.rec + ((int64_t)(key < 0 ? 0 : key) * kp + lr);
+#pragma unroll
+      for (int i = 0; i < NC; ++i) {
+        double v = 0.0;
+        if (key >= 0 && (i < KT - 1 || lr + 16 * i < kp)) v = src[16 * i];
+        st[j][i] = v;
+      }
+    }
+  };
+  auto commit = [&](int half, double& fin) {                 // fin stays 0 while every value is finite (inf * 0 = NaN)
+    double* dst = Ring + half * 16 * KS + h * KS + lr;
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int i = 0; i < NC; ++i) {
+        fin = fma(st[j][i], 0.0, fin);
+        if (i < KT - 1 || lr + 16 * i < kp) dst[4 * j * KS + 16 * i] = st[j][i];
+      }
+  };
+
+  int lo = 0;
+  bool single = false;                                       // a non-finite record was met: the rest of the tile goes point by point
+#pragma clang loop unroll(disable)
+  while (lo < nslot) {
+    if (!((livemask >> lo) & 1u)) { ++lo; continue; }        // a range starts at a live slot, so it is never empty
+    const bool colok = live_c && !((badmask >> (4 * lr)) & 1ull);
+    const double* Dcol = Dl + lr * DS + h;                    // + 16 t + 4 r: slot 16 t + h + 4 r of column lr
+    // A operands out of the current half.  First product / Gram: record row lr of the block, member 16 tm + 4 q + h; second
+    // product: record row 4 q + h, member 16 tj + lr.  Innovation and pad columns are not members (only the last block is ragged).
+    auto a_in = [&](int tm, int q) -> double {
+      const int mem = 16 * tm + 4 * q + h;
+      const bool ok = tm < KT - 1 || mem < k;
+      const double v = Ring[cur * 16 * KS + lr * KS + (ok ? mem : 0)];
+      return ok ? v : 0.0;
+    };
+    auto a_out = [&](int q, int tj) -> double {
+      const int mem = 16 * tj + lr;
+      const bool ok = tj < KT - 1 || mem < k;
+      const double v = Ring[cur * 16 * KS + (4 * q + h) * KS + (ok ? mem : 0)];
+      return ok ? v : 0.0;
+    };
+    // The A operands of four matrix instructions are read from LDS while the four before them run, and the scheduler is
+    // held to that order: left alone it reads a trip's 8 KT operands ahead of its first instruction, which the 40 KT
+    // registers of the recurrence vectors and the staged block leave no room for above 80 members.
+    // T (or Gram) block of the trip: steps (tm, q) ascending through ONE accumulator; b[tm][q] = the B operands
+    auto chain = [&](const auto& b) -> d4t {
+      d4t acc = {0., 0., 0., 0.};
+      double an[4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) an[q] = a_in(0, q);
+#pragma unroll
+      for (int tm = 0; tm < KT; ++tm) {
+        double ac[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) ac[q] = an[q];
+        if (tm + 1 < KT) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) an[q] = a_in(tm + 1, q);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc = MIA_MFMA64(ac[q], b[tm][q], acc);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      return acc;
+    };
+    // y += Yw^T (s o .) over the block of the trip: the second product's steps (tb, q), B = the scaled block; step
+    // e = KT q + tj, four steps per group
+    auto fold = [&](const double (&s)[4], d4t (&y)[KT]) {
+      double an[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) an[i] = a_out(i / KT, i % KT);
+#pragma unroll
+      for (int g = 0; g < KT; ++g) {
+        double ac[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) ac[i] = an[i];
+        if (g + 1 < KT) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) an[i] = a_out((4 * g + 4 + i) / KT, (4 * g + 4 + i) % KT);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) y[(4 * g + i) % KT] = MIA_MFMA64(ac[i], s[(4 * g + i) / KT], y[(4 * g + i) % KT]);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    };
+    // the end of a trip: the staged block into the other half, which becomes the current one
+    auto turn = [&](double& fin) {
+      commit(cur ^ 1, fin);
+      __syncthreads();
+      cur ^= 1;
+    };
+    // ---- union of the lists of slots [lo, hi): slot of the union = RANK of the observation index, found by repeated extraction of
+    //      the smallest remaining key (one sweep over the keys in LDS and one DPP reduction per slot); shrink the range
+    //      until the union fits
+    int n = single ? 1 : 16, hi, U;
+    bool act;
+    for (;;) {
+      hi = lo + n < nslot ? lo + n : nslot;
+      act = lp >= lo && lp < hi && live_l;
+      for (int pos = sub; pos < nl; pos += 4) {
+        int e = -1;
+        if (act && pos < lcnt) e = ib[pos];
+        Kl[lp * nl + pos] = e >= 0 ? (unsigned)e + 1u : 0u;
+      }
+      for (int i = lane; i < UMAX; i += 64) ukey[i] = -1;
+      __syncthreads();
+      U = 0;
+      unsigned last = 0u;
+      const int e0 = lo * nl, e1 = hi * nl;
+#pragma clang loop unroll(disable)
+      for (;;) {
+        unsigned best = 0u;                       // ~(smallest key above `last`), 0 = none left
+        for (int e = e0 + lane; e < e1; e += 64) {
+          const unsigned key1 = Kl[e];
+          const unsigned cand = key1 > last ? ~key1 : 0u;
+          best = cand > best ? cand : best;
+        }
+        best = tile64_wave_max_u32(best);
+        if (best == 0u) break;
+        last = ~best;
+        if (U < UMAX && lane == 0) ukey[U] = (int)(last - 1u);
+        ++U;
+        if (U > UMAX) break;
+      }
+      if (U > UMAX) { __syncthreads(); n >>= 1; continue; }     // (n = 1 always fits: a single list has at most UMAX entries)
+      __syncthreads();
+      UB = (U + 15) >> 4;
+      UB = UB < 1 ? 1 : UB;                                      // blocks in use; slots up to 16 UB are staged
+      // ---- sqrt(rho) of (point, slot): the slot of an entry is the place of its index in the sorted slot table
+      for (int i = lane; i < 16 * DS; i += 64) Dl[i] = 0.0;     // (over the keys: every lane is past the barrier behind their last read)
+      __syncthreads();
+      if (act)
+        for (int pos = sub; pos < lcnt; pos += 4) {
+          const int key = ib[pos];
+          if (key < 0) continue;
+          int a = 0, b = U;
+          while (a < b) {
+            const int mid = (a + b) >> 1;
+            if (ukey[mid] < key) a = mid + 1; else b = mid;
+          }
+          Dl[lp * DS + a] = wb[pos];
+        }
+      // ---- block 0 into the ring
+      double fin = 0.0;
+      stage(0);
+      commit(cur, fin);
+      __syncthreads();
+      // ---- rhs_g = Yw^T (rho_g o d), once per tile (d = column k of the records); this first pass over the union also
+      //      looks at every record (blocks 1 .. UB - 1 and block 0 again pass through commit)
+      d4t rhs[KT];
+#pragma unroll
+      for (int tj = 0; tj < KT; ++tj) rhs[tj] = d4t{0., 0., 0., 0.};
+      {
+        int tb = 0;
+#pragma clang loop unroll(disable)
+        do {
+          stage(tb + 1 < UB ? tb + 1 : 0);
+          double s[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const double dv = Dcol[16 * tb + 4 * q];
+            s[q] = dv * dv * Ring[cur * 16 * KS + (4 * q + h) * KS + k];
+          }
+          fold(s, rhs);
+          turn(fin);
+        } while (++tb < UB);
+      }
+      // A non-finite record would reach EVERY column of the tile through the shared products (NaN * 0 = NaN), also the
+      // points that do not see that observation.  Such a tile is analysed point by point: the union is then the point's
+      // own list and the damage stays where the reference has it.
+      if (__any(fin != fin) && hi - lo > 1) { __syncthreads(); n = 1; single = true; continue; }
+#pragma unroll
+      for (int tj = 0; tj < KT; ++tj)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Rl[(4 * tj + r) * 64 + lane] = rhs[tj][r];
+      break;
+    }
+    const bool colact = colok && lr >= lo && lr < hi;
+    // this lane's column is one point: the 64-bit base of its k x k block (a dead slot: the tile's first live point, never stored to)
+    char* const wcol = reinterpret_cast<char*>(P.W + (int64_t)colpt * (int64_t)(k * k));
+    double nofin = 0.0;                                       // (the later passes do not look at the records again)
+    // ---- Gershgorin bound of every point, streamed: L_g = max_a w_a sum_b |G_ab| w_b.  Row block t is read from memory as
+    //      B operands (slot 16 t + lr, member 16 tm + 4 q + h); every Gram block (tk, t) is formed (4 KT instructions),
+    //      folded into the row sums (4) and dropped
+    double L = 0.0;
+    {
+      int t = 0;
+#pragma clang loop unroll(disable)
+      do {
+        double at[KT][4];
+        {
+          const int key = ukey[16 * t + lr];
+          const double* src = P.rec + ((int64_t)(key < 0 ? 0 : key) * kp + h);
+#pragma unroll
+          for (int tm = 0; tm < KT; ++tm)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+              double v = 0.0;
+              if (key >= 0 && (tm < KT - 1 || 16 * tm + 4 * q + h < k)) v = src[16 * tm + 4 * q];
+              at[tm][q] = v;
+            }
+        }
+        d4t R = {0., 0., 0., 0.};
+        int tk = 0;
+#pragma clang loop unroll(disable)
+        do {
+          stage(tk + 1 < UB ? tk + 1 : 0);
+          __builtin_amdgcn_sched_barrier(0);
+          const d4t Gb = chain(at);
+          double dk[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) dk[q] = Dcol[16 * tk + 4 * q];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) R = MIA_MFMA64(fabs(Gb[q]), dk[q], R);
+          turn(nofin);
+        } while (++tk < UB);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const double v = Dcol[16 * t + 4 * r] * R[r];
+          L = (v > L || v != v) ? v : L;
+        }
+      } while (++t < UB);
+    }
+    // ---- degree and interval of every point from the table
+    double alpha;
+    int deg, tab_idx, pflag = 0;
+    bool decl;
+    {
+      L = tile64_max_h(L);
+      L = fmax(L, 1e-300 * P.reg) * (1.0 + 1e-12);
+      if (!(L == L) || !(fabs(L) < 1e300)) { pflag |= MIA_FLAG_NONFINITE; L = P.reg; }
+      tab_idx = (int)ceil(double(kTabPerOctave) * log2(L * P.inv_reg)) + kTabIdx0;
+      tab_idx = tab_idx < 0 ? 0 : (tab_idx > kTabN - 1 ? kTabN - 1 : tab_idx);      // (the last entries decline: T = 2^8)
+      const Tab64Hdr hd = P.tab_hdr[tab_idx];
+      deg = hd.deg;
+      decl = colact && (deg > P.dmax || deg > kTab64Deg - 1);
+      alpha = (deg > kTab64Deg - 1) ? 0.0 : hd.two_over_T * P.inv_reg;             // (a declined column carries bounded junk)
+      if (decl && h == 0) {
+        P.flags[ptc] = MIA_FLAG_RETRY;
+        atomicAdd(P.retry_count, 1);
+      }
+    }
+    // (a column without observations is written directly: its series is not looked at and asks for no step)
+    const int degmax = (int)tile64_wave_max_u32((colact && !decl && !cempty) ? (unsigned)deg : 0u);
+    const double2* ctab = P.tab_c + (size_t)tab_idx * kTab64Deg;
+    auto coef = [&](int j) -> double2 {                              // (zero beyond a point's own degree)
+      const double2 c = ctab[j < kTab64Deg ? j : kTab64Deg - 1];
+      return double2{c.x * P.cs_phi, c.y * P.cs_psi};
+    };
+
+#pragma clang loop unroll(disable)
+    for (int c = 0; c < k; ++c) {
+      // (lane roles through opaque copies, as in letkf_tile64.hip: what is invariant in this loop -- the member numbers of the
+      // start vector, the 4 KT offsets of the output, their predicates -- would otherwise be hoisted and held in registers
+      // across the recurrence, which has none to spare)
+      int hv = h;
+      asm volatile("" : "+v"(hv));
+      d4t va[KT], vb[KT], aphi[KT], apsi[KT];
+      // ---- the recurrence on the 16 columns at once: v_0 = e_c on live columns (member c < k always exists), v_1 = alpha C v_0 - v_0,
+      //      v_{j+1} = 2 (alpha C v_j - v_j) - v_{j-1}
+#pragma unroll
+      for (int tm = 0; tm < KT; ++tm)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) va[tm][q] = (colact && 16 * tm + 4 * q + hv == c) ? 1.0 : 0.0;
+      // acc += sc C u = Yw^T (sc rho o (Yw u)), one sixteen-slot block of the union per trip; sc = alpha or 2 alpha of the
+      // column.  The caller has put the recurrence's other terms into acc: the step needs no vector of its own for C u,
+      // which at 128 members is the 64 registers that decide between spilling and not
+      auto product = [&](const d4t (&u)[KT], d4t (&acc)[KT], const double sc) {
+        int tb = 0;
+#pragma clang loop unroll(disable)
+        do {
+          stage(tb + 1 < UB ? tb + 1 : 0);
+          __builtin_amdgcn_sched_barrier(0);
+          const d4t Tb = chain(u);
+          double s[4];
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            const double dv = Dcol[16 * tb + 4 * q];
+            s[q] = (sc * (dv * dv)) * Tb[q];
+          }
+          fold(s, acc);
+          turn(nofin);
+        } while (++tb < UB);
+      };
+      // vnew = 2 alpha C vcur - 2 vcur - vold, accumulated over vold; the two functions accumulate c_j vnew
+      auto advance = [&](d4t (&vold)[KT], const d4t (&vcur)[KT], const double2 cj) {
+#pragma unroll
+        for (int t = 0; t < KT; ++t) vold[t] = -2.0 * vcur[t] - vold[t];
+        product(vcur, vold, 2.0 * alpha);
+#pragma unroll
+        for (int t = 0; t < KT; ++t) {
+          aphi[t] = cj.x * vold[t] + aphi[t];
+          apsi[t] = cj.y * vold[t] + apsi[t];
+        }
+      };
+      {
+        const double2 c0 = coef(0), c1 = coef(1);
+#pragma unroll
+        for (int t = 0; t < KT; ++t) vb[t] = -va[t];
+        product(va, vb, alpha);                 // vb = v_1 = alpha C v_0 - v_0
+#pragma unroll
+        for (int t = 0; t < KT; ++t) {
+          aphi[t] = c0.x * va[t] + c1.x * vb[t];
+          apsi[t] = c0.y * va[t] + c1.y * vb[t];
+        }
+      }
+      int j = 2;
+      double2 cj = coef(2), cj1 = coef(3);
+#pragma clang loop unroll(disable)
+      for (; j + 1 <= degmax; j += 2) {
+        const double2 nj = coef(j + 2), nj1 = coef(j + 3);       // requested one trip ahead
+        advance(va, vb, cj);          // va = v_j
+        advance(vb, va, cj1);         // vb = v_{j+1}
+        cj = nj; cj1 = nj1;
+      }
+      if (j <= degmax) advance(va, vb, cj);
+      // ---- wm_c = (psi(C) e_c) . rhs / reg: members in the lane's registers first, then the four lane groups
+      double zs = 0.0;
+#pragma unroll
+      for (int tm = 0; tm < KT; ++tm)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) zs = fma(apsi[tm][r], Rl[(4 * tm + r) * 64 + lane], zs);
+      const double wm = tile64_add_h(zs);
+      // row c of the sixteen points' weights: the lane's 64-bit base (its point) + 32-bit offset (row c, column j) < k^2 8
+      char* obase = wcol;
+      const unsigned olane = (unsigned)(c * k) * 8u + (unsigned)hv * 8u;
+      const bool wr = colact && !decl;
+#pragma unroll
+      for (int tj = 0; tj < KT; ++tj)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int mem = 16 * tj + hv + 4 * r;
+          double o = aphi[tj][r] + wm;
+          if (cempty) o = mem == c ? P.f_id : 0.0;
+          if (!(fabs(o) <= 1e300) && mem < k) pflag |= MIA_FLAG_NONFINITE;
+          if (wr && mem < k) *reinterpret_cast<double*>(obase + (olane + (unsigned)(16 * tj + 4 * r) * 8u)) = o;
+        }
+    }
+    {
+      if (!(colact && !decl)) pflag = 0;          // (columns that are not written do not report)
+      const unsigned long long fb = __ballot(pflag != 0);
+      const bool anyf = ((fb >> lr) & 0x0001000100010001ull) != 0ull;
+      if (h == 0 && colact && !decl) P.flags[ptc] = cempty ? 0 : ((anyf ? MIA_FLAG_NONFINITE : 0) | (deg << 8));
+    }
+    lo = hi;
+    __syncthreads();
+  }
+}
+
+// ---- host side ------------------------------------------------------------------------------------------------------------
+constexpr int kPatch64WMaxBlocks = 16;                          // 256 slots, at every ensemble size of the route
+constexpr int kPatch64WMaxK = 128;
+
+// letkf_stream64w.hip's: ring [2][16][kp | 1] + rhs [4 KT][64] + sqrt(rho) [16][16 ub + 1] doubles, slot table [16 ub] ints
+static size_t patch64w_lds_bytes(int ub, int k) {
+  const int umax = 16 * ub, kp = (k + 1 + 3) & ~3, kt = (k + 15) >> 4;
+  return align_up(((size_t)2 * 16 * (kp | 1) + (size_t)4 * kt * 64 + 16 * (size_t)(umax + 1)) * sizeof(double) +
+                  (size_t)umax * sizeof(int), 16);
+}
+
+bool weights_patch64_route_covers(int k, int p_max, int64_t ng) {
+  if (k < 2 || k > kPatch64WMaxK || p_max <= k || ng < 0) return false;                 // p_max <= k: the dual routes
+  if (p_max > 16 * kPatch64WMaxBlocks) return false;
+  // a lane addresses W as its point's 64-bit base + a 32-bit byte offset inside that point's k x k block; map entries are int32
+  if ((int64_t)k * k * 8 >= ((int64_t)1 << 31) || ng >= ((int64_t)1 << 31)) return false;
+  if (patch64w_lds_bytes(kPatch64WMaxBlocks, k) > kMaxDynamicLds) return false;          // (the largest image; holds at every k: tests/test_patch64w_cover.py)
+  return true;
+}
+
+template <int KT>
+static int patch64w_launch_t(const Patch64WParams& dp, hipStream_t stream) {
+  const size_t lds = patch64w_lds_bytes(dp.ub, dp.k);
+  if (lds > kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
+  auto kern = letkf_patch64w_kernel<KT>;
+  if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  const int64_t ntile = dp.n_tiles;
+  const int64_t gx = ntile < 65536 ? ntile : 65536;
+  const int64_t gy = (ntile + gx - 1) / gx;
+  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
+  kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(64), lds, stream>>>(dp);
+  note_analysis_kernel("letkf_patch64w_kernel<%d>", KT);
+  MIA_LAUNCH_CHECK();
+  return MIA_OK;
+}
+
+int weights_patch64_launch(int k, int64_t ng, const double* rec, const int32_t* nbr_cnt, const int32_t* nbr_idx,
+                           const double* nbr_w, int p_cap, int p_max, double inf_factor, double* W, int32_t* flags,
+                           int32_t* retry_count, const int32_t* tile_pts, int64_t n_tiles, int union_blocks, hipStream_t stream) {
+  if (!option(MIA_OPT_TILE) || !W || !flags || !retry_count || !tile_pts) return MIA_ERR_UNSUPPORTED;
+  if (!weights_patch64_route_covers(k, p_max, ng)) return MIA_ERR_UNSUPPORTED;
+  if (union_blocks < 1 || union_blocks > kPatch64WMaxBlocks || n_tiles < 1 || n_tiles > (int64_t)65536 * 65535) return MIA_ERR_UNSUPPORTED;
+  const CoefTable64* tab = cheb_coef_table64(stream, kTab64Primal);
+  if (!tab) return MIA_ERR_UNSUPPORTED;
+  Patch64WParams dp;
+  dp.k = k; dp.kp = (k + 1 + 3) & ~3;
+  dp.ng = ng; dp.rec = rec;
+  dp.cnt = nbr_cnt; dp.idx = nbr_idx; dp.w = nbr_w; dp.p_cap = p_cap; dp.p_max = p_max;
+  dp.tile_pts = tile_pts; dp.n_tiles = n_tiles;
+  dp.ub = union_blocks;
+  const double rg = (double)(k - 1) / inf_factor, km = (double)(k - 1);
+  dp.reg = rg;
+  dp.inv_reg = 1.0 / rg;
+  dp.cs_phi = sqrt(km / rg);                                  // f0
+  dp.cs_psi = 1.0 / rg;
+  dp.f_id = sqrt(inf_factor);
+  dp.W = W; dp.flags = flags; dp.retry_count = retry_count;
+  dp.dmax = kTab64Deg - 1;
+  dp.tab_hdr = tab->hdr; dp.tab_c = tab->c;
+  switch ((k + 15) >> 4) {
+    case 1: return patch64w_launch_t<1>(dp, stream);
+    case 2: return patch64w_launch_t<2>(dp, stream);
+    case 3: return patch64w_launch_t<3>(dp, stream);
+    case 4: return patch64w_launch_t<4>(dp, stream);
+    case 5: return patch64w_launch_t<5>(dp, stream);
+    case 6: return patch64w_launch_t<6>(dp, stream);
+    case 7: return patch64w_launch_t<7>(dp, stream);
+    case 8: return patch64w_launch_t<8>(dp, stream);
+  }
+  return MIA_ERR_UNSUPPORTED;
+}
+
+}  // namespace mia

@@ -164,6 +164,17 @@ int weights_stream64_launch(int k, int64_t ng, const double* rec, const int32_t*
                             const double* nbr_w, int p_cap, int p_max, double inf_factor, double* W, int32_t* flags,
                             int32_t* retry_count, hipStream_t stream);
 
+// letkf_patch64w.hip: letkf_stream64w.hip's weights with a tile's sixteen points taken from a map (4 x 4 patches of a 2-D mesh)
+// and the slot tables sized by the caller, 1 <= union_blocks <= 16 at every ensemble size.  weights_patch64_route_covers: shape
+// test (host only: 2 <= k <= 128, k < p_max <= 256, ng < 2^31 for the int32 map entries, k^2 8 < 2^31 for the 32-bit offset
+// inside a point's weights, the LDS of the largest image); weights_patch64_launch: MIA_ERR_UNSUPPORTED outside it, with
+// union_blocks outside 1 .. 16, more tiles than a launch grid holds, the option tile = 0, and when its coefficient table
+// cannot be had.  The map is validated by tile_union_census_launch (letkf_patch64.hip).
+bool weights_patch64_route_covers(int k, int p_max, int64_t ng);
+int weights_patch64_launch(int k, int64_t ng, const double* rec, const int32_t* nbr_cnt, const int32_t* nbr_idx,
+                           const double* nbr_w, int p_cap, int p_max, double inf_factor, double* W, int32_t* flags,
+                           int32_t* retry_count, const int32_t* tile_pts, int64_t n_tiles, int union_blocks, hipStream_t stream);
+
 // lienks_wide64.hip: lienks_tile64.hip's float64 IEnKS weight update with tau = 1 for ensembles up to 128 members on
 // letkf_wide64w.hip's frame (2 <= k <= 128, p_max <= k): the weights at inflation 1 with the innovations shifted by
 // D^T w_mean, the row blocks of the union split over two or four wavefronts.  lienks_wide64_route_covers: shape test (host

@@ -767,8 +767,10 @@ class LetkfEngine:
             ub -= 1
         return ub
 
-    def _patch64_map(self, nbrs: NeighbourLists, tile_points: torch.Tensor, union_blocks: Optional[int], k: int):
-        """The device copy of a tile map and the blocks of the record image for it.  The map is validated by
+    def _patch64_map(self, nbrs: NeighbourLists, tile_points: torch.Tensor, union_blocks: Optional[int], k: int,
+                     capacity: Optional[int] = None):
+        """The device copy of a tile map and the blocks of the record image for it (``capacity``: the largest image of the
+        route in sixteen-slot blocks; None = the dense route's at this ensemble size, weights_patch64 passes 16).  The map is validated by
         tile_union_census_kernel (every tile) and, with ``union_blocks=None``, the largest union of a tile counted; both come
         back in one 8-byte read.  The result is kept on ``nbrs`` under the map's identity, so a cycled filter pays once per
         geometry.  ValueError for a map that is not a partition of the shard's points, before any analysis launch.  Returns
@@ -777,7 +779,7 @@ class LetkfEngine:
         if (not isinstance(tile_points, torch.Tensor) or tile_points.dtype != torch.int32 or tile_points.dim() != 2
                 or tile_points.shape[1] != 16):
             raise ValueError("tile_points must be an int32 tensor (n_tiles, 16)")
-        cap = self._dense64_capacity_blocks(k)
+        cap = self._dense64_capacity_blocks(k) if capacity is None else int(capacity)
         if union_blocks is not None and not 1 <= int(union_blocks) <= cap:
             raise ValueError("union_blocks must lie in 1 .. %d at k = %d" % (cap, k))
         if nbrs.tile_census is None:
@@ -1017,9 +1019,11 @@ class LetkfEngine:
             retry, "mia_letkf_analysis_retry_" + sfx, lambda: (*args, _ptr(flags)), alive), defer_retry)
 
     def _weights_tile64(self, entry: str, who: str, Yb, d, nbrs: NeighbourLists, inf_factor, rec, out, return_flags, defer_retry,
-                        rbf_gamma):
-        """The body of :meth:`weights64`, :meth:`weights_wide64` and :meth:`weights_stream64`: the C ``entry`` of the route
-        and the public method's name ``who`` for the messages; arguments and answers as documented there."""
+                        rbf_gamma, more=None):
+        """The body of :meth:`weights64`, :meth:`weights_wide64`, :meth:`weights_stream64` and :meth:`weights_patch64`: the C
+        ``entry`` of the route and the public method's name ``who`` for the messages; arguments and answers as documented
+        there.  ``more(k)``: the entry's further arguments in front of the stream (weights_patch64's map, number of tiles and
+        blocks), asked for once the shapes have been checked and before the launch; None from it: the route does not cover."""
         if rec is None:
             if Yb.dim() != 2 or Yb.dtype != torch.float64:
                 return None
@@ -1046,7 +1050,12 @@ class LetkfEngine:
         shard = (nbrs.g1, 1, k, nbrs.g0, nbrs.g1, _ptr(rec), rec.shape[0], _ptr(nbrs.cnt), _ptr(nbrs.idx), _ptr(nbrs.w),
                  nbrs.p_cap, nbrs.p_max, float(inf_factor), gamma)
         tail = (n, 0, _ptr(W), _ptr(flags))
-        rc = getattr(self.lib, entry)(None, *shard, None, *tail, _ptr(retry), self._stream())
+        extra = ()
+        if more is not None:
+            extra = more(k)
+            if extra is None:
+                return None
+        rc = getattr(self.lib, entry)(None, *shard, None, *tail, _ptr(retry), *extra, self._stream())
         if rc == -3:
             return None
         _cabi.check(rc, entry)
@@ -1145,6 +1154,78 @@ class LetkfEngine:
         A point without observations gets sqrt(inf_factor) I exactly and flag 0."""
         return self._weights_tile64("mia_letkf_weights_stream_f64", "weights_stream64", Yb, d, nbrs, inf_factor, rec, out, return_flags,
                                     defer_retry, rbf_gamma)
+
+    # LETKF(..., mesh_shape=...).estimate_weights_arrays hands float64 weights of DENSE networks to weights_patch64 with the
+    # map of 4 x 4 patches where the census says every tile fits one pass (largest union <= 256), in two cases.  (a) Wherever
+    # _weights_stream64_auto already says yes (from 97 members on): the bits are weights_stream64's, nothing is compared with
+    # the Jacobi kernel.  (b) Where the Jacobi kernel runs: WEIGHTS_PATCH64_AUTO_MIN_K <= k <= WEIGHTS_PATCH64_AUTO_MAX_K and
+    # WEIGHTS_PATCH64_AUTO_DEN * p_max <= WEIGHTS_PATCH64_AUTO_NUM * k -- the range in which every MEASURED case is at least 2x
+    # the Jacobi kernel with W beyond both spreads, counter read included (tools/time_patch64w.py, profiles/patch64w_time.json,
+    # DESIGN 9).  Measured on MI355X, 316 x 316 meshes (224 x 224 at k = 128) with an observation at every point, radius 3 (3.5),
+    # p_max 101 (145), 4 x 4 patches, census (0.2 - 0.8 ms, first call only) outside, median ms, Jacobi kernel with W /
+    # weights_stream64 without a map / this route:
+    #   k  40:   80.3 /  853.3 /  226.2   0.35x the Jacobi kernel, LOSES      3.77x the route without a map
+    #   k  64:  280.2 / 1977.7 /  403.9   0.69x, LOSES                        4.90x
+    #   k  80: 1016.0 / 2630.1 /  770.3   1.32x, misses the factor 2          3.41x
+    #   k  96: 1684.0 / 5091.1 / 1040.4   1.62x, misses the factor 2          4.89x
+    #   k 128: MiaError / 6251.0 / 2426.7  (no Jacobi kernel)                 2.58x
+    # (spreads at most 0.1 % on the tile routes; W and flags bit-identical to the route without a map in all five).  NO case
+    # reaches 2x the Jacobi kernel, so the constants admit NOTHING where it runs: the class takes the map under (a) only, where
+    # it is 2.58x the route the class ran before (k = 128).  NOT measured: other radii, observations at every second point,
+    # ensembles between the measured sizes, 97 - 127 members.  weights_patch64 itself stays available everywhere the kernel covers
+    WEIGHTS_PATCH64_AUTO_MIN_K, WEIGHTS_PATCH64_AUTO_MAX_K = 129, 0
+    WEIGHTS_PATCH64_AUTO_NUM, WEIGHTS_PATCH64_AUTO_DEN = 0, 1
+    WEIGHTS_PATCH64_MAX_BLOCKS = 16        # kPatch64WMaxBlocks (csrc/letkf_patch64w.hip): 256 slots at every ensemble size
+
+    def _weights_patch64_auto(self, k: int, p_max: int) -> bool:
+        if k < 2 or k > 128 or p_max <= k or p_max > 256:
+            return False
+        if self._weights_stream64_auto(k, p_max):
+            return True
+        return (self.WEIGHTS_PATCH64_AUTO_MIN_K <= k <= self.WEIGHTS_PATCH64_AUTO_MAX_K
+                and self.WEIGHTS_PATCH64_AUTO_DEN * p_max <= self.WEIGHTS_PATCH64_AUTO_NUM * k)
+
+    def weights_patch64(self, Yb: Optional[torch.Tensor], d: Optional[torch.Tensor], nbrs: NeighbourLists,
+                        tile_points: torch.Tensor, inf_factor: float = 1.0, rec: Optional[torch.Tensor] = None,
+                        out: Optional[torch.Tensor] = None, return_flags: bool = False, defer_retry: bool = False,
+                        rbf_gamma: Optional[float] = None, union_blocks: Optional[int] = None):
+        """:meth:`weights_stream64` with the sixteen points of a tile taken from ``tile_points`` (mia_letkf_weights_patch_f64,
+        csrc/letkf_patch64w.hip): int32 (n_tiles, 16), a point's index relative to the shard's g0 or -1, every point exactly
+        once -- :func:`mesh_tiles` builds the 4 x 4 patches of a 2-D mesh, whose unions fit one pass where sixteen consecutive
+        points run in parts.  The same float64 weights W (n, k, k), 2 <= k <= 128, k < p_max <= 256, plain ETKF core, bit for
+        bit weights_stream64's under any map; the same arguments and the same answers -- W [, flags (n,)] [, finish], or None
+        where the route does not cover the shape or the entry answers MIA_ERR_UNSUPPORTED (any other shape, p_max <= k
+        included, float32 input, ``rbf_gamma``, option tile = 0).  ``union_blocks``: sixteen-slot blocks of the slot tables, 1
+        .. 16; None sizes them for the largest union of a tile, which the census of the map counts (one 8-byte read, kept on
+        ``nbrs`` under the map's identity and shared with ``analysis(tile_points=...)``: an analysis and a weights call with
+        the same lists and map pay one census); a tile whose union exceeds them runs in halves of its slots.  ValueError for
+        a map that is not a partition of the shard's points, a wrong dtype or shape of it and ``union_blocks`` outside 1 ..
+        16, before any launch.  Points the kernel declines are redone by the Jacobi kernel (mia_letkf_weights_retry_f64, from
+        the lists in natural order) behind the 8-byte read of the decline counter; with ``defer_retry`` that read is left to
+        the caller, who must invoke the trailing callable (it returns the number of points redone).  The Jacobi kernel cannot
+        hold a dense point from 97 members on: a declined point there makes the redo raise MiaError AFTER every other point
+        has been written -- data-dependent, the same raise as weights_stream64's.  A point without observations gets
+        sqrt(inf_factor) I exactly and flag 0."""
+        n = nbrs.g1 - nbrs.g0
+        cap = self.WEIGHTS_PATCH64_MAX_BLOCKS
+        if (not isinstance(tile_points, torch.Tensor) or tile_points.dtype != torch.int32 or tile_points.dim() != 2
+                or tile_points.shape[1] != 16):
+            raise ValueError("tile_points must be an int32 tensor (n_tiles, 16)")
+        if union_blocks is not None and not 1 <= int(union_blocks) <= cap:
+            raise ValueError("union_blocks must lie in 1 .. %d" % cap)
+
+        def more(k):
+            if n <= 0 or self.lib.mia_letkf_weights_patch_f64_cover(k, nbrs.p_max, n, rec.shape[0] if rec is not None else
+                                                                    Yb.shape[1]) != 1:
+                return None
+            tp, ub, _ = self._patch64_map(nbrs, tile_points, union_blocks, k, cap)
+            return (_ptr(tp), tp.shape[0], ub)
+        return self._weights_tile64("mia_letkf_weights_patch_f64", "weights_patch64", Yb, d, nbrs, inf_factor, rec, out, return_flags,
+                                    defer_retry, rbf_gamma, more)
+
+    def weights_patch64_fits(self, nbrs: NeighbourLists, tile_points: torch.Tensor, k: int) -> bool:
+        """Whether every tile of the map runs in ONE pass of weights_patch64 (largest union <= 256): the census, once per map."""
+        return self._patch64_map(nbrs, tile_points, None, k, self.WEIGHTS_PATCH64_MAX_BLOCKS)[2]
 
     # ------------------------------------------------------------------- IEnKS
     # ienks_update(method="auto") hands float64 updates with tau = 1 to the tile kernel (csrc/lienks_tile64.hip) only from this

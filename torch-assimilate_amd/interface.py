@@ -199,17 +199,23 @@ class LETKF(ETKF):
         self.chunksize = chunksize          # dask chunking of the reference; the GPU path does not chunk
         # (ny, nx) of a row-major 2-D mesh the grid points form: the float64 analysis then hands the engine a tile map of
         # 4 x 4 patches (engine.mesh_tiles), which the dense route takes under LetkfEngine.PATCH64_AUTO_*; the result is the
-        # same bit for bit.  Ignored (with a warning) when ny * nx is not the number of grid points; the weights paths, the
-        # kernelised filter and float32 never look at it
+        # same bit for bit; the float64 weights of dense networks (estimate_weights_arrays, weight_save_path) take the same map
+        # to engine.weights_patch64 under LetkfEngine.WEIGHTS_PATCH64_AUTO_*, bit for bit as well.  Ignored (with a warning)
+        # when ny * nx is not the number of grid points; the other weights paths, the kernelised filter, IEnKS and float32 never
+        # look at it
         self.mesh_shape = None if mesh_shape is None else (int(mesh_shape[0]), int(mesh_shape[1]))
         self._mesh_maps = {}
 
     def _mesh_map(self, x, nb):
         """The tile map of the shard's points on ``mesh_shape`` (built once per (g0, g1)), or None."""
-        if self.mesh_shape is None or x.dtype != torch.float64:
+        return self._mesh_map_of(x.dtype, x.shape[-1], nb)
+
+    def _mesh_map_of(self, dtype, G, nb):
+        """:meth:`_mesh_map` from the working precision and the number of grid points."""
+        if self.mesh_shape is None or dtype != torch.float64:
             return None
-        if self.mesh_shape[0] * self.mesh_shape[1] != x.shape[-1]:
-            warnings.warn("mesh_shape %r does not have the state's %d grid points: ignored" % (self.mesh_shape, x.shape[-1]),
+        if self.mesh_shape[0] * self.mesh_shape[1] != G:
+            warnings.warn("mesh_shape %r does not have the state's %d grid points: ignored" % (self.mesh_shape, G),
                           RuntimeWarning)
             return None
         key = (nb.g0, nb.g1)
@@ -279,6 +285,9 @@ class LETKF(ETKF):
         W = self._weights_on_wide64(yb, d, nb)
         if W is not None:
             return W
+        W = self._weights_on_patch64(yb, d, nb, G)
+        if W is not None:
+            return W
         W = self._weights_on_stream64(yb, d, nb)
         if W is not None:
             return W
@@ -290,6 +299,8 @@ class LETKF(ETKF):
             if err.status != -3:
                 raise
             W = self._weights_on_wide64(yb, d, nb, gated=False)
+            if W is None:
+                W = self._weights_on_patch64(yb, d, nb, G, gated=False)
             if W is None:
                 W = self._weights_on_stream64(yb, d, nb, gated=False)
             if W is None:
@@ -359,6 +370,28 @@ class LETKF(ETKF):
                 or nb.g1 - nb.g0 <= 0 or (gated and yb.shape[0] < self.engine.WEIGHTS_WIDE64_AUTO_MIN_K)):
             return None
         return self.engine.weights_wide64(yb, d, nb, self.inf_factor)
+
+    def _weights_on_patch64(self, yb, d, nb, G, gated=True):
+        """The float64 weights of DENSE local networks on a 2-D mesh (engine.weights_patch64, csrc/letkf_patch64w.hip) with
+        the map of 4 x 4 patches that ``mesh_shape`` gives, where that route applies: the default dtype, the plain ETKF core,
+        the kernel's cover (k <= 128, k < p_max <= 256), a census that says every tile fits ONE pass (a map that does not is
+        left to the routes below) and -- ``gated`` -- LetkfEngine._weights_patch64_auto(k, p_max): wherever
+        _weights_stream64_auto says yes (from 97 members on; the bits are that route's) and elsewhere only inside the measured
+        WEIGHTS_PATCH64_AUTO_*; ungated it serves where the Jacobi kernel answered MIA_ERR_UNSUPPORTED.  Declined points are
+        redone by the Jacobi kernel inside the engine call, with weights_stream64's data-dependent MiaError from 97 members on.
+        None: the caller goes on to :meth:`_weights_on_stream64`."""
+        ka = self._kernel_args()
+        eng = self.engine
+        k, n = int(yb.shape[0]), nb.g1 - nb.g0
+        if (self.mesh_shape is None or yb.dtype != torch.float64 or ka.get("rbf_gamma") is not None
+                or ka.get("kernel_program") is not None or n <= 0 or (gated and not eng._weights_patch64_auto(k, int(nb.p_max)))):
+            return None
+        if eng.lib.mia_letkf_weights_patch_f64_cover(k, int(nb.p_max), n, int(yb.shape[1])) != 1:
+            return None
+        tiles = self._mesh_map_of(yb.dtype, G, nb)
+        if tiles is None or not eng.weights_patch64_fits(nb, tiles, k):
+            return None
+        return eng.weights_patch64(yb, d, nb, tiles, self.inf_factor)
 
     def _weights_on_stream64(self, yb, d, nb, gated=True):
         """The float64 weights of DENSE local networks (engine.weights_stream64, csrc/letkf_stream64w.hip) where that route
