@@ -27,7 +27,7 @@ std::set<void*> g_allocs;
 thread_local struct { dim3 g, b; size_t shm; hipStream_t s; } t_cfg;
 struct StubEvent { std::atomic<long long> recorded{0}; };
 // ---- call trace
-std::atomic<bool> g_trace{false};
+std::atomic<bool> g_trace{false}, g_trace_attr{false};
 std::map<const void*, std::string>& kernel_names() { static auto* m = new std::map<const void*, std::string>(); return *m; }      // (filled by static initialisers)
 std::map<const void*, int> g_event_ids;
 int g_event_next = 0;
@@ -91,7 +91,8 @@ void* dev_alloc(size_t n) {
 extern "C" long long mia_stub_launch_count() { return g_launches.load(); }
 extern "C" long long mia_stub_live_allocations() { std::lock_guard<std::mutex> lk(g_mu); return (long long)g_allocs.size(); }
 // the call trace: switch it on or off; add a line of the driver's own (a communicator callback); print what was collected and forget it
-extern "C" void mia_stub_trace_enable(int on) { g_trace.store(on != 0); }
+// (bit 2 adds an "attr <kernel> <bytes>" line per hipFuncSetAttribute, for tests/test_tile_launch_trace.py; 1 alone traces as ever)
+extern "C" void mia_stub_trace_enable(int on) { g_trace.store(on != 0); g_trace_attr.store((on & 2) != 0); }
 extern "C" void mia_stub_trace_note(const char* text) {
   if (!g_trace.load()) return;
   std::lock_guard<std::mutex> lk(g_mu);
@@ -136,7 +137,14 @@ hipError_t hipStreamIsCapturing(hipStream_t, hipStreamCaptureStatus* st) { *st =
 hipError_t hipGetDevice(int* d) { *d = 0; return hipSuccess; }
 hipError_t hipSetDevice(int) { return hipSuccess; }
 hipError_t hipGetLastError(void) { return hipSuccess; }
-hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { return hipSuccess; }
+hipError_t hipFuncSetAttribute(const void* f, hipFuncAttribute, int bytes) {
+  if (g_trace_attr.load(std::memory_order_relaxed)) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    auto it = kernel_names().find(f);
+    trace("attr %s %d", it == kernel_names().end() ? "?" : short_name(it->second.c_str()).c_str(), bytes);
+  }
+  return hipSuccess;
+}
 hipError_t hipIpcGetMemHandle(hipIpcMemHandle_t*, void*) { return hipErrorNotSupported; }
 hipError_t hipIpcOpenMemHandle(void**, hipIpcMemHandle_t, unsigned) { return hipErrorNotSupported; }
 hipError_t hipIpcCloseMemHandle(void*) { return hipErrorNotSupported; }

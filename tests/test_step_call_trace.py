@@ -30,54 +30,19 @@ Which scenario takes which route decision of the step (names as in the driver's 
 The direct peer exchange is reachable: mia_comm_peer_attach maps a second communicator's buffers in-process, so peer_begin /
 peer_finish, mia_comm_peer_exchange and mia_comm_peer_rewait appear in the trace.  The error returns close the list.  A recording run
 writes the file and then FAILS, so that it cannot be taken for a check."""
-import importlib.util
 import os
-import shutil
 import subprocess
-from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "torch-assimilate_amd", "csrc")
-HERE = os.path.join(ROOT, "tests", "host_sanitize")
+from host_build import HIPCC, ROOT, link_driver
+
 GOLDEN = os.path.join(ROOT, "tests", "golden", "step_call_trace.txt")
-HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-
-
-def _build(tmp):
-    """tests/test_host_sanitizers.py's build without sanitizers, at -O0, with the trace driver."""
-    spec = importlib.util.spec_from_file_location("_mia_build", os.path.join(ROOT, "torch-assimilate_amd", "_build.py"))
-    bld = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(bld)
-    common = ["-O0", "-std=c++17", "-fPIC", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC]
-
-    def cc(src):
-        obj = os.path.join(tmp, os.path.basename(src) + ".o")
-        cmd = [HIPCC, "--offload-arch=gfx950", "--cuda-host-only", "-x", "hip"] + common + bld.SOURCE_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
-        res = subprocess.run(cmd, capture_output=True, text=True)
-        assert res.returncode == 0, res.stderr[-3000:]
-        return obj
-
-    with ThreadPoolExecutor(max_workers=min(16, len(os.sched_getaffinity(0)))) as ex:
-        objs = list(ex.map(cc, [os.path.join(CSRC, s) for s in bld.SOURCES]))
-    nm = subprocess.run(["nm", "-u"] + objs, capture_output=True, text=True).stdout
-    fat = sorted({l.split()[-1] for l in nm.splitlines() if "__hip_fatbin_" in l})
-    with open(os.path.join(tmp, "fatbin_stub.cc"), "w") as fh:
-        fh.write("".join('extern "C" { extern const char %s[16]; const char %s[16] = {0}; }\n' % (s, s) for s in fat))
-    exe = os.path.join(tmp, "trace_driver")
-    rocm_inc = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(HIPCC))), "include")
-    cmd = [HIPCC, "--cuda-host-only", "-x", "c++", "-D__HIP_PLATFORM_AMD__", "-I" + rocm_inc] + common + \
-          [os.path.join(HERE, "hip_stub.cc"), os.path.join(HERE, "trace_driver.cc"), os.path.join(tmp, "fatbin_stub.cc"), "-x", "none"] + objs + \
-          ["-ldl", "-pthread", "-o", exe]
-    res = subprocess.run(cmd, capture_output=True, text=True)
-    assert res.returncode == 0, res.stderr[-3000:]
-    return exe
 
 
 def test_step_driver_call_trace_matches_recorded(tmp_path):
     assert os.path.exists(HIPCC), "hipcc not found: the library cannot be built here either, and the step driver must not go unchecked"
-    exe = _build(str(tmp_path))
+    exe = link_driver(str(tmp_path), "trace_driver")
     env = {k: v for k, v in os.environ.items() if not k.startswith("MIA_")}
     runs = [subprocess.run([exe], capture_output=True, text=True, env=env, timeout=300) for _ in range(2)]
     for res in runs:

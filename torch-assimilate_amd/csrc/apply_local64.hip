@@ -48,6 +48,7 @@
 #include "mia_common.h"
 #include "mia_kernels.h"
 #include "mia_options.h"
+#include "mia_tile_launch.h"
 
 namespace mia {
 
@@ -288,17 +289,7 @@ int apply_global64_tile_launch(const double* X, int64_t ldx, int m, int k, int64
   Apply64Params p{X, ldx, m, k, g0, ng, W, Xa, ldo, o0, (k + 3) & ~3, 0};
   const int kt = (k + 15) >> 4;
   void (*kern)(Apply64Params) = nullptr;
-  switch (kt) {
-    case 1: kern = apply_global64_tile_kernel<1>; break;
-    case 2: kern = apply_global64_tile_kernel<2>; break;
-    case 3: kern = apply_global64_tile_kernel<3>; break;
-    case 4: kern = apply_global64_tile_kernel<4>; break;
-    case 5: kern = apply_global64_tile_kernel<5>; break;
-    case 6: kern = apply_global64_tile_kernel<6>; break;
-    case 7: kern = apply_global64_tile_kernel<7>; break;
-    case 8: kern = apply_global64_tile_kernel<8>; break;
-    default: return MIA_ERR_UNSUPPORTED;
-  }
+  if (dispatch_upto<8>(kt, [&](auto kt_c) { kern = apply_global64_tile_kernel<kt_c()>; return MIA_OK; }) != MIA_OK) return MIA_ERR_UNSUPPORTED;
   kern<<<dim3((unsigned)nb), dim3(256), 0, stream>>>(p);
   MIA_LAUNCH_CHECK();
   note_transform_kernel("apply_global64_tile_kernel<%d>", kt);
@@ -314,17 +305,7 @@ int apply_local64_tile_launch(const double* X, int64_t ldx, int m, int k, int64_
   const size_t lds = apply_local64_lds_bytes(k);
   const int kt = (k + 15) >> 4;
   void (*kern)(Apply64Params) = nullptr;
-  switch (kt) {
-    case 1: kern = apply_local64_tile_kernel<1>; break;
-    case 2: kern = apply_local64_tile_kernel<2>; break;
-    case 3: kern = apply_local64_tile_kernel<3>; break;
-    case 4: kern = apply_local64_tile_kernel<4>; break;
-    case 5: kern = apply_local64_tile_kernel<5>; break;
-    case 6: kern = apply_local64_tile_kernel<6>; break;
-    case 7: kern = apply_local64_tile_kernel<7>; break;
-    case 8: kern = apply_local64_tile_kernel<8>; break;
-    default: return MIA_ERR_UNSUPPORTED;
-  }
+  if (dispatch_upto<8>(kt, [&](auto kt_c) { kern = apply_local64_tile_kernel<kt_c()>; return MIA_OK; }) != MIA_OK) return MIA_ERR_UNSUPPORTED;
   if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   kern<<<dim3((unsigned)ntile), dim3(256), lds, stream>>>(p);
   MIA_LAUNCH_CHECK();

@@ -33,6 +33,7 @@
 #include "mia_localize_dev.h"
 #include "mia_kernels.h"
 #include "mia_options.h"
+#include "mia_tile_launch.h"
 
 namespace mia {
 
@@ -1463,19 +1464,16 @@ __global__ __launch_bounds__(64) void letkf_cheb_big_kernel(ChebParams P) {
   }
 }
 
+// the orders the kernels are built for (ntrue rounded up); weights and row batches end at 48
+static const int kChebOrders[] = {4, 8, 12, 16, 20, 24, 32, 40, 48, 64};
+template <typename F>
+static int cheb_for_order(int nmax, F&& f) { return dispatch_among<64, 48, 40, 32, 24, 20, 16, 12, 8, 4>(nmax, f); }
+
 template <int NMAX>
 static int cheb_launch_big(const ChebParams& ap, hipStream_t stream) {
   const size_t e = (size_t)NMAX * (NMAX + 4) + 4 * (size_t)NMAX + 16 + 4 * 64 + 8 + (size_t)((ap.p_max + 3) & ~1);
   const size_t lds = align_up(e * sizeof(float) + (size_t)((ap.p_max + 3) & ~1) * sizeof(int), 16);
-  if (lds > kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
-  auto kern = letkf_cheb_big_kernel<NMAX>;
-  if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t gx = ap.ng < 65536 ? ap.ng : 65536;
-  const int64_t gy = (ap.ng + gx - 1) / gx;
-  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
-  kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(64), lds, stream>>>(ap);
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
+  return launch_blocks(letkf_cheb_big_kernel<NMAX>, ap.ng, 64, lds, stream, no_note, ap);
 }
 
 static size_t cheb_lds_bytes(int kp, int p_max, int nmax, int rows, bool dual, bool batch = false, int k_weights = 0,
@@ -1497,14 +1495,7 @@ static size_t cheb_lds_bytes(int kp, int p_max, int nmax, int rows, bool dual, b
 template <int NMAX>
 static int cheb_launch_weights(const ChebParams& ap, size_t lds, hipStream_t stream) {
   if constexpr (NMAX <= 48) {
-    auto kern = letkf_cheb_weights_kernel<NMAX>;
-    if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int64_t gx = ap.ng < 65536 ? ap.ng : 65536;
-    const int64_t gy = (ap.ng + gx - 1) / gx;
-    if (gy > 65535) return MIA_ERR_UNSUPPORTED;
-    kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(64), lds, stream>>>(ap);
-    MIA_LAUNCH_CHECK();
-    return MIA_OK;
+    return launch_blocks(letkf_cheb_weights_kernel<NMAX>, ap.ng, 64, lds, stream, no_note, ap);
   } else {
     return MIA_ERR_UNSUPPORTED;
   }
@@ -1513,14 +1504,7 @@ static int cheb_launch_weights(const ChebParams& ap, size_t lds, hipStream_t str
 template <int NMAX>
 static int cheb_launch_rows(const ChebParams& ap, size_t lds, hipStream_t stream) {
   if constexpr (NMAX <= 48) {
-    auto kern = letkf_cheb_rows_kernel<NMAX>;
-    if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const int64_t gx = ap.ng < 65536 ? ap.ng : 65536;
-    const int64_t gy = (ap.ng + gx - 1) / gx;
-    if (gy > 65535) return MIA_ERR_UNSUPPORTED;
-    kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(64), lds, stream>>>(ap);
-    MIA_LAUNCH_CHECK();
-    return MIA_OK;
+    return launch_blocks(letkf_cheb_rows_kernel<NMAX>, ap.ng, 64, lds, stream, no_note, ap);
   } else {
     return MIA_ERR_UNSUPPORTED;
   }
@@ -1528,21 +1512,12 @@ static int cheb_launch_rows(const ChebParams& ap, size_t lds, hipStream_t stream
 
 template <int NMAX, int KL, bool FUSED, int WPB>
 static int cheb_launch_w(const ChebParams& ap, size_t lds, hipStream_t stream) {
-  auto kern = letkf_cheb_kernel<NMAX, KL, FUSED, WPB>;
-  const size_t tot = lds * WPB;
-  if (tot > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tot));
-  const int64_t nblk = (ap.ng + WPB - 1) / WPB;
-  const int64_t gx = nblk < 65536 ? nblk : 65536;
-  const int64_t gy = (nblk + gx - 1) / gx;
-  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
-  kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(64 * WPB), tot, stream>>>(ap);
-  note_analysis_kernel("letkf_cheb_kernel<%d, %d, %s, %d>", NMAX, KL, FUSED ? "true" : "false", WPB);
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
+  return launch_blocks(letkf_cheb_kernel<NMAX, KL, FUSED, WPB>, (ap.ng + WPB - 1) / WPB, 64 * WPB, lds * WPB, stream,
+                       [] { note_analysis_kernel("letkf_cheb_kernel<%d, %d, %s, %d>", NMAX, KL, FUSED ? "true" : "false", WPB); }, ap);
 }
 
 template <int NMAX, int KL, bool FUSED>
-static int cheb_launch(const ChebParams& ap, size_t lds, dim3, hipStream_t stream) {
+static int cheb_launch(const ChebParams& ap, size_t lds, hipStream_t stream) {
   // four independent points per workgroup when their LDS slices fit comfortably
   if (MIA_EXP_FLAG("MIA_CHEB_WPB4") && lds * 4 <= 40 * 1024) return cheb_launch_w<NMAX, KL, FUSED, 4>(ap, lds, stream);
   return cheb_launch_w<NMAX, KL, FUSED, 1>(ap, lds, stream);
@@ -1550,14 +1525,7 @@ static int cheb_launch(const ChebParams& ap, size_t lds, dim3, hipStream_t strea
 
 template <int NMAX, int KL>
 static int cheb_launch_seg(const ChebParams& ap, size_t lds, hipStream_t stream) {
-  auto kern = letkf_cheb_seg_kernel<NMAX, KL>;
-  if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t gx = ap.ng < 65536 ? ap.ng : 65536;
-  const int64_t gy = (ap.ng + gx - 1) / gx;
-  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
-  kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(64), lds, stream>>>(ap);
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
+  return launch_blocks(letkf_cheb_seg_kernel<NMAX, KL>, ap.ng, 64, lds, stream, no_note, ap);
 }
 
 int segment_wait_launch(const int32_t* done64, int expected, int32_t* err, hipStream_t stream) {
@@ -1625,9 +1593,8 @@ int cheb_analysis_launch(const float* X, int64_t ldx, int m, int k, int64_t g0, 
     if (k <= 112) return cheb_launch_big<112>(ap, stream);
     return cheb_launch_big<128>(ap, stream);
   }
-  static const int buckets[] = {4, 8, 12, 16, 20, 24, 32, 40, 48, 64};
   int nmax = 0;
-  for (int b : buckets) if (b >= ntrue) { nmax = b; break; }
+  for (int b : kChebOrders) if (b >= ntrue) { nmax = b; break; }
   if (nmax == 0 || k > 128) return MIA_ERR_UNSUPPORTED;
   ap.rows = ap.dual ? nmax : 0;      // the primal route streams the records: no local block in LDS
   // N = deg + 1 coefficient lanes <= 64; 62 covers lambda_max / reg up to ~100 (dense local networks, p >> k)
@@ -1659,10 +1626,7 @@ int cheb_analysis_launch(const float* X, int64_t ldx, int m, int k, int64_t g0, 
   const size_t lds = cheb_lds_bytes(ap.kp, p_max, nmax, ap.rows, ap.dual != 0, false, 0, ap.fused != 0);
   if (lds > (long long)kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
   ap.lds_per_wave = (int)lds;
-  const int64_t gx = ng < 65536 ? ng : 65536;
-  const int64_t gy = (ng + gx - 1) / gx;
-  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)gx, (unsigned)gy);
+  if (!grid_covers(ng)) return MIA_ERR_UNSUPPORTED;
   const bool two = k > 64;
   if (W_out) {   // weights output: dual route up to order 32, primal route (linear / RBF) up to k = 48, one member per lane
     const bool ok_dual = ap.dual && nmax <= 32;
@@ -1670,52 +1634,20 @@ int cheb_analysis_launch(const float* X, int64_t ldx, int m, int k, int64_t g0, 
     if (!((ok_dual || ok_primal) && !two && !ap.fused && seg_len == 0)) return MIA_ERR_UNSUPPORTED;
     ap.lds_per_wave = (int)cheb_lds_bytes(ap.kp, p_max, nmax, ap.rows, ap.dual != 0, false, k);
     if (ap.lds_per_wave > (long long)kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
-    switch (nmax) {
-      case 4: return cheb_launch_weights<4>(ap, ap.lds_per_wave, stream);
-      case 8: return cheb_launch_weights<8>(ap, ap.lds_per_wave, stream);
-      case 12: return cheb_launch_weights<12>(ap, ap.lds_per_wave, stream);
-      case 16: return cheb_launch_weights<16>(ap, ap.lds_per_wave, stream);
-      case 20: return cheb_launch_weights<20>(ap, ap.lds_per_wave, stream);
-      case 24: return cheb_launch_weights<24>(ap, ap.lds_per_wave, stream);
-      case 32: return cheb_launch_weights<32>(ap, ap.lds_per_wave, stream);
-      case 40: return cheb_launch_weights<40>(ap, ap.lds_per_wave, stream);
-      case 48: return cheb_launch_weights<48>(ap, ap.lds_per_wave, stream);
-    }
-    return MIA_ERR_UNSUPPORTED;
+    return cheb_for_order(nmax, [&](auto n) { return cheb_launch_weights<n()>(ap, ap.lds_per_wave, stream); });
   }
   // many state rows: batches of 16 rows on the matrix cores (dual route, order <= 32, one member per lane)
   if (m >= 8 && ((ap.dual && nmax <= 32) || (!ap.dual && nmax <= 48)) && !two && !ap.fused && seg_len == 0 &&
       option(MIA_OPT_CHEB_ROWBATCH)) {
     ap.lds_per_wave = (int)cheb_lds_bytes(ap.kp, p_max, nmax, ap.rows, ap.dual != 0, true);
-    switch (nmax) {
-      case 4: return cheb_launch_rows<4>(ap, ap.lds_per_wave, stream);
-      case 8: return cheb_launch_rows<8>(ap, ap.lds_per_wave, stream);
-      case 12: return cheb_launch_rows<12>(ap, ap.lds_per_wave, stream);
-      case 16: return cheb_launch_rows<16>(ap, ap.lds_per_wave, stream);
-      case 20: return cheb_launch_rows<20>(ap, ap.lds_per_wave, stream);
-      case 24: return cheb_launch_rows<24>(ap, ap.lds_per_wave, stream);
-      case 32: return cheb_launch_rows<32>(ap, ap.lds_per_wave, stream);
-      case 40: return cheb_launch_rows<40>(ap, ap.lds_per_wave, stream);
-      case 48: return cheb_launch_rows<48>(ap, ap.lds_per_wave, stream);
-    }
+    return cheb_for_order(nmax, [&](auto n) { return cheb_launch_rows<n()>(ap, ap.lds_per_wave, stream); });
   }
-  if (seg_len > 0) {
-#define MIA_CHEB_SEG(N) case N: return two ? cheb_launch_seg<N, 2>(ap, lds, stream) : cheb_launch_seg<N, 1>(ap, lds, stream);
-    switch (nmax) {
-      MIA_CHEB_SEG(4) MIA_CHEB_SEG(8) MIA_CHEB_SEG(12) MIA_CHEB_SEG(16) MIA_CHEB_SEG(20)
-      MIA_CHEB_SEG(24) MIA_CHEB_SEG(32) MIA_CHEB_SEG(40) MIA_CHEB_SEG(48) MIA_CHEB_SEG(64)
-    }
-#undef MIA_CHEB_SEG
-    return MIA_ERR_UNSUPPORTED;
-  }
-#define MIA_CHEB_CASE(N) case N: return ap.fused ? (two ? cheb_launch<N, 2, true>(ap, lds, grid, stream) : cheb_launch<N, 1, true>(ap, lds, grid, stream)) \
-                                        : (two ? cheb_launch<N, 2, false>(ap, lds, grid, stream) : cheb_launch<N, 1, false>(ap, lds, grid, stream));
-  switch (nmax) {
-    MIA_CHEB_CASE(4) MIA_CHEB_CASE(8) MIA_CHEB_CASE(12) MIA_CHEB_CASE(16) MIA_CHEB_CASE(20)
-    MIA_CHEB_CASE(24) MIA_CHEB_CASE(32) MIA_CHEB_CASE(40) MIA_CHEB_CASE(48) MIA_CHEB_CASE(64)
-  }
-#undef MIA_CHEB_CASE
-  return MIA_ERR_UNSUPPORTED;
+  if (seg_len > 0)
+    return cheb_for_order(nmax, [&](auto n) { return two ? cheb_launch_seg<n(), 2>(ap, lds, stream) : cheb_launch_seg<n(), 1>(ap, lds, stream); });
+  return cheb_for_order(nmax, [&](auto n) {
+    return ap.fused ? (two ? cheb_launch<n(), 2, true>(ap, lds, stream) : cheb_launch<n(), 1, true>(ap, lds, stream))
+                    : (two ? cheb_launch<n(), 2, false>(ap, lds, stream) : cheb_launch<n(), 1, false>(ap, lds, stream));
+  });
 }
 
 }  // namespace mia

@@ -36,6 +36,8 @@
 // that holds a non-finite record is analysed point by point.  Points whose degree exceeds the table's cap are DECLINED
 // (MIA_FLAG_RETRY, counted, Xa untouched) and redone by letkf_wave_kernel<double>.
 #include "mia_cheb_table64.h"
+#include "mia_frames64.h"
+#include "mia_tile_launch.h"
 
 namespace mia {
 
@@ -392,48 +394,19 @@ __global__ __launch_bounds__(64, 1) void letkf_dense64_kernel(Dense64Params P) {
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-constexpr int kDense64MaxBlocks = 16;                          // 256 slots, where the record image fits
-
-static size_t dense64_lds_bytes(int ub, int kp) {
-  const int umax = 16 * ub;
-  return align_up(((size_t)umax * (kp | 1) + 16 * (size_t)(umax + 1)) * sizeof(double) + (size_t)umax * sizeof(int), 16);
-}
-// sixteen-slot blocks the record image of this ensemble size may have
-static int dense64_capacity_blocks(int k) {
-  const int kp = (k + 1 + 3) & ~3;
-  int ub = kDense64MaxBlocks;
-  while (ub > 0 && dense64_lds_bytes(ub, kp) > kMaxDynamicLds) --ub;
-  return ub;
-}
-// ... and the blocks a launch takes: the longest list plus what sixteen consecutive points of a regular network add (one
-// observation per point at stride 1).  Fewer slots = more workgroups per compute unit; a tile that needs more is halved.
-static int dense64_blocks(int k, int p_max) {
-  const int cap = dense64_capacity_blocks(k), want = (p_max + 16 + 15) >> 4;
-  return want < cap ? want : cap;
-}
-
+// launches with the sizes of the resident image (mia_frames64.h): its capacity at this ensemble size, its blocks for p_max
 bool dense64_route_covers(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t ng) {
   if (m < 1 || k < 2 || k > 64 || p_max <= k || ldx < 1 || ldo < 1 || ng < 0) return false;     // p_max <= k: letkf_tile64.hip
-  if (p_max > 16 * dense64_capacity_blocks(k)) return false;
+  if (p_max > 16 * resident64_capacity_blocks(k)) return false;
   // the state and the output are addressed as wave-uniform base + 32-bit byte offset of a column of one state row block
   if ((int64_t)k * ldx * 8 >= ((int64_t)1 << 31) || (int64_t)k * ldo * 8 >= ((int64_t)1 << 31)) return false;
-  return ((ng + 15) >> 4) <= (int64_t)65536 * 65535;
+  return grid_covers((ng + 15) >> 4);
 }
 
 template <int KT>
 static int dense64_launch_t(const Dense64Params& dp, hipStream_t stream) {
-  const size_t lds = dense64_lds_bytes(dp.ub, dp.kp);
-  if (lds > kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
-  auto kern = letkf_dense64_kernel<KT>;
-  if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t ntile = (dp.ng + 15) >> 4;
-  const int64_t gx = ntile < 65536 ? ntile : 65536;
-  const int64_t gy = (ntile + gx - 1) / gx;
-  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
-  kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(64), lds, stream>>>(dp);
-  note_analysis_kernel("letkf_dense64_kernel<%d>", KT);
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
+  return launch_blocks(letkf_dense64_kernel<KT>, (dp.ng + 15) >> 4, 64, resident64_lds_bytes(dp.ub, dp.kp), stream,
+                       [] { note_analysis_kernel("letkf_dense64_kernel<%d>", KT); }, dp);
 }
 
 int dense64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t ng, const double* rec,
@@ -448,7 +421,7 @@ int dense64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t 
   dp.X = X; dp.ldx = ldx; dp.m = m; dp.k = k; dp.kp = (k + 1 + 3) & ~3;
   dp.g0 = g0; dp.ng = ng; dp.rec = rec;
   dp.cnt = nbr_cnt; dp.idx = nbr_idx; dp.w = nbr_w; dp.p_cap = p_cap; dp.p_max = p_max;
-  dp.ub = dense64_blocks(k, p_max);
+  dp.ub = resident64_blocks(k, p_max);
   const double rg = (double)(k - 1) / inf_factor, km = (double)(k - 1);
   dp.reg = rg;
   dp.inv_reg = 1.0 / rg;
@@ -458,13 +431,7 @@ int dense64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t 
   dp.Xa = Xa; dp.ldo = ldo; dp.o0 = o0; dp.flags = flags; dp.retry_count = retry_count;
   dp.dmax = kTab64Deg - 1;
   dp.tab_hdr = tab->hdr; dp.tab_c = tab->c;
-  switch ((k + 15) >> 4) {
-    case 1: return dense64_launch_t<1>(dp, stream);
-    case 2: return dense64_launch_t<2>(dp, stream);
-    case 3: return dense64_launch_t<3>(dp, stream);
-    case 4: return dense64_launch_t<4>(dp, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
+  return dispatch_upto<4>((k + 15) >> 4, [&](auto kt) { return dense64_launch_t<kt()>(dp, stream); });
 }
 
 }  // namespace mia

@@ -24,6 +24,8 @@
 // dense route's code generation -- registers, the placement of loads beside matrix instructions -- would have to be
 // re-verified; the project's precedent is the same (letkf_stream64.hip, lketkf_kern64.hip).
 #include "mia_cheb_table64.h"
+#include "mia_frames64.h"
+#include "mia_tile_launch.h"
 #include "mia_kernels.h"
 
 namespace mia {
@@ -455,40 +457,12 @@ __global__ __launch_bounds__(64) void tile_union_census_kernel(const int32_t* ti
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-// (the record image is letkf_dense64.hip's: the same bytes, the same capacity)
-constexpr int kPatch64MaxBlocks = 16;                          // 256 slots, where the record image fits
-
-static size_t patch64_lds_bytes(int ub, int kp) {
-  const int umax = 16 * ub;
-  return align_up(((size_t)umax * (kp | 1) + 16 * (size_t)(umax + 1)) * sizeof(double) + (size_t)umax * sizeof(int), 16);
-}
-int patch64_capacity_blocks(int k) {
-  const int kp = (k + 1 + 3) & ~3;
-  int ub = kPatch64MaxBlocks;
-  while (ub > 0 && patch64_lds_bytes(ub, kp) > kMaxDynamicLds) --ub;
-  return ub;
-}
-
-static bool patch64_grid(int64_t ntile, dim3* grid) {
-  const int64_t gx = ntile < 65536 ? ntile : 65536;
-  const int64_t gy = (ntile + gx - 1) / gx;
-  if (gy > 65535) return false;
-  *grid = dim3((unsigned)gx, (unsigned)gy);
-  return true;
-}
-
+// launches with the sizes of the resident image (mia_frames64.h), as letkf_dense64.hip: the same bytes, the same capacity; the
+// caller chooses the blocks
 template <int KT>
 static int patch64_launch_t(const Patch64Params& dp, hipStream_t stream) {
-  const size_t lds = patch64_lds_bytes(dp.ub, dp.kp);
-  if (lds > kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
-  auto kern = letkf_patch64_kernel<KT>;
-  if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  dim3 grid;
-  if (!patch64_grid(dp.n_tiles, &grid)) return MIA_ERR_UNSUPPORTED;
-  kern<<<grid, dim3(64), lds, stream>>>(dp);
-  note_analysis_kernel("letkf_patch64_kernel<%d>", KT);
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
+  return launch_blocks(letkf_patch64_kernel<KT>, dp.n_tiles, 64, resident64_lds_bytes(dp.ub, dp.kp), stream,
+                       [] { note_analysis_kernel("letkf_patch64_kernel<%d>", KT); }, dp);
 }
 
 int patch64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t ng, const double* rec,
@@ -497,8 +471,8 @@ int patch64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t 
                             const int32_t* tile_pts, int64_t n_tiles, int union_blocks, hipStream_t stream) {
   if (!option(MIA_OPT_TILE) || !flags || !retry_count) return MIA_ERR_UNSUPPORTED;
   if (!dense64_route_covers(m, k, p_max, ldx, ldo, ng)) return MIA_ERR_UNSUPPORTED;
-  if (ng >= ((int64_t)1 << 31) || n_tiles > (int64_t)65536 * 65535) return MIA_ERR_UNSUPPORTED;   // (map entries are int32)
-  if (union_blocks < 1 || union_blocks > patch64_capacity_blocks(k) || n_tiles < 1) return MIA_ERR_SIZE;
+  if (ng >= ((int64_t)1 << 31) || !grid_covers(n_tiles)) return MIA_ERR_UNSUPPORTED;   // (map entries are int32)
+  if (union_blocks < 1 || union_blocks > resident64_capacity_blocks(k) || n_tiles < 1) return MIA_ERR_SIZE;
   const CoefTable64* tab = cheb_coef_table64(stream, kTab64Primal);
   if (!tab) return MIA_ERR_UNSUPPORTED;
   Patch64Params dp;
@@ -516,19 +490,13 @@ int patch64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t 
   dp.Xa = Xa; dp.ldo = ldo; dp.o0 = o0; dp.flags = flags; dp.retry_count = retry_count;
   dp.dmax = kTab64Deg - 1;
   dp.tab_hdr = tab->hdr; dp.tab_c = tab->c;
-  switch ((k + 15) >> 4) {
-    case 1: return patch64_launch_t<1>(dp, stream);
-    case 2: return patch64_launch_t<2>(dp, stream);
-    case 3: return patch64_launch_t<3>(dp, stream);
-    case 4: return patch64_launch_t<4>(dp, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
+  return dispatch_upto<4>((k + 15) >> 4, [&](auto kt) { return patch64_launch_t<kt()>(dp, stream); });
 }
 
 int tile_union_census_launch(const int32_t* tile_pts, int64_t n_tiles, int64_t ng, const int32_t* nbr_cnt, const int32_t* nbr_idx,
                              int p_cap, int p_max, int count_unions, int32_t* out2, int32_t* ws, hipStream_t stream) {
   dim3 grid;
-  if (ng >= ((int64_t)1 << 31) - 2 || n_tiles >= ((int64_t)1 << 31) || !patch64_grid(n_tiles, &grid)) return MIA_ERR_UNSUPPORTED;
+  if (ng >= ((int64_t)1 << 31) - 2 || n_tiles >= ((int64_t)1 << 31) || !launch_grid(n_tiles, &grid)) return MIA_ERR_UNSUPPORTED;
   MIA_HIP_TRY(hipMemsetAsync(ws, 0, (size_t)(ng + 2) * sizeof(int32_t), stream));
   MIA_HIP_TRY(hipMemsetAsync(out2, 0, 2 * sizeof(int32_t), stream));
   tile_union_census_kernel<<<grid, dim3(64), 0, stream>>>(tile_pts, n_tiles, ng, nbr_cnt, nbr_idx, p_cap, p_max, count_unions, ws,

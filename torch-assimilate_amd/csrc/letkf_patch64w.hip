@@ -27,6 +27,8 @@
 // The kernel is a copy of letkf_patch64w_kernel with the frame changed, not a shared body (DESIGN 2.18 on letkf_patch64.hip:
 // the map reaches every address the frame forms, and the parent's code object stays what it was).
 #include "mia_cheb_table64.h"
+#include "mia_frames64.h"
+#include "mia_tile_launch.h"
 
 namespace mia {
 
@@ -463,39 +465,23 @@ __global__ __launch_bounds__(64, 1) void letkf_patch64w_kernel(Patch64WParams P)
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-constexpr int kPatch64WMaxBlocks = 16;                          // 256 slots, at every ensemble size of the route
+constexpr int kPatch64WMaxBlocks = kRing64MaxBlocks;            // union_blocks of the caller: 256 slots, at every ensemble size of the route
 constexpr int kPatch64WMaxK = 128;
-
-// letkf_stream64w.hip's: ring [2][16][kp | 1] + rhs [4 KT][64] + sqrt(rho) [16][16 ub + 1] doubles, slot table [16 ub] ints
-static size_t patch64w_lds_bytes(int ub, int k) {
-  const int umax = 16 * ub, kp = (k + 1 + 3) & ~3, kt = (k + 15) >> 4;
-  return align_up(((size_t)2 * 16 * (kp | 1) + (size_t)4 * kt * 64 + 16 * (size_t)(umax + 1)) * sizeof(double) +
-                  (size_t)umax * sizeof(int), 16);
-}
 
 bool weights_patch64_route_covers(int k, int p_max, int64_t ng) {
   if (k < 2 || k > kPatch64WMaxK || p_max <= k || ng < 0) return false;                 // p_max <= k: the dual routes
   if (p_max > 16 * kPatch64WMaxBlocks) return false;
   // a lane addresses W as its point's 64-bit base + a 32-bit byte offset inside that point's k x k block; map entries are int32
   if ((int64_t)k * k * 8 >= ((int64_t)1 << 31) || ng >= ((int64_t)1 << 31)) return false;
-  if (patch64w_lds_bytes(kPatch64WMaxBlocks, k) > kMaxDynamicLds) return false;          // (the largest image; holds at every k: tests/test_patch64w_cover.py)
+  if (ring64_lds_bytes(kPatch64WMaxBlocks, k) > kMaxDynamicLds) return false;       // (the largest image; holds at every k: tests/test_patch64w_cover.py)
   return true;
 }
 
+// launches with the sizes of the ring frame (mia_frames64.h)
 template <int KT>
 static int patch64w_launch_t(const Patch64WParams& dp, hipStream_t stream) {
-  const size_t lds = patch64w_lds_bytes(dp.ub, dp.k);
-  if (lds > kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
-  auto kern = letkf_patch64w_kernel<KT>;
-  if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t ntile = dp.n_tiles;
-  const int64_t gx = ntile < 65536 ? ntile : 65536;
-  const int64_t gy = (ntile + gx - 1) / gx;
-  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
-  kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(64), lds, stream>>>(dp);
-  note_analysis_kernel("letkf_patch64w_kernel<%d>", KT);
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
+  return launch_blocks(letkf_patch64w_kernel<KT>, dp.n_tiles, 64, ring64_lds_bytes(dp.ub, dp.k), stream,
+                       [] { note_analysis_kernel("letkf_patch64w_kernel<%d>", KT); }, dp);
 }
 
 int weights_patch64_launch(int k, int64_t ng, const double* rec, const int32_t* nbr_cnt, const int32_t* nbr_idx,
@@ -503,7 +489,7 @@ int weights_patch64_launch(int k, int64_t ng, const double* rec, const int32_t* 
                            int32_t* retry_count, const int32_t* tile_pts, int64_t n_tiles, int union_blocks, hipStream_t stream) {
   if (!option(MIA_OPT_TILE) || !W || !flags || !retry_count || !tile_pts) return MIA_ERR_UNSUPPORTED;
   if (!weights_patch64_route_covers(k, p_max, ng)) return MIA_ERR_UNSUPPORTED;
-  if (union_blocks < 1 || union_blocks > kPatch64WMaxBlocks || n_tiles < 1 || n_tiles > (int64_t)65536 * 65535) return MIA_ERR_UNSUPPORTED;
+  if (union_blocks < 1 || union_blocks > kPatch64WMaxBlocks || n_tiles < 1 || !grid_covers(n_tiles)) return MIA_ERR_UNSUPPORTED;
   const CoefTable64* tab = cheb_coef_table64(stream, kTab64Primal);
   if (!tab) return MIA_ERR_UNSUPPORTED;
   Patch64WParams dp;
@@ -521,17 +507,7 @@ int weights_patch64_launch(int k, int64_t ng, const double* rec, const int32_t* 
   dp.W = W; dp.flags = flags; dp.retry_count = retry_count;
   dp.dmax = kTab64Deg - 1;
   dp.tab_hdr = tab->hdr; dp.tab_c = tab->c;
-  switch ((k + 15) >> 4) {
-    case 1: return patch64w_launch_t<1>(dp, stream);
-    case 2: return patch64w_launch_t<2>(dp, stream);
-    case 3: return patch64w_launch_t<3>(dp, stream);
-    case 4: return patch64w_launch_t<4>(dp, stream);
-    case 5: return patch64w_launch_t<5>(dp, stream);
-    case 6: return patch64w_launch_t<6>(dp, stream);
-    case 7: return patch64w_launch_t<7>(dp, stream);
-    case 8: return patch64w_launch_t<8>(dp, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
+  return dispatch_upto<8>((k + 15) >> 4, [&](auto kt) { return patch64w_launch_t<kt()>(dp, stream); });
 }
 
 }  // namespace mia

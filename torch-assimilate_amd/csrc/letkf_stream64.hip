@@ -48,6 +48,8 @@
 // that holds a non-finite record is analysed point by point.  Points whose degree exceeds the table's cap are DECLINED
 // (MIA_FLAG_RETRY, counted, Xa untouched) and redone by letkf_wave_kernel<double> where that kernel holds the shape.
 #include "mia_cheb_table64.h"
+#include "mia_frames64.h"
+#include "mia_tile_launch.h"
 
 namespace mia {
 
@@ -500,45 +502,22 @@ __global__ __launch_bounds__(64, 1) void letkf_stream64_kernel(Stream64Params P)
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-constexpr int kStream64MaxBlocks = 16;                         // 256 slots, at every ensemble size of the route
 constexpr int kStream64MaxK = 128;
-
-// ring [2][16][kp | 1] + rhs [4 KT][64] + sqrt(rho) [16][16 ub + 1] doubles, slot table [16 ub] ints
-static size_t stream64_lds_bytes(int ub, int k) {
-  const int umax = 16 * ub, kp = (k + 1 + 3) & ~3, kt = (k + 15) >> 4;
-  return align_up(((size_t)2 * 16 * (kp | 1) + (size_t)4 * kt * 64 + 16 * (size_t)(umax + 1)) * sizeof(double) +
-                  (size_t)umax * sizeof(int), 16);
-}
-// the blocks a launch takes: the longest list plus what sixteen consecutive points of a regular network add (one
-// observation per point at stride 1).  Fewer slots = more workgroups per compute unit; a tile that needs more is halved.
-static int stream64_blocks(int p_max) {
-  const int want = (p_max + 16 + 15) >> 4;
-  return want < kStream64MaxBlocks ? want : kStream64MaxBlocks;
-}
 
 bool stream64_route_covers(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t ng) {
   if (m < 1 || k < 2 || k > kStream64MaxK || p_max <= k || ldx < 1 || ldo < 1 || ng < 0) return false;   // p_max <= k: the dual routes
-  if (p_max > 16 * kStream64MaxBlocks) return false;
-  if (stream64_lds_bytes(kStream64MaxBlocks, k) > kMaxDynamicLds) return false;      // (holds at every k: tests/test_stream64_cover.py)
+  if (p_max > 16 * kRing64MaxBlocks) return false;
+  if (ring64_lds_bytes(kRing64MaxBlocks, k) > kMaxDynamicLds) return false;      // (holds at every k: tests/test_stream64_cover.py)
   // the state and the output are addressed as wave-uniform base + 32-bit byte offset of a column of one state row block
   if ((int64_t)k * ldx * 8 >= ((int64_t)1 << 31) || (int64_t)k * ldo * 8 >= ((int64_t)1 << 31)) return false;
-  return ((ng + 15) >> 4) <= (int64_t)65536 * 65535;
+  return grid_covers((ng + 15) >> 4);
 }
 
+// launches with the sizes of the ring frame (mia_frames64.h)
 template <int KT>
 static int stream64_launch_t(const Stream64Params& dp, hipStream_t stream) {
-  const size_t lds = stream64_lds_bytes(dp.ub, dp.k);
-  if (lds > kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
-  auto kern = letkf_stream64_kernel<KT>;
-  if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t ntile = (dp.ng + 15) >> 4;
-  const int64_t gx = ntile < 65536 ? ntile : 65536;
-  const int64_t gy = (ntile + gx - 1) / gx;
-  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
-  kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(64), lds, stream>>>(dp);
-  note_analysis_kernel("letkf_stream64_kernel<%d>", KT);
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
+  return launch_blocks(letkf_stream64_kernel<KT>, (dp.ng + 15) >> 4, 64, ring64_lds_bytes(dp.ub, dp.k), stream,
+                       [] { note_analysis_kernel("letkf_stream64_kernel<%d>", KT); }, dp);
 }
 
 int stream64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t ng, const double* rec,
@@ -553,7 +532,7 @@ int stream64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t
   dp.X = X; dp.ldx = ldx; dp.m = m; dp.k = k; dp.kp = (k + 1 + 3) & ~3;
   dp.g0 = g0; dp.ng = ng; dp.rec = rec;
   dp.cnt = nbr_cnt; dp.idx = nbr_idx; dp.w = nbr_w; dp.p_cap = p_cap; dp.p_max = p_max;
-  dp.ub = stream64_blocks(p_max);
+  dp.ub = ring64_blocks(p_max);
   const double rg = (double)(k - 1) / inf_factor, km = (double)(k - 1);
   dp.reg = rg;
   dp.inv_reg = 1.0 / rg;
@@ -563,17 +542,7 @@ int stream64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t
   dp.Xa = Xa; dp.ldo = ldo; dp.o0 = o0; dp.flags = flags; dp.retry_count = retry_count;
   dp.dmax = kTab64Deg - 1;
   dp.tab_hdr = tab->hdr; dp.tab_c = tab->c;
-  switch ((k + 15) >> 4) {
-    case 1: return stream64_launch_t<1>(dp, stream);
-    case 2: return stream64_launch_t<2>(dp, stream);
-    case 3: return stream64_launch_t<3>(dp, stream);
-    case 4: return stream64_launch_t<4>(dp, stream);
-    case 5: return stream64_launch_t<5>(dp, stream);
-    case 6: return stream64_launch_t<6>(dp, stream);
-    case 7: return stream64_launch_t<7>(dp, stream);
-    case 8: return stream64_launch_t<8>(dp, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
+  return dispatch_upto<8>((k + 15) >> 4, [&](auto kt) { return stream64_launch_t<kt()>(dp, stream); });
 }
 
 }  // namespace mia

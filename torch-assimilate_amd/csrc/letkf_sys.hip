@@ -21,6 +21,7 @@
 #include "mia_common.h"
 #include "mia_kernels.h"
 #include "mia_options.h"
+#include "mia_tile_launch.h"
 
 namespace mia {
 
@@ -608,13 +609,10 @@ static size_t sys_lds_bytes(int k, int kp, int m, int p_max, int nmax, int rows,
 }
 
 template <int NMAX, int NT>
-static int sys_launch(const SysParams& ap, size_t lds, dim3 grid, hipStream_t stream) {
-  auto kern = letkf_sys_kernel<NMAX, NT>;
-  if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  kern<<<grid, dim3(NT), lds, stream>>>(ap);
-  if (!ap.only_flagged) note_analysis_kernel("letkf_sys_kernel<%d, %d>", NMAX, NT);      // (the redo of declined points is not a step's analysis kernel)
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
+static int sys_launch(const SysParams& ap, size_t lds, hipStream_t stream) {
+  return launch_blocks(letkf_sys_kernel<NMAX, NT>, ap.ng, NT, lds, stream, [&] {
+    if (!ap.only_flagged) note_analysis_kernel("letkf_sys_kernel<%d, %d>", NMAX, NT);      // (the redo of declined points is not a step's analysis kernel)
+  }, ap);
 }
 
 // returns MIA_ERR_UNSUPPORTED when no bucket fits (caller falls back to the runtime-order kernel)
@@ -658,23 +656,8 @@ int sys_analysis_launch(const float* X, int64_t ldx, int m, int k, int64_t g0, i
   // one grid point per workgroup (measured on MI355X, C2: 1-2 points per workgroup beat 4-10 by 5-12 %:
   // the dispatcher's dynamic placement balances the data-dependent sweep counts)
   ap.pts_per_block = 1;
-  const int64_t gx = ng < 65536 ? ng : 65536;
-  const int64_t gy = (ng + gx - 1) / gx;
-  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
-  const dim3 grid((unsigned)gx, (unsigned)gy);
-  switch (nmax) {
-    case 4: return sys_launch<4, 64>(ap, lds, grid, stream);
-    case 8: return sys_launch<8, 64>(ap, lds, grid, stream);
-    case 12: return sys_launch<12, 64>(ap, lds, grid, stream);
-    case 16: return sys_launch<16, 64>(ap, lds, grid, stream);
-    case 20: return sys_launch<20, 64>(ap, lds, grid, stream);
-    case 24: return sys_launch<24, 64>(ap, lds, grid, stream);
-    case 32: return sys_launch<32, 64>(ap, lds, grid, stream);
-    case 40: return sys_launch<40, 256>(ap, lds, grid, stream);
-    case 48: return sys_launch<48, 256>(ap, lds, grid, stream);
-    case 64: return sys_launch<64, 256>(ap, lds, grid, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
+  // the buckets above; one wavefront up to order 32, four beyond
+  return dispatch_among<64, 48, 40, 32, 24, 20, 16, 12, 8, 4>(nmax, [&](auto n) { return sys_launch<n(), (n() > 32 ? 256 : 64)>(ap, lds, stream); });
 }
 
 }  // namespace mia

@@ -39,6 +39,7 @@
 #include <hip/hip_ext.h>
 #include "mia_kernels.h"
 #include "mia_options.h"
+#include "mia_tile_launch.h"
 
 namespace mia {
 
@@ -1059,28 +1060,12 @@ static size_t tile_lds_bytes(int ut, int kp, int rsb) {
 template <int UT, int KT, bool SEG, bool SPL>
 static int tile_launch_s(const TileParams& tp, hipStream_t stream) {
   const size_t lds = tile_lds_bytes(UT, tp.kp, SPL ? tp.rsb : 0);
-  if (lds > kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
   TileParams tpl = tp;
   tpl.lds_bytes = (int)lds;
-  auto kern = letkf_tile_kernel<UT, KT, SEG, SPL>;
-  if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   const int64_t ntile = SEG ? (((int64_t)tp.seg_len + 15) >> 4) * ((tp.ng + tp.seg_len - 1) / tp.seg_len) : (tp.ng + 15) >> 4;
-  const int64_t gx = ntile < 65536 ? ntile : 65536;
-  const int64_t gy = (ntile + gx - 1) / gx;
-  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
-  hipEvent_t& stop = launch_stop_event();
-  if (stop) {
-    hipExtLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)gy), dim3(64), (unsigned)lds, stream, launch_start_event(), stop, 0,
-                          tpl);
-    stop = nullptr;        // taken
-    launch_start_event() = nullptr;
-  } else {
-    kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(64), lds, stream>>>(tpl);
-  }
-  ++tile_launch_count();
-  note_analysis_kernel("letkf_tile_kernel<%d, %d, %s, %s>", UT, KT, SEG ? "true" : "false", SPL ? "true" : "false");
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
+  return launch_blocks_carried(letkf_tile_kernel<UT, KT, SEG, SPL>, ntile, 64, lds, stream, [] {
+    note_analysis_kernel("letkf_tile_kernel<%d, %d, %s, %s>", UT, KT, SEG ? "true" : "false", SPL ? "true" : "false");
+  }, tpl);
 }
 
 // Instantiations: UT <= KT + 1 (the dual route has p <= k, so a union of p + slack slots never needs more row blocks than
@@ -1096,19 +1081,6 @@ static int tile_launch_t(const TileParams& tp, hipStream_t stream) {
   } else {
     return MIA_ERR_UNSUPPORTED;
   }
-}
-
-template <int UT, bool SPL>
-static int tile_launch_u(const TileParams& tp, int kt, hipStream_t stream) {
-  switch (kt) {
-    case 1: return tile_launch_t<UT, 1, SPL>(tp, stream);
-    case 2: return tile_launch_t<UT, 2, SPL>(tp, stream);
-    case 3: return tile_launch_t<UT, 3, SPL>(tp, stream);
-    case 4: return tile_launch_t<UT, 4, SPL>(tp, stream);
-    case 5: return tile_launch_t<UT, 5, SPL>(tp, stream);
-    case 6: return tile_launch_t<UT, 6, SPL>(tp, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
 }
 
 // Slots an instantiation offers a tile beyond the longest single list.  Sixteen consecutive points of a regular
@@ -1133,7 +1105,7 @@ static bool tile_launch_args_ok(int m, int k, int p_max, int p_cap, int64_t ldx,
   const int kp = (k + 1 + 3) & ~3, rsb = 32 * ((k + 1 + 7) >> 3) + 16;
   if (tile_lds_bytes(ut, kp, spl ? rsb : 0) > kMaxDynamicLds) return false;
   const int64_t ntile = seg_len > 0 ? (((int64_t)seg_len + 15) >> 4) * ((ng + seg_len - 1) / seg_len) : (ng + 15) >> 4;
-  return ntile <= (int64_t)65536 * 65535;
+  return grid_covers(ntile);
 }
 
 template <bool SPL>
@@ -1165,15 +1137,9 @@ static int tile_launch_impl(const float* X, int64_t ldx, int m, int k, int64_t g
   tp.rsb = 32 * tp.nc + 16;
   const int kt = (k + 15) >> 4;
   const int ut = (p_max + kTileSlack + 15) >> 4;
-  switch (ut < 1 ? 1 : ut) {
-    case 1: return tile_launch_u<1, SPL>(tp, kt, stream);
-    case 2: return tile_launch_u<2, SPL>(tp, kt, stream);
-    case 3: return tile_launch_u<3, SPL>(tp, kt, stream);
-    case 4: return tile_launch_u<4, SPL>(tp, kt, stream);
-    case 5: return tile_launch_u<5, SPL>(tp, kt, stream);
-    case 6: return tile_launch_u<6, SPL>(tp, kt, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
+  return dispatch_upto<6>(ut < 1 ? 1 : ut, [&](auto ut_c) {
+    return dispatch_upto<6>(kt, [&](auto kt_c) { return tile_launch_t<ut_c(), kt_c(), SPL>(tp, stream); });
+  });
 }
 
 #ifdef MIA_TILE_TU_SPLIT

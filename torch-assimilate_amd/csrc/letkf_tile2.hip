@@ -31,6 +31,7 @@
 #include "mia_kernels.h"
 #include "mia_options.h"
 #include "mia_tiles.h"
+#include "mia_tile_launch.h"
 #include "letkf_tile2_kernel.h"
 
 namespace mia {
@@ -63,25 +64,9 @@ static int tile2_launch_m(const Tile2Params& tp, hipStream_t stream) {
     MIA_EXP_SET(per_cu, "MIA_TILE2_WAVES_PER_CU", atoi);
     if (per_cu > 0 && (size_t)(160 * 1024) / per_cu > lds) lds = ((size_t)(160 * 1024) / per_cu) & ~(size_t)255;
   }
-  if (lds > kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
-  auto kern = letkf_tile2_kernel<UT, KT, MROWS, WAVES>;
-  if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t ntile = (tp.ng + 15) >> 4;
-  const int64_t gx = ntile < 65536 ? ntile : 65536;
-  const int64_t gy = (ntile + gx - 1) / gx;
-  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
-  hipEvent_t& stop = launch_stop_event();
-  if (stop) {
-    hipExtLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)gy), dim3(64), (unsigned)lds, stream, launch_start_event(), stop, 0, tp);
-    stop = nullptr;        // taken
-    launch_start_event() = nullptr;
-  } else {
-    kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(64), lds, stream>>>(tp);
-  }
-  ++tile_launch_count();
-  note_analysis_kernel("letkf_tile2_kernel<%d, %d, %s, %d>", UT, KT, MROWS ? "true" : "false", WAVES);
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
+  return launch_blocks_carried(letkf_tile2_kernel<UT, KT, MROWS, WAVES>, (tp.ng + 15) >> 4, 64, lds, stream, [] {
+    note_analysis_kernel("letkf_tile2_kernel<%d, %d, %s, %d>", UT, KT, MROWS ? "true" : "false", WAVES);
+  }, tp);
 }
 
 template <int UT, int KT>
@@ -100,17 +85,13 @@ static int tile2_launch_s(const Tile2Params& tp, hipStream_t stream) {
   return tp.m == 1 && !force_rows ? tile2_launch_m<UT, KT, false>(tp, stream) : tile2_launch_m<UT, KT, true>(tp, stream);
 }
 
+// (UT <= KT + 1, as the dual route bounds it, up to four member blocks; every UT from five on)
 template <int UT>
 static int tile2_launch_u(const Tile2Params& tp, int kt, hipStream_t stream) {
-  switch (kt) {
-    case 1: if constexpr (UT <= 2) return tile2_launch_s<UT, 1>(tp, stream); else break;
-    case 2: if constexpr (UT <= 3) return tile2_launch_s<UT, 2>(tp, stream); else break;
-    case 3: if constexpr (UT <= 4) return tile2_launch_s<UT, 3>(tp, stream); else break;
-    case 4: if constexpr (UT <= 5) return tile2_launch_s<UT, 4>(tp, stream); else break;
-    case 5: return tile2_launch_s<UT, 5>(tp, stream);
-    case 6: return tile2_launch_s<UT, 6>(tp, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
+  return dispatch_upto<6>(kt, [&](auto kt_c) {
+    if constexpr (kt_c() >= 5 || UT <= kt_c() + 1) return tile2_launch_s<UT, kt_c()>(tp, stream);
+    else return MIA_ERR_UNSUPPORTED;
+  });
 }
 
 // dual route (p_max <= k), k <= 96, union of at most 96 slots (16 per row block: tile_ut_for(p_max) + extra_blocks of them, at most
@@ -121,7 +102,7 @@ bool tile2_covers(int m, int k, int p_max, int extra_blocks, int64_t ldx, int64_
   const int kt = (k + 15) >> 4, ut = tile_ut_for(p_max) + extra_blocks;
   if (ut > kt + 1 || ut > 6) return false;
   if (tile2_lds_bytes(ut, k) > kMaxDynamicLds) return false;
-  return ((ng + 15) >> 4) <= (int64_t)65536 * 65535;
+  return grid_covers((ng + 15) >> 4);
 }
 
 // the kernels address a record as base + 32-bit byte offset: (P + 1) records must fit 4 GB (2.4e7 observations at k = 40)
@@ -167,15 +148,7 @@ int tile2_analysis_launch(const float* X, int64_t ldx, int m, int k, int64_t g0,
   if (ut == 2 && kt == 3) return tile2_launch_s<2, 3>(tp, stream);
   return MIA_ERR_UNSUPPORTED;
 #else
-  switch (ut) {
-    case 1: return tile2_launch_u<1>(tp, kt, stream);
-    case 2: return tile2_launch_u<2>(tp, kt, stream);
-    case 3: return tile2_launch_u<3>(tp, kt, stream);
-    case 4: return tile2_launch_u<4>(tp, kt, stream);
-    case 5: return tile2_launch_u<5>(tp, kt, stream);
-    case 6: return tile2_launch_u<6>(tp, kt, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
+  return dispatch_upto<6>(ut, [&](auto ut_c) { return tile2_launch_u<ut_c()>(tp, kt, stream); });
 #endif
 }
 

@@ -12,6 +12,7 @@
 #include "mia_kernels.h"
 #include "mia_options.h"
 #include "mia_tiles.h"
+#include "mia_tile_launch.h"
 #include "letkf_tile2_kernel.h"
 
 namespace mia {
@@ -38,25 +39,10 @@ template <int UT, int KT, int NC, bool MROWS>
 static int tile2f_launch_m(const Tile2FParams& pf, hipStream_t stream) {
   const size_t a = tile2_lds_bytes(UT, pf.t.k), b = tile_loc_lds(UT);
   const size_t lds = a > b ? a : b;
-  if (lds > kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
-  auto kern = letkf_tile2f_kernel<UT, KT, NC, MROWS, MROWS ? 2 : MIA_TILE2_WAVES_UT2>;
-  if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t ntile = (pf.t.ng + 15) >> 4;
-  const int64_t gx = ntile < 65536 ? ntile : 65536;
-  const int64_t gy = (ntile + gx - 1) / gx;
-  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
-  hipEvent_t& stop = launch_stop_event();
-  if (stop) {
-    hipExtLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)gy), dim3(64), (unsigned)lds, stream, launch_start_event(), stop, 0, pf);
-    stop = nullptr;        // taken
-    launch_start_event() = nullptr;
-  } else {
-    kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(64), lds, stream>>>(pf);
-  }
-  ++tile_launch_count();
-  note_analysis_kernel("letkf_tile2f_kernel<%d, %d, %d, %s, %d>", UT, KT, NC, MROWS ? "true" : "false", MROWS ? 2 : MIA_TILE2_WAVES_UT2);
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
+  constexpr int WAVES = MROWS ? 2 : MIA_TILE2_WAVES_UT2;
+  return launch_blocks_carried(letkf_tile2f_kernel<UT, KT, NC, MROWS, WAVES>, (pf.t.ng + 15) >> 4, 64, lds, stream, [] {
+    note_analysis_kernel("letkf_tile2f_kernel<%d, %d, %d, %s, %d>", UT, KT, NC, MROWS ? "true" : "false", WAVES);
+  }, pf);
 }
 
 template <int UT, int KT, int NC>
@@ -64,30 +50,12 @@ static int tile2f_launch_n(const Tile2FParams& pf, hipStream_t stream) {        
   return pf.t.m == 1 ? tile2f_launch_m<UT, KT, NC, false>(pf, stream) : tile2f_launch_m<UT, KT, NC, true>(pf, stream);
 }
 
-template <int UT, int KT>
-static int tile2f_launch_k(const Tile2FParams& pf, hipStream_t stream) {
-  switch (pf.loc.scan.nc + (pf.loc.periodic ? 4 : 0)) {
-    case 1: return tile2f_launch_n<UT, KT, 1>(pf, stream);
-    case 2: return tile2f_launch_n<UT, KT, 2>(pf, stream);
-    case 3: return tile2f_launch_n<UT, KT, 3>(pf, stream);
-    case 5: return tile2f_launch_n<UT, KT, 5>(pf, stream);
-    case 6: return tile2f_launch_n<UT, KT, 6>(pf, stream);
-    case 7: return tile2f_launch_n<UT, KT, 7>(pf, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
-}
-
+// NC: the coordinates of the cell scan, + 4 on cyclic coordinates
 template <int UT>
 static int tile2f_launch_u(const Tile2FParams& pf, int kt, hipStream_t stream) {
-  switch (kt) {
-    case 1: return tile2f_launch_k<UT, 1>(pf, stream);
-    case 2: return tile2f_launch_k<UT, 2>(pf, stream);
-    case 3: return tile2f_launch_k<UT, 3>(pf, stream);
-    case 4: return tile2f_launch_k<UT, 4>(pf, stream);
-    case 5: return tile2f_launch_k<UT, 5>(pf, stream);
-    case 6: return tile2f_launch_k<UT, 6>(pf, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
+  return dispatch_upto<6>(kt, [&](auto kt_c) {
+    return dispatch_among<7, 6, 5, 3, 2, 1>(pf.loc.scan.nc + (pf.loc.periodic ? 4 : 0), [&](auto nc) { return tile2f_launch_n<UT, kt_c(), nc()>(pf, stream); });
+  });
 }
 
 int tile2f_launch(const Tile2Params& tp, const Tile2Loc& loc, int ut, int kt, hipStream_t stream) {

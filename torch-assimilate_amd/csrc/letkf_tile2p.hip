@@ -22,6 +22,7 @@
 #include "mia_kernels.h"
 #include "mia_options.h"
 #include "mia_tiles.h"
+#include "mia_tile_launch.h"
 #include <cstdio>
 #include <type_traits>
 #include <cstdlib>
@@ -602,13 +603,7 @@ static size_t tile2p_lds_bytes(int ut, int k, int nw) {
 template <int UT, int KT, bool MROWS, int NW>
 static int tile2p_launch_m(const Tile2Params& tp, hipStream_t stream) {
   const size_t lds = tile2p_lds_bytes(UT, tp.k, NW);
-  if (lds > kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
   auto kern = letkf_tile2p_kernel<UT, KT, MROWS, NW>;
-  if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t ntile = (tp.ng + 15) >> 4;
-  const int64_t gx = ntile < 65536 ? ntile : 65536;
-  const int64_t gy = (ntile + gx - 1) / gx;
-  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
 #ifdef MIA_EXPERIMENTS
   if (MIA_EXP_FLAG("MIA_T2P_OCC")) {
     int nb = 0;
@@ -616,18 +611,8 @@ static int tile2p_launch_m(const Tile2Params& tp, hipStream_t stream) {
     fprintf(stderr, "letkf_tile2p_kernel<%d,%d,%d,%d>: %d workgroups per CU at %zu bytes of LDS\n", UT, KT, (int)MROWS, NW, nb, lds);
   }
 #endif
-  hipEvent_t& stop = launch_stop_event();
-  if (stop) {
-    hipExtLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)gy), dim3(64 * NW), (unsigned)lds, stream, launch_start_event(), stop, 0, tp);
-    stop = nullptr;
-    launch_start_event() = nullptr;
-  } else {
-    kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(64 * NW), lds, stream>>>(tp);
-  }
-  ++tile_launch_count();
-  note_analysis_kernel("letkf_tile2p_kernel<%d, %d, %s, %d>", UT, KT, MROWS ? "true" : "false", NW);
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
+  return launch_blocks_carried(kern, (tp.ng + 15) >> 4, 64 * NW, lds, stream,
+                               [] { note_analysis_kernel("letkf_tile2p_kernel<%d, %d, %s, %d>", UT, KT, MROWS ? "true" : "false", NW); }, tp);
 }
 
 // one state row per grid point only: with more rows the loop's carried values cost the second wave per SIMD and the kernel loses

@@ -26,6 +26,7 @@
 #include "mia_kernels.h"
 #include "mia_options.h"
 #include "mia_tiles.h"
+#include "mia_tile_launch.h"
 #include <type_traits>
 
 namespace mia {
@@ -608,30 +609,13 @@ static size_t tile2w_lds_bytes(int ut, int kt, int k) {
 
 template <int UT, int KT>
 static int tile2w_launch(const Tile2wParams& tp, hipStream_t stream) {
-  const size_t lds = tile2w_lds_bytes(UT, KT, tp.k);
-  if (lds > kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
   auto kern = (tp.k & 3) == 0 ? letkf_tile2w_kernel<UT, KT, true> : letkf_tile2w_kernel<UT, KT, false>;
-  if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t nwork = (tp.ng + 15) >> 4;
-  const int64_t gx = nwork < 65536 ? nwork : 65536;
-  const int64_t gy = (nwork + gx - 1) / gx;
-  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
-  kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(64 * (16 / kWPts)), lds, stream>>>(tp);
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
+  return launch_blocks(kern, (tp.ng + 15) >> 4, 64 * (16 / kWPts), tile2w_lds_bytes(UT, KT, tp.k), stream, no_note, tp);
 }
 
 template <int UT>
 static int tile2w_launch_u(const Tile2wParams& tp, int kt, hipStream_t stream) {
-  switch (kt) {
-    case 1: return tile2w_launch<UT, 1>(tp, stream);
-    case 2: return tile2w_launch<UT, 2>(tp, stream);
-    case 3: return tile2w_launch<UT, 3>(tp, stream);
-    case 4: return tile2w_launch<UT, 4>(tp, stream);
-    case 5: return tile2w_launch<UT, 5>(tp, stream);
-    case 6: return tile2w_launch<UT, 6>(tp, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
+  return dispatch_upto<6>(kt, [&](auto kt_c) { return tile2w_launch<UT, kt_c()>(tp, stream); });
 }
 
 // dual route with a union of at most 32 slots (UT <= 2), k <= 96, W addressed with 32-bit element offsets inside a point

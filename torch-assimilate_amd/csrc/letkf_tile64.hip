@@ -34,6 +34,8 @@
 // so that the damage stays with the points that use the observation.  Points whose degree exceeds the table's cap are
 // DECLINED (MIA_FLAG_RETRY, counted, Xa untouched) and redone by letkf_wave_kernel<double>.
 #include "mia_cheb_table64.h"
+#include "mia_frames64.h"
+#include "mia_tile_launch.h"
 
 namespace mia {
 
@@ -410,51 +412,19 @@ __global__ __launch_bounds__(64, (UT <= 2 ? 2 : 1)) void letkf_tile64_kernel(Til
   }
 }
 
-static size_t tile64_lds_bytes(int ut, int kp) {
-  const int umax = 16 * ut;
-  return align_up(((size_t)umax * (kp | 1) + 16 * (size_t)(umax + 1)) * sizeof(double) + (size_t)umax * sizeof(int), 16);
-}
-
+// launches with the sizes of the resident image (mia_frames64.h): UT blocks of records of kp doubles
 template <int UT, int KT>
 static int tile64_launch_t(const Tile64Params& tp, hipStream_t stream) {
-  const size_t lds = tile64_lds_bytes(UT, tp.kp);
-  if (lds > kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
-  auto kern = letkf_tile64_kernel<UT, KT>;
-  if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t ntile = (tp.ng + 15) >> 4;
-  const int64_t gx = ntile < 65536 ? ntile : 65536;
-  const int64_t gy = (ntile + gx - 1) / gx;
-  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
-  kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(64), lds, stream>>>(tp);
-  note_analysis_kernel("letkf_tile64_kernel<%d, %d>", UT, KT);
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
-}
-
-template <int UT>
-static int tile64_launch_u(const Tile64Params& tp, int kt, hipStream_t stream) {
-  switch (kt) {
-    case 1: return tile64_launch_t<UT, 1>(tp, stream);
-    case 2: return tile64_launch_t<UT, 2>(tp, stream);
-    case 3: return tile64_launch_t<UT, 3>(tp, stream);
-    case 4: return tile64_launch_t<UT, 4>(tp, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
-}
-
-// Slots an instantiation offers a tile beyond the longest single list (as letkf_tile.hip: sixteen consecutive points of a
-// regular network add ~one observation per second point), up to the four blocks the kernel is built for.
-static int tile64_ut(int p_max) {
-  const int ut = (p_max + 8 + 15) >> 4;
-  return ut < 1 ? 1 : (ut > 4 ? 4 : ut);
+  return launch_blocks(letkf_tile64_kernel<UT, KT>, (tp.ng + 15) >> 4, 64, resident64_lds_bytes(UT, tp.kp), stream,
+                       [] { note_analysis_kernel("letkf_tile64_kernel<%d, %d>", UT, KT); }, tp);
 }
 
 bool tile64_route_covers(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t ng) {
   if (m < 1 || k < 2 || k > 64 || p_max < 0 || p_max > k || ldx < 1 || ldo < 1 || ng < 0) return false;
   // the state and the output are addressed as wave-uniform base + 32-bit byte offset of a column of one state row block
   if ((int64_t)k * ldx * 8 >= ((int64_t)1 << 31) || (int64_t)k * ldo * 8 >= ((int64_t)1 << 31)) return false;
-  if (tile64_lds_bytes(tile64_ut(p_max), (k + 1 + 3) & ~3) > kMaxDynamicLds) return false;
-  return ((ng + 15) >> 4) <= (int64_t)65536 * 65535;
+  if (resident64_lds_bytes(resident64_ut(p_max), (k + 1 + 3) & ~3) > kMaxDynamicLds) return false;
+  return grid_covers((ng + 15) >> 4);
 }
 
 int tile64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t ng, const double* rec,
@@ -480,13 +450,9 @@ int tile64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g
   tp.dmax = kTab64Deg - 1;
   tp.tab_hdr = tab->hdr; tp.tab_c = tab->c;
   const int kt = (k + 15) >> 4;
-  switch (tile64_ut(p_max)) {
-    case 1: return tile64_launch_u<1>(tp, kt, stream);
-    case 2: return tile64_launch_u<2>(tp, kt, stream);
-    case 3: return tile64_launch_u<3>(tp, kt, stream);
-    case 4: return tile64_launch_u<4>(tp, kt, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
+  return dispatch_upto<4>(resident64_ut(p_max), [&](auto ut) {
+    return dispatch_upto<4>(kt, [&](auto kt_c) { return tile64_launch_t<ut(), kt_c()>(tp, stream); });
+  });
 }
 
 }  // namespace mia

@@ -26,6 +26,8 @@
 // MIA_FLAG_NONFINITE stays with the points that use the record.  A point without observations gets sqrt(inf) I exactly
 // (D = 0 keeps every product out; etkf.py:91-95).
 #include "mia_cheb_table64.h"
+#include "mia_frames64.h"
+#include "mia_tile_launch.h"
 
 namespace mia {
 
@@ -349,48 +351,17 @@ __global__ __launch_bounds__(64, (UT <= 2 ? 2 : 1)) void letkf_weights64_kernel(
   }
 }
 
-static size_t tile64w_lds_bytes(int ut, int kp) {
-  const int umax = 16 * ut;
-  return align_up(((size_t)umax * (kp | 1) + 16 * (size_t)(umax + 1)) * sizeof(double) + (size_t)umax * sizeof(int), 16);
-}
-
+// launches with the sizes of the resident image (mia_frames64.h): UT blocks of records of kp doubles
 template <int UT, int KT>
 static int tile64w_launch_t(const Tile64WParams& tp, hipStream_t stream) {
-  const size_t lds = tile64w_lds_bytes(UT, tp.kp);
-  if (lds > kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
-  auto kern = letkf_weights64_kernel<UT, KT>;
-  if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t ntile = (tp.ng + 15) >> 4;
-  const int64_t gx = ntile < 65536 ? ntile : 65536;
-  const int64_t gy = (ntile + gx - 1) / gx;
-  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
-  kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(64), lds, stream>>>(tp);
-  note_analysis_kernel("letkf_weights64_kernel<%d, %d>", UT, KT);
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
-}
-
-template <int UT>
-static int tile64w_launch_u(const Tile64WParams& tp, int kt, hipStream_t stream) {
-  switch (kt) {
-    case 1: return tile64w_launch_t<UT, 1>(tp, stream);
-    case 2: return tile64w_launch_t<UT, 2>(tp, stream);
-    case 3: return tile64w_launch_t<UT, 3>(tp, stream);
-    case 4: return tile64w_launch_t<UT, 4>(tp, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
-}
-
-// slots of an instantiation: the analysis kernel's rule (letkf_tile64.hip, tile64_ut)
-static int tile64w_ut(int p_max) {
-  const int ut = (p_max + 8 + 15) >> 4;
-  return ut < 1 ? 1 : (ut > 4 ? 4 : ut);
+  return launch_blocks(letkf_weights64_kernel<UT, KT>, (tp.ng + 15) >> 4, 64, resident64_lds_bytes(UT, tp.kp), stream,
+                       [] { note_analysis_kernel("letkf_weights64_kernel<%d, %d>", UT, KT); }, tp);
 }
 
 bool weights64_route_covers(int k, int p_max, int64_t ng) {
   if (k < 2 || k > 64 || p_max < 0 || p_max > k || ng < 0) return false;
-  if (tile64w_lds_bytes(tile64w_ut(p_max), (k + 1 + 3) & ~3) > kMaxDynamicLds) return false;
-  return ((ng + 15) >> 4) <= (int64_t)65536 * 65535;
+  if (resident64_lds_bytes(resident64_ut(p_max), (k + 1 + 3) & ~3) > kMaxDynamicLds) return false;
+  return grid_covers((ng + 15) >> 4);
 }
 
 int weights64_launch(int k, int64_t ng, const double* rec, const int32_t* nbr_cnt, const int32_t* nbr_idx,
@@ -414,13 +385,9 @@ int weights64_launch(int k, int64_t ng, const double* rec, const int32_t* nbr_cn
   tp.dmax = kTab64Deg - 1;
   tp.tab_hdr = tab->hdr; tp.tab_c = tab->c;
   const int kt = (k + 15) >> 4;
-  switch (tile64w_ut(p_max)) {
-    case 1: return tile64w_launch_u<1>(tp, kt, stream);
-    case 2: return tile64w_launch_u<2>(tp, kt, stream);
-    case 3: return tile64w_launch_u<3>(tp, kt, stream);
-    case 4: return tile64w_launch_u<4>(tp, kt, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
+  return dispatch_upto<4>(resident64_ut(p_max), [&](auto ut) {
+    return dispatch_upto<4>(kt, [&](auto kt_c) { return tile64w_launch_t<ut(), kt_c()>(tp, stream); });
+  });
 }
 
 }  // namespace mia

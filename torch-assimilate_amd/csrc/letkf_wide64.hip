@@ -33,6 +33,8 @@
 // barrier is reached by all waves: the union loop, the halves path, the point-by-point path of a tile with a non-finite record
 // and the recurrence of a tile whose columns are all declined run the same trips in every wave.
 #include "mia_cheb_table64.h"
+#include "mia_frames64.h"
+#include "mia_tile_launch.h"
 
 namespace mia {
 
@@ -480,53 +482,14 @@ __global__ __launch_bounds__(64 * NW, 1) void letkf_wide64_kernel(Wide64Params P
   }
 }
 
-// UT = ceil((p_max + 8) / 16) as letkf_tile64.hip, up to eight blocks
-static int wide64_ut(int p_max) {
-  const int ut = (p_max + 8 + 15) >> 4;
-  return ut < 1 ? 1 : (ut > 8 ? 8 : ut);
-}
-// two wavefronts hold up to six row blocks (three each: 8 * 6 * 3 = 144 registers of Gram matrix), four the rest
-static int wide64_nw(int ut) { return ut <= 6 ? 2 : 4; }
-
-static size_t wide64_lds_bytes(int ut, int kt, int nw) {
-  const int umax = 16 * ut;
-  return align_up(((size_t)umax * (16 * kt + 5) + 16 * (size_t)(umax + 1) + 16 * (size_t)nw) * sizeof(double) +
-                  (size_t)(umax + nw) * sizeof(int), 16);
-}
-
+// launches with the sizes of the wide frame (mia_frames64.h): UT blocks shared by NW wavefronts
 template <int UT, int KT, int NW>
 static int wide64_launch_t(const Wide64Params& tp, hipStream_t stream) {
   // p_max <= k bounds UT = ceil((p_max + 8) / 16) by KT + 1: the other pairs are never asked for and not built
   if constexpr (UT > KT + 1) return MIA_ERR_UNSUPPORTED;
-  else {
-  const size_t lds = wide64_lds_bytes(UT, KT, NW);
-  if (lds > kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
-  auto kern = letkf_wide64_kernel<UT, KT, NW>;
-  if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t ntile = (tp.ng + 15) >> 4;
-  const int64_t gx = ntile < 65536 ? ntile : 65536;
-  const int64_t gy = (ntile + gx - 1) / gx;
-  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
-  kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(64 * NW), lds, stream>>>(tp);
-  note_analysis_kernel("letkf_wide64_kernel<%d, %d, %d>", UT, KT, NW);
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
-  }
-}
-
-template <int UT, int NW>
-static int wide64_launch_u(const Wide64Params& tp, int kt, hipStream_t stream) {
-  switch (kt) {
-    case 1: return wide64_launch_t<UT, 1, NW>(tp, stream);
-    case 2: return wide64_launch_t<UT, 2, NW>(tp, stream);
-    case 3: return wide64_launch_t<UT, 3, NW>(tp, stream);
-    case 4: return wide64_launch_t<UT, 4, NW>(tp, stream);
-    case 5: return wide64_launch_t<UT, 5, NW>(tp, stream);
-    case 6: return wide64_launch_t<UT, 6, NW>(tp, stream);
-    case 7: return wide64_launch_t<UT, 7, NW>(tp, stream);
-    case 8: return wide64_launch_t<UT, 8, NW>(tp, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
+  else
+    return launch_blocks(letkf_wide64_kernel<UT, KT, NW>, (tp.ng + 15) >> 4, 64 * NW, wide64_lds_bytes(UT, KT, NW), stream,
+                         [] { note_analysis_kernel("letkf_wide64_kernel<%d, %d, %d>", UT, KT, NW); }, tp);
 }
 
 bool wide64_route_covers(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t ng) {
@@ -535,7 +498,7 @@ bool wide64_route_covers(int m, int k, int p_max, int64_t ldx, int64_t ldo, int6
   if ((int64_t)k * ldx * 8 >= ((int64_t)1 << 31) || (int64_t)k * ldo * 8 >= ((int64_t)1 << 31)) return false;
   const int ut = wide64_ut(p_max);
   if (wide64_lds_bytes(ut, (k + 15) >> 4, wide64_nw(ut)) > kMaxDynamicLds) return false;
-  return ((ng + 15) >> 4) <= (int64_t)65536 * 65535;
+  return grid_covers((ng + 15) >> 4);
 }
 
 int wide64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t ng, const double* rec,
@@ -561,17 +524,9 @@ int wide64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g
   tp.dmax = kTab64Deg - 1;
   tp.tab_hdr = tab->hdr; tp.tab_c = tab->c;
   const int kt = (k + 15) >> 4;
-  switch (wide64_ut(p_max)) {
-    case 1: return wide64_launch_u<1, 2>(tp, kt, stream);
-    case 2: return wide64_launch_u<2, 2>(tp, kt, stream);
-    case 3: return wide64_launch_u<3, 2>(tp, kt, stream);
-    case 4: return wide64_launch_u<4, 2>(tp, kt, stream);
-    case 5: return wide64_launch_u<5, 2>(tp, kt, stream);
-    case 6: return wide64_launch_u<6, 2>(tp, kt, stream);
-    case 7: return wide64_launch_u<7, 4>(tp, kt, stream);
-    case 8: return wide64_launch_u<8, 4>(tp, kt, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
+  return dispatch_upto<8>(wide64_ut(p_max), [&](auto ut) {
+    return dispatch_upto<8>(kt, [&](auto kt_c) { return wide64_launch_t<ut(), kt_c(), wide64_nw(ut())>(tp, stream); });
+  });
 }
 
 }  // namespace mia

@@ -46,6 +46,8 @@
 // MIA_FLAG_NONFINITE stays with the points that use the record.  Every barrier is reached by all waves on every path: the
 // member loop's trip count is k, degmax is the same in every wave.
 #include "mia_cheb_table64.h"
+#include "mia_frames64.h"
+#include "mia_tile_launch.h"
 
 namespace mia {
 
@@ -585,62 +587,23 @@ __global__ __launch_bounds__(64 * NW, 1) void lienks_wide64_kernel(LienksWide64P
   }
 }
 
-// UT, NW and the LDS of an instantiation are letkf_wide64w.hip's: UT = ceil((p_max + 8) / 16) up to eight blocks; two
-// wavefronts hold up to six row blocks, four the rest
-static int lienks_wide64_ut(int p_max) {
-  const int ut = (p_max + 8 + 15) >> 4;
-  return ut < 1 ? 1 : (ut > 8 ? 8 : ut);
-}
-static int lienks_wide64_nw(int ut) { return ut <= 6 ? 2 : 4; }
-
-static size_t lienks_wide64_lds_bytes(int ut, int kt, int nw) {
-  const int umax = 16 * ut;
-  return align_up(((size_t)umax * (16 * kt + 5) + 16 * (size_t)(umax + 1) + 16 * (size_t)nw) * sizeof(double) +
-                  (size_t)(umax + nw) * sizeof(int), 16);
-}
-
+// launches with the sizes of the wide frame (mia_frames64.h): UT blocks shared by NW wavefronts
 template <int UT, int KT, int NW>
 static int lienks_wide64_launch_t(const LienksWide64Params& tp, hipStream_t stream) {
   // p_max <= k bounds UT = ceil((p_max + 8) / 16) by KT + 1: the other pairs are never asked for and not built
   if constexpr (UT > KT + 1) return MIA_ERR_UNSUPPORTED;
-  else {
-  const size_t lds = lienks_wide64_lds_bytes(UT, KT, NW);
-  if (lds > kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
-  auto kern = lienks_wide64_kernel<UT, KT, NW>;
-  if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t ntile = (tp.ng + 15) >> 4;
-  const int64_t gx = ntile < 65536 ? ntile : 65536;
-  const int64_t gy = (ntile + gx - 1) / gx;
-  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
-  kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(64 * NW), lds, stream>>>(tp);
-  note_analysis_kernel("lienks_wide64_kernel<%d, %d, %d>", UT, KT, NW);
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
-  }
-}
-
-template <int UT, int NW>
-static int lienks_wide64_launch_u(const LienksWide64Params& tp, int kt, hipStream_t stream) {
-  switch (kt) {
-    case 1: return lienks_wide64_launch_t<UT, 1, NW>(tp, stream);
-    case 2: return lienks_wide64_launch_t<UT, 2, NW>(tp, stream);
-    case 3: return lienks_wide64_launch_t<UT, 3, NW>(tp, stream);
-    case 4: return lienks_wide64_launch_t<UT, 4, NW>(tp, stream);
-    case 5: return lienks_wide64_launch_t<UT, 5, NW>(tp, stream);
-    case 6: return lienks_wide64_launch_t<UT, 6, NW>(tp, stream);
-    case 7: return lienks_wide64_launch_t<UT, 7, NW>(tp, stream);
-    case 8: return lienks_wide64_launch_t<UT, 8, NW>(tp, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
+  else
+    return launch_blocks(lienks_wide64_kernel<UT, KT, NW>, (tp.ng + 15) >> 4, 64 * NW, wide64_lds_bytes(UT, KT, NW), stream,
+                         [] { note_analysis_kernel("lienks_wide64_kernel<%d, %d, %d>", UT, KT, NW); }, tp);
 }
 
 bool lienks_wide64_route_covers(int k, int p_max, int64_t ng) {
   if (k < 2 || k > 128 || p_max < 0 || p_max > k || ng < 0) return false;
   // a pass addresses W as wave-uniform base (tile, row) + 32-bit byte offset inside the tile's sixteen matrices
   if ((int64_t)16 * k * k * 8 >= ((int64_t)1 << 31)) return false;
-  const int ut = lienks_wide64_ut(p_max);
-  if (lienks_wide64_lds_bytes(ut, (k + 15) >> 4, lienks_wide64_nw(ut)) > kMaxDynamicLds) return false;
-  return ((ng + 15) >> 4) <= (int64_t)65536 * 65535;
+  const int ut = wide64_ut(p_max);
+  if (wide64_lds_bytes(ut, (k + 15) >> 4, wide64_nw(ut)) > kMaxDynamicLds) return false;
+  return grid_covers((ng + 15) >> 4);
 }
 
 int lienks_wide64_launch(const double* W_in, int64_t w_stride, int k, int64_t ng, const double* rec, const int32_t* nbr_cnt,
@@ -669,17 +632,9 @@ int lienks_wide64_launch(const double* W_in, int64_t w_stride, int k, int64_t ng
   tp.dmax = kTab64Deg - 1;
   tp.tab_hdr = tab->hdr; tp.tab_c = tab->c;
   const int kt = (k + 15) >> 4;
-  switch (lienks_wide64_ut(p_max)) {
-    case 1: return lienks_wide64_launch_u<1, 2>(tp, kt, stream);
-    case 2: return lienks_wide64_launch_u<2, 2>(tp, kt, stream);
-    case 3: return lienks_wide64_launch_u<3, 2>(tp, kt, stream);
-    case 4: return lienks_wide64_launch_u<4, 2>(tp, kt, stream);
-    case 5: return lienks_wide64_launch_u<5, 2>(tp, kt, stream);
-    case 6: return lienks_wide64_launch_u<6, 2>(tp, kt, stream);
-    case 7: return lienks_wide64_launch_u<7, 4>(tp, kt, stream);
-    case 8: return lienks_wide64_launch_u<8, 4>(tp, kt, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
+  return dispatch_upto<8>(wide64_ut(p_max), [&](auto ut) {
+    return dispatch_upto<8>(kt, [&](auto kt_c) { return lienks_wide64_launch_t<ut(), kt_c(), wide64_nw(ut())>(tp, stream); });
+  });
 }
 
 }  // namespace mia

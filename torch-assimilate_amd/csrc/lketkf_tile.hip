@@ -37,6 +37,7 @@
 #include "mia_kernels.h"
 #include "mia_options.h"
 #include "mia_tiles.h"
+#include "mia_tile_launch.h"
 
 #ifndef LK_SPLIT8
 #define LK_SPLIT8 split8
@@ -573,24 +574,8 @@ static size_t lk_lds_bytes(int r, int ut) { return (size_t)(6 * r + 1) * (16 * u
 
 template <int R, int UT, bool PAD>
 static int lk_launch_p(const LkTileParams& tp, hipStream_t stream) {
-  const size_t lds = lk_lds_bytes(R, UT);
-  auto kern = lketkf_tile_kernel<R, UT, PAD>;
-  const int64_t ntile = (tp.ng + 15) >> 4;
-  const int64_t gx = ntile < 65536 ? ntile : 65536;
-  const int64_t gy = (ntile + gx - 1) / gx;
-  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
-  hipEvent_t& stop = launch_stop_event();
-  if (stop) {
-    hipExtLaunchKernelGGL(kern, dim3((unsigned)gx, (unsigned)gy), dim3(64), (unsigned)lds, stream, launch_start_event(), stop, 0, tp);
-    stop = nullptr;
-    launch_start_event() = nullptr;
-  } else {
-    kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(64), lds, stream>>>(tp);
-  }
-  ++tile_launch_count();
-  note_analysis_kernel("lketkf_tile_kernel<%d, %d, %s>", R, UT, PAD ? "true" : "false");
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
+  return launch_blocks_carried(lketkf_tile_kernel<R, UT, PAD>, (tp.ng + 15) >> 4, 64, lk_lds_bytes(R, UT), stream,
+                               [] { note_analysis_kernel("lketkf_tile_kernel<%d, %d, %s>", R, UT, PAD ? "true" : "false"); }, tp);
 }
 
 template <int R, int UT>
@@ -605,7 +590,7 @@ bool lketkf_tile_covers(int m, int k, int p_max, int extra_blocks, int64_t ldx, 
   if ((int64_t)k * (P > 0 ? P : 1) * 4 >= ((int64_t)1 << 31)) return false;
   const int ut = tile_ut_for(p_max) + extra_blocks;
   if (ut > 4 || ut > ((k + 15) >> 4) + 1) return false;       // (the workspace of the step driver is sized by the same rule)
-  return ((ng + 15) >> 4) <= (int64_t)65536 * 65535;
+  return grid_covers((ng + 15) >> 4);
 }
 
 int lketkf_tile_launch(const float* X, int64_t ldx, int m, int k, int64_t g0, int64_t ng, const float* Yb, const float* d,

@@ -59,6 +59,8 @@
 // (kernels.py, kernel_is_psd).
 #include "mia_cheb_table64.h"
 #include "mia_kernel_prog.h"
+#include "mia_frames64.h"
+#include "mia_tile_launch.h"
 
 namespace mia {
 
@@ -487,47 +489,18 @@ static size_t rbf64_lds_bytes(int ut, int k) {
   return align_up(((size_t)npb * 256 + rbf64_region(ut, k, kp)) * sizeof(double) + ((size_t)16 * ut + 16 * (size_t)npb + 48) * sizeof(int), 16);
 }
 
+// (a frame of its own: pair blocks and statistic region above; UT from p_max as the resident image, resident64_ut)
 template <int UT, int NR, int ST>
 static int rbf64_launch_t(const Rbf64Params& tp, hipStream_t stream) {
-  const size_t lds = rbf64_lds_bytes(UT, tp.k);
-  if (lds > kMaxDynamicLds) return MIA_ERR_UNSUPPORTED;
-  auto kern = lketkf_tile64_kernel<UT, NR, ST>;
-  if (lds > 48 * 1024) MIA_HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const int64_t ntile = (tp.ng + 15) >> 4;
-  const int64_t gx = ntile < 65536 ? ntile : 65536;
-  const int64_t gy = (ntile + gx - 1) / gx;
-  if (gy > 65535) return MIA_ERR_UNSUPPORTED;
-  kern<<<dim3((unsigned)gx, (unsigned)gy), dim3(256), lds, stream>>>(tp);
-  note_analysis_kernel("lketkf_tile64_kernel<%d, %d, %d>", UT, NR, ST);     // (ST: 0 RBF; 1 dot, 2 sq, 7 dot + sq + l1)
-  MIA_LAUNCH_CHECK();
-  return MIA_OK;
-}
-
-template <int UT, int ST>
-static int rbf64_launch_u(const Rbf64Params& tp, hipStream_t stream) {
-  switch ((tp.k + 15) >> 4) {
-    case 1: return rbf64_launch_t<UT, 1, ST>(tp, stream);
-    case 2: return rbf64_launch_t<UT, 2, ST>(tp, stream);
-    case 3: return rbf64_launch_t<UT, 3, ST>(tp, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
-}
-
-// slots an instantiation offers a tile beyond the longest single list, as letkf_tile64.hip
-static int rbf64_ut(int p_max) {
-  const int ut = (p_max + 8 + 15) >> 4;
-  return ut < 1 ? 1 : (ut > 4 ? 4 : ut);
+  return launch_blocks(lketkf_tile64_kernel<UT, NR, ST>, (tp.ng + 15) >> 4, 256, rbf64_lds_bytes(UT, tp.k), stream,
+                       [] { note_analysis_kernel("lketkf_tile64_kernel<%d, %d, %d>", UT, NR, ST); }, tp);     // (ST: 0 RBF; 1 dot, 2 sq, 7 dot + sq + l1)
 }
 
 template <int ST>
 static int rbf64_launch_s(const Rbf64Params& tp, hipStream_t stream) {
-  switch (rbf64_ut(tp.p_max)) {
-    case 1: return rbf64_launch_u<1, ST>(tp, stream);
-    case 2: return rbf64_launch_u<2, ST>(tp, stream);
-    case 3: return rbf64_launch_u<3, ST>(tp, stream);
-    case 4: return rbf64_launch_u<4, ST>(tp, stream);
-  }
-  return MIA_ERR_UNSUPPORTED;
+  return dispatch_upto<4>(resident64_ut(tp.p_max), [&](auto ut) {
+    return dispatch_upto<3>((tp.k + 15) >> 4, [&](auto nr) { return rbf64_launch_t<ut(), nr(), ST>(tp, stream); });
+  });
 }
 
 // the parameter block of both forms (ngamma and prog are the caller's)
@@ -558,8 +531,8 @@ static Rbf64Params rbf64_params(const double* X, int64_t ldx, int m, int k, int6
 // RBF kernel, float64, 2 <= k <= 40 members, lists of at most 64 observations (no p_max <= k condition: the matrix is k x k)
 bool rbf64_route_covers(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t ng) {
   if (m < 1 || k < 2 || k > kRbf64MaxK || p_max < 0 || p_max > 64 || ldx < 1 || ldo < 1 || ng < 0) return false;
-  if (rbf64_lds_bytes(rbf64_ut(p_max), k) > kMaxDynamicLds) return false;
-  return ((ng + 15) >> 4) <= (int64_t)65536 * 65535;
+  if (rbf64_lds_bytes(resident64_ut(p_max), k) > kMaxDynamicLds) return false;
+  return grid_covers((ng + 15) >> 4);
 }
 
 int rbf64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t ng, const double* rec,

@@ -112,9 +112,8 @@ int dense64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t 
 // letkf_patch64.hip: letkf_dense64.hip's analysis with a tile's sixteen points taken from a map (4 x 4 patches of a 2-D mesh)
 // and the record image sized by the caller; the cover is dense64_route_covers.  patch64_analysis_launch: MIA_ERR_UNSUPPORTED
 // outside it, with the option tile = 0, and when the coefficient table cannot be had; MIA_ERR_SIZE for union_blocks outside
-// 1 .. patch64_capacity_blocks(k).  tile_union_census_launch: validates the map and counts the largest union of a tile (ws:
+// 1 .. resident64_capacity_blocks(k) (mia_frames64.h).  tile_union_census_launch: validates the map and counts the largest union of a tile (ws:
 // ng + 2 int32, zeroed here; out2: error bits MIA_TILEMAP_*, largest union).
-int patch64_capacity_blocks(int k);
 int patch64_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t ng, const double* rec,
                             const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
                             double inf_factor, double* Xa, int64_t ldo, int64_t o0, int32_t* flags, int32_t* retry_count,
