@@ -35,7 +35,7 @@ def engine_cls():
 
 
 def lds_bytes(k, p_max):
-    """letkf_stream64w.hip's formula to the byte: ring [2][16][kp | 1], rhs [4 KT][64], sqrt(rho) [16][16 ub + 1] doubles and
+    """ring64_lds_bytes and ring64_blocks (csrc/mia_frames64.h) to the byte: ring [2][16][kp | 1], rhs [4 KT][64], sqrt(rho) [16][16 ub + 1] doubles and
     the slot table [16 ub] ints; w_mean and the shift live in registers"""
     ub = min((p_max + 16 + 15) >> 4, 16)
     kp, kt = (k + 1 + 3) & ~3, (k + 15) >> 4

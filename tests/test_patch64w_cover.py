@@ -26,8 +26,8 @@ def lib():
 
 
 def lds_bytes(k, ub):
-    """LDS of a launch, restated from patch64w_lds_bytes (csrc/letkf_patch64w.hip; letkf_stream64w.hip's with the caller's
-    blocks): ring [2][16][kp | 1], rhs [4 KT][64] and the sqrt(rho) table [16][16 ub + 1] in doubles, the slot table [16 ub]
+    """LDS of a launch, restated from ring64_lds_bytes (csrc/mia_frames64.h) with the caller's
+    blocks: ring [2][16][kp | 1], rhs [4 KT][64] and the sqrt(rho) table [16][16 ub + 1] in doubles, the slot table [16 ub]
     in ints"""
     umax, kp, kt = 16 * ub, (k + 1 + 3) & ~3, (k + 15) >> 4
     return ((2 * 16 * (kp | 1) + 4 * kt * 64 + 16 * (umax + 1)) * 8 + umax * 4 + 15) // 16 * 16

@@ -17,7 +17,7 @@ def _lib():
 
 
 def lds_bytes(ub, k):
-    """Restates stream64_lds_bytes: ring [2][16][kp | 1] + rhs [4 KT][64] + sqrt(rho) [16][16 ub + 1] doubles, slot table
+    """Restates ring64_lds_bytes (csrc/mia_frames64.h): ring [2][16][kp | 1] + rhs [4 KT][64] + sqrt(rho) [16][16 ub + 1] doubles, slot table
     [16 ub] ints, rounded up to 16 bytes."""
     umax, kp, kt = 16 * ub, (k + 1 + 3) & ~3, (k + 15) >> 4
     b = (2 * 16 * (kp | 1) + 4 * kt * 64 + 16 * (umax + 1)) * 8 + umax * 4

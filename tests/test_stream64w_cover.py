@@ -21,7 +21,7 @@ def lib():
 
 
 def lds_bytes(k, p_max):
-    """LDS of a launch, restated from stream64_lds_bytes (csrc/letkf_stream64.hip, copied into csrc/letkf_stream64w.hip): ring
+    """LDS of a launch, restated from ring64_lds_bytes and ring64_blocks (csrc/mia_frames64.h): ring
     [2][16][kp | 1], rhs [4 KT][64] and the sqrt(rho) table [16][16 UB + 1] in doubles, the slot table [16 UB] in ints, with
     UB = min(ceil((p_max + 16) / 16), 16) sixteen-slot blocks"""
     ub = min((p_max + 16 + 15) >> 4, 16)

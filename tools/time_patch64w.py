@@ -29,7 +29,7 @@ CASES = ["40,3.0,316", "64,3.0,316", "80,3.0,316", "96,3.0,316", "128,3.5,224"]
 
 
 def lds_bytes(ub, k):
-    """Restates stream64w_lds_bytes / patch64w_lds_bytes (csrc)."""
+    """Restates ring64_lds_bytes (csrc/mia_frames64.h)."""
     umax, kp, kt = 16 * ub, (k + 4) & ~3, (k + 15) >> 4
     return -(-((2 * 16 * (kp | 1) + 4 * kt * 64 + 16 * (umax + 1)) * 8 + umax * 4) // 16) * 16
 

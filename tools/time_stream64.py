@@ -34,7 +34,7 @@ CASES = ["80,93,1", "80,93,8", "80,173,1", "80,173,8", "96,107,1", "96,107,8", "
 
 
 def lds_bytes(ub, k):
-    """Restates stream64_lds_bytes (csrc/letkf_stream64.hip)."""
+    """Restates ring64_lds_bytes (csrc/mia_frames64.h)."""
     umax, kp, kt = 16 * ub, (k + 4) & ~3, (k + 15) >> 4
     return -(-((2 * 16 * (kp | 1) + 4 * kt * 64 + 16 * (umax + 1)) * 8 + umax * 4) // 16) * 16
 

@@ -35,7 +35,7 @@ CASES = ["80,93", "80,173", "96,107", "96,173", "128,139", "128,203", "65,77", "
 
 
 def lds_bytes(ub, k):
-    """Restates stream64w_lds_bytes (csrc/letkf_stream64w.hip)."""
+    """Restates ring64_lds_bytes (csrc/mia_frames64.h)."""
     umax, kp, kt = 16 * ub, (k + 4) & ~3, (k + 15) >> 4
     return -(-((2 * 16 * (kp | 1) + 4 * kt * 64 + 16 * (umax + 1)) * 8 + umax * 4) // 16) * 16
 

@@ -1,8 +1,9 @@
 // letkf_stream64w.hip's WEIGHTS (FLOAT64, dense local networks p_max > k, ensembles up to 128 members, sixteen grid points per
 // wavefront, every contraction a v_mfma_f64_16x16x4_f64, the union's records streamed through a ring of two sixteen-slot blocks)
 // with letkf_patch64.hip's two changes to the FRAME; mathematics, lane roles, summation order, the ring and its
-// stage / chain / fold / turn discipline, the streamed bound, table, decline and the run-time loops are letkf_stream64w.hip's
-// (reference: core/etkf.py:57-103 + interface/letkf.py:127-146) and are not restated here.
+// stage / chain / fold / turn discipline and the run-time loops are the ring family's (csrc/mia_ring64_dev.h, shared), the
+// streamed bound, table and decline letkf_stream64w.hip's (reference: core/etkf.py:57-103 +
+// interface/letkf.py:127-146) and are not restated here.
 //
 // 1. TILE MAP.  The sixteen points of tile t are tile_pts[16 t + s], s = 0 .. 15: indices into the launch's range [0, ng),
 //    -1 = empty slot.  On a row-major 2-D mesh sixteen CONSECUTIVE points are a 16 x 1 strip whose lists have a union of 200
@@ -24,10 +25,11 @@
 // A point's observations are summed in ascending index order with exact zeros in between whatever else is in the tile, so W
 // and flags are letkf_patch64w_kernel's bit for bit under any map (tests/test_gpu_patch64w.py).
 //
-// The kernel is a copy of letkf_patch64w_kernel with the frame changed, not a shared body (DESIGN 2.18 on letkf_patch64.hip:
-// the map reaches every address the frame forms, and the parent's code object stays what it was).
+// The kernel keeps its own text for everything the map reaches (DESIGN 2.18 on letkf_patch64.hip: the map reaches every
+// address the frame forms); what it does not reach is mia_ring64_dev.h's.
 #include "mia_cheb_table64.h"
 #include "mia_frames64.h"
+#include "mia_ring64_dev.h"
 #include "mia_tile_launch.h"
 
 namespace mia {
@@ -53,20 +55,16 @@ __global__ __launch_bounds__(64, 1) void letkf_patch64w_kernel(Patch64WParams P)
   const int k = P.k, kp = P.kp, pm = P.p_max;
   const int UMAX = 16 * P.ub, DS = UMAX + 1;
   const int KS = kp | 1;                                     // odd row pitch (in doubles) of a staged block
-  constexpr int NC = KT + 1;                                 // column trips of a staged row: kp <= 16 KT + 4
   double* Ring = reinterpret_cast<double*>(smem_raw);        // [2][16][KS] two sixteen-slot blocks of union records
   double* Rl = Ring + 2 * 16 * KS;                           // [4 KT][64]  rhs of the tile, every lane its own registers' worth
   double* Dl = Rl + 4 * KT * 64;                             // [16][DS]    sqrt(rho) of (point, slot), 0 = not local
   int* ukey = reinterpret_cast<int*>(Dl + 16 * DS);          // [UMAX]      observation index of a slot, ascending; -1 = none
   unsigned* Kl = reinterpret_cast<unsigned*>(Dl);            // [16][nl]    index + 1 of the lists' entries while the union is formed
 
-  // XCD-aware block -> tile map: blocks b, b + 8, ... share an XCD (and its L2) and take consecutive tiles, whose
-  // records overlap (consecutive tiles of a patch row)
   const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
   const int64_t ntile = P.n_tiles;
   if (bid >= ntile) return;
-  const int64_t q8 = ntile >> 3, r8 = ntile & 7, xcd = bid & 7;
-  const int64_t tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int64_t tile = ring64_tile_of_block(bid, ntile);
   const int lr = lane & 15, h = lane >> 4, lp = lane >> 2, sub = lane & 3;
 
   // ---- the tile's points: slot lr is this lane's column, slot lp the list it walks.  An entry outside [0, ng) is an empty
@@ -104,34 +102,11 @@ __global__ __launch_bounds__(64, 1) void letkf_patch64w_kernel(Patch64WParams P)
   // a point without observations: sqrt(inf) I, written directly (lanes 4 lr .. 4 lr + 3 hold slot lr's count)
   const bool cempty = __shfl(lcnt, 4 * lr, 64) == 0;
 
-  // ---- the ring: stage() asks memory for block tb of the union (rows 4 j + h, columns lr + 16 i of this lane), commit()
-  //      writes the staged registers to one half.  Rows beyond the union (key -1) are zeros and touch no memory
+  // ---- the ring (mia_ring64_dev.h); st holds the block this lane has staged
   int UB = 1;
   int cur = 0;                                               // the half that holds the block of the trip
-  double st[4][NC];
-  auto stage = [&](int tb) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int key = ukey[16 * tb + 4 * j + h];
-      const double* src = P.rec + ((int64_t)(key < 0 ? 0 : key) * kp + lr);
-#pragma unroll
-      for (int i = 0; i < NC; ++i) {
-        double v = 0.0;
-        if (key >= 0 && (i < KT - 1 || lr + 16 * i < kp)) v = src[16 * i];
-        st[j][i] = v;
-      }
-    }
-  };
-  auto commit = [&](int half, double& fin) {                 // fin stays 0 while every value is finite (inf * 0 = NaN)
-    double* dst = Ring + half * 16 * KS + h * KS + lr;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int i = 0; i < NC; ++i) {
-        fin = fma(st[j][i], 0.0, fin);
-        if (i < KT - 1 || lr + 16 * i < kp) dst[4 * j * KS + 16 * i] = st[j][i];
-      }
-  };
+  double st[4][Ring64<KT>::NC];
+  const Ring64<KT> ring{Ring, P.rec, ukey, k, kp, KS, lr, h, cur, st};
 
   int lo = 0;
   bool single = false;                                       // a non-finite record was met: the rest of the tile goes point by point
@@ -140,72 +115,6 @@ __global__ __launch_bounds__(64, 1) void letkf_patch64w_kernel(Patch64WParams P)
     if (!((livemask >> lo) & 1u)) { ++lo; continue; }        // a range starts at a live slot, so it is never empty
     const bool colok = live_c && !((badmask >> (4 * lr)) & 1ull);
     const double* Dcol = Dl + lr * DS + h;                    // + 16 t + 4 r: slot 16 t + h + 4 r of column lr
-    // A operands out of the current half.  First product / Gram: record row lr of the block, member 16 tm + 4 q + h; second
-    // product: record row 4 q + h, member 16 tj + lr.  Innovation and pad columns are not members (only the last block is ragged).
-    auto a_in = [&](int tm, int q) -> double {
-      const int mem = 16 * tm + 4 * q + h;
-      const bool ok = tm < KT - 1 || mem < k;
-      const double v = Ring[cur * 16 * KS + lr * KS + (ok ? mem : 0)];
-      return ok ? v : 0.0;
-    };
-    auto a_out = [&](int q, int tj) -> double {
-      const int mem = 16 * tj + lr;
-      const bool ok = tj < KT - 1 || mem < k;
-      const double v = Ring[cur * 16 * KS + (4 * q + h) * KS + (ok ? mem : 0)];
-      return ok ? v : 0.0;
-    };
-    // The A operands of four matrix instructions are read from LDS while the four before them run, and the scheduler is
-    // held to that order: left alone it reads a trip's 8 KT operands ahead of its first instruction, which the 40 KT
-    // registers of the recurrence vectors and the staged block leave no room for above 80 members.
-    // T (or Gram) block of the trip: steps (tm, q) ascending through ONE accumulator; b[tm][q] = the B operands
-    auto chain = [&](const auto& b) -> d4t {
-      d4t acc = {0., 0., 0., 0.};
-      double an[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) an[q] = a_in(0, q);
-#pragma unroll
-      for (int tm = 0; tm < KT; ++tm) {
-        double ac[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) ac[q] = an[q];
-        if (tm + 1 < KT) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) an[q] = a_in(tm + 1, q);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc = MIA_MFMA64(ac[q], b[tm][q], acc);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      return acc;
-    };
-    // y += Yw^T (s o .) over the block of the trip: the second product's steps (tb, q), B = the scaled block; step
-    // e = KT q + tj, four steps per group
-    auto fold = [&](const double (&s)[4], d4t (&y)[KT]) {
-      double an[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) an[i] = a_out(i / KT, i % KT);
-#pragma unroll
-      for (int g = 0; g < KT; ++g) {
-        double ac[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ac[i] = an[i];
-        if (g + 1 < KT) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) an[i] = a_out((4 * g + 4 + i) / KT, (4 * g + 4 + i) % KT);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) y[(4 * g + i) % KT] = MIA_MFMA64(ac[i], s[(4 * g + i) / KT], y[(4 * g + i) % KT]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    };
-    // the end of a trip: the staged block into the other half, which becomes the current one
-    auto turn = [&](double& fin) {
-      commit(cur ^ 1, fin);
-      __syncthreads();
-      cur ^= 1;
-    };
     // ---- union of the lists of slots [lo, hi): slot of the union = RANK of the observation index, found by repeated extraction of
     //      the smallest remaining key (one sweep over the keys in LDS and one DPP reduction per slot); shrink the range
     //      until the union fits
@@ -259,8 +168,8 @@ __global__ __launch_bounds__(64, 1) void letkf_patch64w_kernel(Patch64WParams P)
         }
       // ---- block 0 into the ring
       double fin = 0.0;
-      stage(0);
-      commit(cur, fin);
+      ring.stage(0);
+      ring.commit(cur, fin);
       __syncthreads();
       // ---- rhs_g = Yw^T (rho_g o d), once per tile (d = column k of the records); this first pass over the union also
       //      looks at every record (blocks 1 .. UB - 1 and block 0 again pass through commit)
@@ -271,15 +180,15 @@ __global__ __launch_bounds__(64, 1) void letkf_patch64w_kernel(Patch64WParams P)
         int tb = 0;
 #pragma clang loop unroll(disable)
         do {
-          stage(tb + 1 < UB ? tb + 1 : 0);
+          ring.stage(tb + 1 < UB ? tb + 1 : 0);
           double s[4];
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const double dv = Dcol[16 * tb + 4 * q];
             s[q] = dv * dv * Ring[cur * 16 * KS + (4 * q + h) * KS + k];
           }
-          fold(s, rhs);
-          turn(fin);
+          ring.fold(s, rhs);
+          ring.turn(fin);
         } while (++tb < UB);
       }
       // A non-finite record would reach EVERY column of the tile through the shared products (NaN * 0 = NaN), also the
@@ -321,15 +230,15 @@ __global__ __launch_bounds__(64, 1) void letkf_patch64w_kernel(Patch64WParams P)
         int tk = 0;
 #pragma clang loop unroll(disable)
         do {
-          stage(tk + 1 < UB ? tk + 1 : 0);
+          ring.stage(tk + 1 < UB ? tk + 1 : 0);
           __builtin_amdgcn_sched_barrier(0);
-          const d4t Gb = chain(at);
+          const d4t Gb = ring.chain(at);
           double dk[4];
 #pragma unroll
           for (int q = 0; q < 4; ++q) dk[q] = Dcol[16 * tk + 4 * q];
 #pragma unroll
           for (int q = 0; q < 4; ++q) R = MIA_MFMA64(fabs(Gb[q]), dk[q], R);
-          turn(nofin);
+          ring.turn(nofin);
         } while (++tk < UB);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -359,11 +268,7 @@ __global__ __launch_bounds__(64, 1) void letkf_patch64w_kernel(Patch64WParams P)
     }
     // (a column without observations is written directly: its series is not looked at and asks for no step)
     const int degmax = (int)tile64_wave_max_u32((colact && !decl && !cempty) ? (unsigned)deg : 0u);
-    const double2* ctab = P.tab_c + (size_t)tab_idx * kTab64Deg;
-    auto coef = [&](int j) -> double2 {                              // (zero beyond a point's own degree)
-      const double2 c = ctab[j < kTab64Deg ? j : kTab64Deg - 1];
-      return double2{c.x * P.cs_phi, c.y * P.cs_psi};
-    };
+    const Coef64 coef{P.tab_c + (size_t)tab_idx * kTab64Deg, P.cs_phi, P.cs_psi};
 
 #pragma clang loop unroll(disable)
     for (int c = 0; c < k; ++c) {
@@ -379,42 +284,12 @@ __global__ __launch_bounds__(64, 1) void letkf_patch64w_kernel(Patch64WParams P)
       for (int tm = 0; tm < KT; ++tm)
 #pragma unroll
         for (int q = 0; q < 4; ++q) va[tm][q] = (colact && 16 * tm + 4 * q + hv == c) ? 1.0 : 0.0;
-      // acc += sc C u = Yw^T (sc rho o (Yw u)), one sixteen-slot block of the union per trip; sc = alpha or 2 alpha of the
-      // column.  The caller has put the recurrence's other terms into acc: the step needs no vector of its own for C u,
-      // which at 128 members is the 64 registers that decide between spilling and not
-      auto product = [&](const d4t (&u)[KT], d4t (&acc)[KT], const double sc) {
-        int tb = 0;
-#pragma clang loop unroll(disable)
-        do {
-          stage(tb + 1 < UB ? tb + 1 : 0);
-          __builtin_amdgcn_sched_barrier(0);
-          const d4t Tb = chain(u);
-          double s[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const double dv = Dcol[16 * tb + 4 * q];
-            s[q] = (sc * (dv * dv)) * Tb[q];
-          }
-          fold(s, acc);
-          turn(nofin);
-        } while (++tb < UB);
-      };
-      // vnew = 2 alpha C vcur - 2 vcur - vold, accumulated over vold; the two functions accumulate c_j vnew
-      auto advance = [&](d4t (&vold)[KT], const d4t (&vcur)[KT], const double2 cj) {
-#pragma unroll
-        for (int t = 0; t < KT; ++t) vold[t] = -2.0 * vcur[t] - vold[t];
-        product(vcur, vold, 2.0 * alpha);
-#pragma unroll
-        for (int t = 0; t < KT; ++t) {
-          aphi[t] = cj.x * vold[t] + aphi[t];
-          apsi[t] = cj.y * vold[t] + apsi[t];
-        }
-      };
+      const Recur64<KT> step{ring, Dcol, UB, nofin, alpha, aphi, apsi};     // product / advance of the recurrence
       {
         const double2 c0 = coef(0), c1 = coef(1);
 #pragma unroll
         for (int t = 0; t < KT; ++t) vb[t] = -va[t];
-        product(va, vb, alpha);                 // vb = v_1 = alpha C v_0 - v_0
+        step.product(va, vb, alpha);                 // vb = v_1 = alpha C v_0 - v_0
 #pragma unroll
         for (int t = 0; t < KT; ++t) {
           aphi[t] = c0.x * va[t] + c1.x * vb[t];
@@ -426,11 +301,11 @@ __global__ __launch_bounds__(64, 1) void letkf_patch64w_kernel(Patch64WParams P)
 #pragma clang loop unroll(disable)
       for (; j + 1 <= degmax; j += 2) {
         const double2 nj = coef(j + 2), nj1 = coef(j + 3);       // requested one trip ahead
-        advance(va, vb, cj);          // va = v_j
-        advance(vb, va, cj1);         // vb = v_{j+1}
+        step.advance(va, vb, cj);          // va = v_j
+        step.advance(vb, va, cj1);         // vb = v_{j+1}
         cj = nj; cj1 = nj1;
       }
-      if (j <= degmax) advance(va, vb, cj);
+      if (j <= degmax) step.advance(va, vb, cj);
       // ---- wm_c = (psi(C) e_c) . rhs / reg: members in the lane's registers first, then the four lane groups
       double zs = 0.0;
 #pragma unroll

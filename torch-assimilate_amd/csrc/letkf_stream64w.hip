@@ -2,11 +2,11 @@
 // wavefront, every contraction on the matrix cores (v_mfma_f64_16x16x4_f64): what LETKF.estimate_weights returns
 // (interface/letkf.py:127-146, core/etkf.py:57-103), W[g][i][j] = w_mean_i + W_pert_ij, without an eigensolver.
 //
-// The frame is letkf_stream64.hip's, statement for statement up to and including the degree and decline of
-// every point: per-point lists of any metric, union by rank extraction, the union's records streamed through a ring of two
-// sixteen-slot blocks in LDS, rhs in LDS, the streamed Gershgorin bound, the primal table.  (A copy, not a template switch: the
-// analysis kernel's code object stays what it was.)  What stays in LDS per wave is the sqrt(rho) table, the slot table, the
-// ring and the tile's rhs: 256 slots at every 2 <= k <= 128.
+// The frame is the ring family's (csrc/mia_ring64_dev.h: mathematics of the products, lane roles, summation order, the ring
+// and the rules of the run-time loops) and, block for block, letkf_stream64.hip's up to and including the degree
+// and decline of every point: per-point lists of any metric, union by rank extraction, the union's records streamed through
+// a ring of two sixteen-slot blocks in LDS, rhs in LDS, the streamed Gershgorin bound, the primal table.  What stays in LDS
+// per wave is the sqrt(rho) table, the slot table, the ring and the tile's rhs: 256 slots at every 2 <= k <= 128.
 //
 // What differs is letkf_tile64w.hip's: instead of one pass per state row there is one pass per MEMBER c < k
 // with x' = e_c -- no state load, no mean.  With reg = (k - 1) / inf, C_g = Yw^T diag(rho_g) Yw (k x k, what the reference
@@ -19,37 +19,7 @@
 // wave-uniform base (tile, row c) + a 32-bit lane offset (16 k^2 8 <= 2^21).  For fixed (tj, r) the four lane groups h hold
 // four consecutive j: one store instruction writes sixteen 32-byte segments, one per point.  A point WITHOUT observations
 // gets sqrt(inf) I exactly (etkf.py:91-95): the truncated series at C = 0 is only about 1, so such a column is written
-// directly, takes no part in the tile's degree and reports flag 0.  C_g is never formed:
-//
-//     C_g u = Yw^T (rho_g o (Yw u))          T = Yw . U   (16 slots x k)(k x 16 points),   y += Yw^T . (rho o T)
-//
-// two thin products per sixteen-slot block whose left factors belong to the tile and whose sixteen columns are the sixteen
-// points; both read their A operands from the staged block, which is therefore fetched once per trip and read twice.  The
-// recurrence keeps FOUR k-vectors, not letkf_dense64.hip's five: the accumulator of the second product starts at the step's
-// other terms, -2 v_j - v_{j-1}, and the column's 2 alpha rides on rho o T, so that the chain leaves v_{j+1} in place.  The
-// spectral bound is the dual route's: L_g = max_a w_a sum_b |G_ab| w_b; row block t is held as operands in registers (read
-// straight from memory, once per t) while the blocks tk stream through the ring.
-//
-// Lane roles follow v_mfma_f64_16x16x4_f64 as in letkf_tile64.hip: lane (lr, h) = (lane & 15, lane >> 4) supplies A[lr][h]
-// and B[h][lr]; of a result block it holds column lr (= grid point lr), rows h + 4 r in register r.  A k-vector of the
-// sixteen points is KT result blocks (member 16 tm + h + 4 r in register r): register q of block tm IS the B operand of
-// step (tm, q) of the first product, the scaled block of T the B operand of steps (tb, q) of the second.
-//
-// Summation order is canonical: slot = RANK of the observation index inside the union, blocks and steps ascend, every sum
-// over the union is ONE chain of matrix instructions through its accumulator (never partial sums per block), so a point's
-// own observations are summed in ascending index order with exact zeros in between, whatever else is in the tile.
-//
-// The ring.  Every pass over the union (rhs, the rows of the bound, every product of the recurrence) finds block 0 in the
-// ring's current half and leaves it there: trip tb asks memory for block tb + 1 (block 0 in the last trip) at its top,
-// multiplies block tb out of the current half, writes the staged registers to the other half, passes the barrier and swaps
-// the halves.  A lane stages rows 4 j + h, columns lr + 16 i: one base address per row, the columns are immediate offsets.
-// A slot beyond the union has key -1: it is never turned into an address, its row is written as zeros.
-//
-// The loops over union blocks are run-time loops.  What they rely on: builtins only; every such loop is a
-// do-while that runs at least once, so that it is left on the fall-through side of its closing branch; an accumulator that
-// lives across the back edge is touched by matrix instructions only until the loop has been left; a block of T (or of the
-// Gram matrix) is fresh in every trip and its vector read is followed by the trip's remaining matrix instructions.  The
-// ring's loads stand at the top of a trip, before its first matrix instruction; its LDS writes and barrier behind the last.
+// directly, takes no part in the tile's degree and reports flag 0.
 //
 // A tile whose union exceeds the slots of the launch is processed in halves (quarters, ...): one point always fits.  A tile
 // that holds a non-finite record is done point by point.  Points whose degree exceeds the table's cap are DECLINED
@@ -57,6 +27,7 @@
 // (mia_letkf_weights_retry_f64) where that kernel holds the shape.
 #include "mia_cheb_table64.h"
 #include "mia_frames64.h"
+#include "mia_ring64_dev.h"
 #include "mia_tile_launch.h"
 
 namespace mia {
@@ -81,20 +52,16 @@ __global__ __launch_bounds__(64, 1) void letkf_stream64w_kernel(Stream64WParams 
   const int k = P.k, kp = P.kp, pm = P.p_max;
   const int UMAX = 16 * P.ub, DS = UMAX + 1;
   const int KS = kp | 1;                                     // odd row pitch (in doubles) of a staged block
-  constexpr int NC = KT + 1;                                 // column trips of a staged row: kp <= 16 KT + 4
   double* Ring = reinterpret_cast<double*>(smem_raw);        // [2][16][KS] two sixteen-slot blocks of union records
   double* Rl = Ring + 2 * 16 * KS;                           // [4 KT][64]  rhs of the tile, every lane its own registers' worth
   double* Dl = Rl + 4 * KT * 64;                             // [16][DS]    sqrt(rho) of (point, slot), 0 = not local
   int* ukey = reinterpret_cast<int*>(Dl + 16 * DS);          // [UMAX]      observation index of a slot, ascending; -1 = none
   unsigned* Kl = reinterpret_cast<unsigned*>(Dl);            // [16][nl]    index + 1 of the lists' entries while the union is formed
 
-  // XCD-aware block -> tile map: blocks b, b + 8, ... share an XCD (and its L2) and take consecutive tiles, whose
-  // records overlap
   const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
   const int64_t ntile = (P.ng + 15) >> 4;
   if (bid >= ntile) return;
-  const int64_t q8 = ntile >> 3, r8 = ntile & 7, xcd = bid & 7;
-  const int64_t tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int64_t tile = ring64_tile_of_block(bid, ntile);
   const int64_t p0 = tile << 4;                              // first point of the tile (index into the launch's ng points)
   const int npts = P.ng - p0 < 16 ? (int)(P.ng - p0) : 16;
   const int lr = lane & 15, h = lane >> 4, lp = lane >> 2, sub = lane & 3;
@@ -122,34 +89,11 @@ __global__ __launch_bounds__(64, 1) void letkf_stream64w_kernel(Stream64WParams 
   // a point without observations: sqrt(inf) I, written directly (lanes 4 lr .. 4 lr + 3 hold point lr's count)
   const bool cempty = __shfl(lcnt, 4 * lr, 64) == 0;
 
-  // ---- the ring: stage() asks memory for block tb of the union (rows 4 j + h, columns lr + 16 i of this lane), commit()
-  //      writes the staged registers to one half.  Rows beyond the union (key -1) are zeros and touch no memory
+  // ---- the ring (mia_ring64_dev.h); st holds the block this lane has staged
   int UB = 1;
   int cur = 0;                                               // the half that holds the block of the trip
-  double st[4][NC];
-  auto stage = [&](int tb) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int key = ukey[16 * tb + 4 * j + h];
-      const double* src = P.rec + ((int64_t)(key < 0 ? 0 : key) * kp + lr);
-#pragma unroll
-      for (int i = 0; i < NC; ++i) {
-        double v = 0.0;
-        if (key >= 0 && (i < KT - 1 || lr + 16 * i < kp)) v = src[16 * i];
-        st[j][i] = v;
-      }
-    }
-  };
-  auto commit = [&](int half, double& fin) {                 // fin stays 0 while every value is finite (inf * 0 = NaN)
-    double* dst = Ring + half * 16 * KS + h * KS + lr;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int i = 0; i < NC; ++i) {
-        fin = fma(st[j][i], 0.0, fin);
-        if (i < KT - 1 || lr + 16 * i < kp) dst[4 * j * KS + 16 * i] = st[j][i];
-      }
-  };
+  double st[4][Ring64<KT>::NC];
+  const Ring64<KT> ring{Ring, P.rec, ukey, k, kp, KS, lr, h, cur, st};
 
   int lo = 0;
   bool single = false;                                       // a non-finite record was met: the rest of the tile goes point by point
@@ -157,72 +101,6 @@ __global__ __launch_bounds__(64, 1) void letkf_stream64w_kernel(Stream64WParams 
   while (lo < npts) {
     const bool colok = lr < npts && !((badmask >> (4 * lr)) & 1ull);
     const double* Dcol = Dl + lr * DS + h;                    // + 16 t + 4 r: slot 16 t + h + 4 r of column lr
-    // A operands out of the current half.  First product / Gram: record row lr of the block, member 16 tm + 4 q + h; second
-    // product: record row 4 q + h, member 16 tj + lr.  Innovation and pad columns are not members (only the last block is ragged).
-    auto a_in = [&](int tm, int q) -> double {
-      const int mem = 16 * tm + 4 * q + h;
-      const bool ok = tm < KT - 1 || mem < k;
-      const double v = Ring[cur * 16 * KS + lr * KS + (ok ? mem : 0)];
-      return ok ? v : 0.0;
-    };
-    auto a_out = [&](int q, int tj) -> double {
-      const int mem = 16 * tj + lr;
-      const bool ok = tj < KT - 1 || mem < k;
-      const double v = Ring[cur * 16 * KS + (4 * q + h) * KS + (ok ? mem : 0)];
-      return ok ? v : 0.0;
-    };
-    // The A operands of four matrix instructions are read from LDS while the four before them run, and the scheduler is
-    // held to that order: left alone it reads a trip's 8 KT operands ahead of its first instruction, which the 40 KT
-    // registers of the recurrence vectors and the staged block leave no room for above 80 members.
-    // T (or Gram) block of the trip: steps (tm, q) ascending through ONE accumulator; b[tm][q] = the B operands
-    auto chain = [&](const auto& b) -> d4t {
-      d4t acc = {0., 0., 0., 0.};
-      double an[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) an[q] = a_in(0, q);
-#pragma unroll
-      for (int tm = 0; tm < KT; ++tm) {
-        double ac[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) ac[q] = an[q];
-        if (tm + 1 < KT) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) an[q] = a_in(tm + 1, q);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc = MIA_MFMA64(ac[q], b[tm][q], acc);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      return acc;
-    };
-    // y += Yw^T (s o .) over the block of the trip: the second product's steps (tb, q), B = the scaled block; step
-    // e = KT q + tj, four steps per group
-    auto fold = [&](const double (&s)[4], d4t (&y)[KT]) {
-      double an[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) an[i] = a_out(i / KT, i % KT);
-#pragma unroll
-      for (int g = 0; g < KT; ++g) {
-        double ac[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ac[i] = an[i];
-        if (g + 1 < KT) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) an[i] = a_out((4 * g + 4 + i) / KT, (4 * g + 4 + i) % KT);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) y[(4 * g + i) % KT] = MIA_MFMA64(ac[i], s[(4 * g + i) / KT], y[(4 * g + i) % KT]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    };
-    // the end of a trip: the staged block into the other half, which becomes the current one
-    auto turn = [&](double& fin) {
-      commit(cur ^ 1, fin);
-      __syncthreads();
-      cur ^= 1;
-    };
     // ---- union of the lists of points [lo, hi): slot = RANK of the observation index, found by repeated extraction of
     //      the smallest remaining key (one sweep over the keys in LDS and one DPP reduction per slot); shrink the range
     //      until the union fits
@@ -276,8 +154,8 @@ __global__ __launch_bounds__(64, 1) void letkf_stream64w_kernel(Stream64WParams 
         }
       // ---- block 0 into the ring
       double fin = 0.0;
-      stage(0);
-      commit(cur, fin);
+      ring.stage(0);
+      ring.commit(cur, fin);
       __syncthreads();
       // ---- rhs_g = Yw^T (rho_g o d), once per tile (d = column k of the records); this first pass over the union also
       //      looks at every record (blocks 1 .. UB - 1 and block 0 again pass through commit)
@@ -288,15 +166,15 @@ __global__ __launch_bounds__(64, 1) void letkf_stream64w_kernel(Stream64WParams 
         int tb = 0;
 #pragma clang loop unroll(disable)
         do {
-          stage(tb + 1 < UB ? tb + 1 : 0);
+          ring.stage(tb + 1 < UB ? tb + 1 : 0);
           double s[4];
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const double dv = Dcol[16 * tb + 4 * q];
             s[q] = dv * dv * Ring[cur * 16 * KS + (4 * q + h) * KS + k];
           }
-          fold(s, rhs);
-          turn(fin);
+          ring.fold(s, rhs);
+          ring.turn(fin);
         } while (++tb < UB);
       }
       // A non-finite record would reach EVERY column of the tile through the shared products (NaN * 0 = NaN), also the
@@ -336,15 +214,15 @@ __global__ __launch_bounds__(64, 1) void letkf_stream64w_kernel(Stream64WParams 
         int tk = 0;
 #pragma clang loop unroll(disable)
         do {
-          stage(tk + 1 < UB ? tk + 1 : 0);
+          ring.stage(tk + 1 < UB ? tk + 1 : 0);
           __builtin_amdgcn_sched_barrier(0);
-          const d4t Gb = chain(at);
+          const d4t Gb = ring.chain(at);
           double dk[4];
 #pragma unroll
           for (int q = 0; q < 4; ++q) dk[q] = Dcol[16 * tk + 4 * q];
 #pragma unroll
           for (int q = 0; q < 4; ++q) R = MIA_MFMA64(fabs(Gb[q]), dk[q], R);
-          turn(nofin);
+          ring.turn(nofin);
         } while (++tk < UB);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -374,11 +252,7 @@ __global__ __launch_bounds__(64, 1) void letkf_stream64w_kernel(Stream64WParams 
     }
     // (a column without observations is written directly: its series is not looked at and asks for no step)
     const int degmax = (int)tile64_wave_max_u32((colact && !decl && !cempty) ? (unsigned)deg : 0u);
-    const double2* ctab = P.tab_c + (size_t)tab_idx * kTab64Deg;
-    auto coef = [&](int j) -> double2 {                              // (zero beyond a point's own degree)
-      const double2 c = ctab[j < kTab64Deg ? j : kTab64Deg - 1];
-      return double2{c.x * P.cs_phi, c.y * P.cs_psi};
-    };
+    const Coef64 coef{P.tab_c + (size_t)tab_idx * kTab64Deg, P.cs_phi, P.cs_psi};
 
 #pragma clang loop unroll(disable)
     for (int c = 0; c < k; ++c) {
@@ -394,42 +268,12 @@ __global__ __launch_bounds__(64, 1) void letkf_stream64w_kernel(Stream64WParams 
       for (int tm = 0; tm < KT; ++tm)
 #pragma unroll
         for (int q = 0; q < 4; ++q) va[tm][q] = (colact && 16 * tm + 4 * q + hv == c) ? 1.0 : 0.0;
-      // acc += sc C u = Yw^T (sc rho o (Yw u)), one sixteen-slot block of the union per trip; sc = alpha or 2 alpha of the
-      // column.  The caller has put the recurrence's other terms into acc: the step needs no vector of its own for C u,
-      // which at 128 members is the 64 registers that decide between spilling and not
-      auto product = [&](const d4t (&u)[KT], d4t (&acc)[KT], const double sc) {
-        int tb = 0;
-#pragma clang loop unroll(disable)
-        do {
-          stage(tb + 1 < UB ? tb + 1 : 0);
-          __builtin_amdgcn_sched_barrier(0);
-          const d4t Tb = chain(u);
-          double s[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const double dv = Dcol[16 * tb + 4 * q];
-            s[q] = (sc * (dv * dv)) * Tb[q];
-          }
-          fold(s, acc);
-          turn(nofin);
-        } while (++tb < UB);
-      };
-      // vnew = 2 alpha C vcur - 2 vcur - vold, accumulated over vold; the two functions accumulate c_j vnew
-      auto advance = [&](d4t (&vold)[KT], const d4t (&vcur)[KT], const double2 cj) {
-#pragma unroll
-        for (int t = 0; t < KT; ++t) vold[t] = -2.0 * vcur[t] - vold[t];
-        product(vcur, vold, 2.0 * alpha);
-#pragma unroll
-        for (int t = 0; t < KT; ++t) {
-          aphi[t] = cj.x * vold[t] + aphi[t];
-          apsi[t] = cj.y * vold[t] + apsi[t];
-        }
-      };
+      const Recur64<KT> step{ring, Dcol, UB, nofin, alpha, aphi, apsi};     // product / advance of the recurrence
       {
         const double2 c0 = coef(0), c1 = coef(1);
 #pragma unroll
         for (int t = 0; t < KT; ++t) vb[t] = -va[t];
-        product(va, vb, alpha);                 // vb = v_1 = alpha C v_0 - v_0
+        step.product(va, vb, alpha);                 // vb = v_1 = alpha C v_0 - v_0
 #pragma unroll
         for (int t = 0; t < KT; ++t) {
           aphi[t] = c0.x * va[t] + c1.x * vb[t];
@@ -441,11 +285,11 @@ __global__ __launch_bounds__(64, 1) void letkf_stream64w_kernel(Stream64WParams 
 #pragma clang loop unroll(disable)
       for (; j + 1 <= degmax; j += 2) {
         const double2 nj = coef(j + 2), nj1 = coef(j + 3);       // requested one trip ahead
-        advance(va, vb, cj);          // va = v_j
-        advance(vb, va, cj1);         // vb = v_{j+1}
+        step.advance(va, vb, cj);          // va = v_j
+        step.advance(vb, va, cj1);         // vb = v_{j+1}
         cj = nj; cj1 = nj1;
       }
-      if (j <= degmax) advance(va, vb, cj);
+      if (j <= degmax) step.advance(va, vb, cj);
       // ---- wm_c = (psi(C) e_c) . rhs / reg: members in the lane's registers first, then the four lane groups
       double zs = 0.0;
 #pragma unroll

@@ -11,12 +11,12 @@
 //
 // i.e. the LETKF weights at inflation 1 with the innovations shifted by D^T w_mean.
 //
-// The frame is letkf_stream64w.hip's, statement for statement: per-point lists of any metric, union by rank
+// The frame is letkf_stream64w.hip's, block for block: per-point lists of any metric, union by rank
 // extraction, the union's records streamed through a ring of two sixteen-slot blocks in LDS with its stage / chain / fold /
-// turn discipline, rhs in LDS, the streamed Gershgorin bound, the primal table with its degree, decline and MIA_FLAG_RETRY
-// count, halving of oversized tiles, the point-by-point pass after a non-finite record, MIA_FLAG_OVERFLOW with NaN into the
-// point's block, the XCD tile map, one pass of the recurrence per MEMBER c < k on e_c, the stores (64-bit wave-uniform base
-// plus 32-bit lane offset).  (A copy, not a template switch: the weights kernel's code object stays what it was.)  With
+// turn discipline (csrc/mia_ring64_dev.h, shared), rhs in LDS, the streamed Gershgorin bound, the primal table with its
+// degree, decline and MIA_FLAG_RETRY count, halving of oversized tiles, the point-by-point pass after a non-finite record,
+// MIA_FLAG_OVERFLOW with NaN into the point's block, the XCD tile map, one pass of the recurrence per MEMBER c < k on e_c,
+// the stores (64-bit wave-uniform base plus 32-bit lane offset).  With
 // C_g = Yw^T diag(rho_g [/ eps^2]) Yw:
 //
 //     W'[g][c][j] = wm_c + (phi(C_g) e_c)_j,        wm_c = (psi(C_g) e_c) . rhs_g / reg
@@ -27,7 +27,7 @@
 // step (tm, q) of the first product, the scaled block of T the B operand of steps (tb, q) of the second.  Summation order
 // is canonical: slot = RANK of the observation index inside the union, blocks and steps ascend, every sum over the union is
 // ONE chain of matrix instructions through its accumulator, so a point's bits depend on neither tile nor shard.  The ring
-// and the rules of the run-time loops (builtins only) are described in letkf_stream64w.hip.
+// and the rules of the run-time loops (builtins only) are described in mia_ring64_dev.h.
 //
 // What differs is lienks_wide64.hip's, placed into this frame:
 //
@@ -46,6 +46,7 @@
 // where it holds the shape.
 #include "mia_cheb_table64.h"
 #include "mia_frames64.h"
+#include "mia_ring64_dev.h"
 #include "mia_tile_launch.h"
 
 namespace mia {
@@ -150,20 +151,16 @@ __global__ __launch_bounds__(64, 1) void lienks_stream64_kernel(LienksStream64Pa
   const int k = P.k, kp = P.kp, pm = P.p_max;
   const int UMAX = 16 * P.ub, DS = UMAX + 1;
   const int KS = kp | 1;                                     // odd row pitch (in doubles) of a staged block
-  constexpr int NC = KT + 1;                                 // column trips of a staged row: kp <= 16 KT + 4
   double* Ring = reinterpret_cast<double*>(smem_raw);        // [2][16][KS] two sixteen-slot blocks of union records
   double* Rl = Ring + 2 * 16 * KS;                           // [4 KT][64]  rhs of the tile, every lane its own registers' worth
   double* Dl = Rl + 4 * KT * 64;                             // [16][DS]    sqrt(rho) of (point, slot), 0 = not local
   int* ukey = reinterpret_cast<int*>(Dl + 16 * DS);          // [UMAX]      observation index of a slot, ascending; -1 = none
   unsigned* Kl = reinterpret_cast<unsigned*>(Dl);            // [16][nl]    index + 1 of the lists' entries while the union is formed
 
-  // XCD-aware block -> tile map: blocks b, b + 8, ... share an XCD (and its L2) and take consecutive tiles, whose
-  // records overlap
   const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
   const int64_t ntile = (P.ng + 15) >> 4;
   if (bid >= ntile) return;
-  const int64_t q8 = ntile >> 3, r8 = ntile & 7, xcd = bid & 7;
-  const int64_t tile = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int64_t tile = ring64_tile_of_block(bid, ntile);
   const int64_t p0 = tile << 4;                              // first point of the tile (index into the launch's ng points)
   const int npts = P.ng - p0 < 16 ? (int)(P.ng - p0) : 16;
   const int lr = lane & 15, h = lane >> 4, lp = lane >> 2, sub = lane & 3;
@@ -217,34 +214,11 @@ __global__ __launch_bounds__(64, 1) void lienks_stream64_kernel(LienksStream64Pa
     if (!__any(lcnt > 0)) return;                            // nothing left to update in this tile
   }
 
-  // ---- the ring: stage() asks memory for block tb of the union (rows 4 j + h, columns lr + 16 i of this lane), commit()
-  //      writes the staged registers to one half.  Rows beyond the union (key -1) are zeros and touch no memory
+  // ---- the ring (mia_ring64_dev.h); st holds the block this lane has staged
   int UB = 1;
   int cur = 0;                                               // the half that holds the block of the trip
-  double st[4][NC];
-  auto stage = [&](int tb) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int key = ukey[16 * tb + 4 * j + h];
-      const double* src = P.rec + ((int64_t)(key < 0 ? 0 : key) * kp + lr);
-#pragma unroll
-      for (int i = 0; i < NC; ++i) {
-        double v = 0.0;
-        if (key >= 0 && (i < KT - 1 || lr + 16 * i < kp)) v = src[16 * i];
-        st[j][i] = v;
-      }
-    }
-  };
-  auto commit = [&](int half, double& fin) {                 // fin stays 0 while every value is finite (inf * 0 = NaN)
-    double* dst = Ring + half * 16 * KS + h * KS + lr;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int i = 0; i < NC; ++i) {
-        fin = fma(st[j][i], 0.0, fin);
-        if (i < KT - 1 || lr + 16 * i < kp) dst[4 * j * KS + 16 * i] = st[j][i];
-      }
-  };
+  double st[4][Ring64<KT>::NC];
+  const Ring64<KT> ring{Ring, P.rec, ukey, k, kp, KS, lr, h, cur, st};
 
   int lo = 0;
   bool single = false;                                       // a non-finite record was met: the rest of the tile goes point by point
@@ -252,72 +226,6 @@ __global__ __launch_bounds__(64, 1) void lienks_stream64_kernel(LienksStream64Pa
   while (lo < npts) {
     const bool colok = lr < npts && !((skipmask >> (4 * lr)) & 1ull);
     const double* Dcol = Dl + lr * DS + h;                    // + 16 t + 4 r: slot 16 t + h + 4 r of column lr
-    // A operands out of the current half.  First product / Gram: record row lr of the block, member 16 tm + 4 q + h; second
-    // product: record row 4 q + h, member 16 tj + lr.  Innovation and pad columns are not members (only the last block is ragged).
-    auto a_in = [&](int tm, int q) -> double {
-      const int mem = 16 * tm + 4 * q + h;
-      const bool ok = tm < KT - 1 || mem < k;
-      const double v = Ring[cur * 16 * KS + lr * KS + (ok ? mem : 0)];
-      return ok ? v : 0.0;
-    };
-    auto a_out = [&](int q, int tj) -> double {
-      const int mem = 16 * tj + lr;
-      const bool ok = tj < KT - 1 || mem < k;
-      const double v = Ring[cur * 16 * KS + (4 * q + h) * KS + (ok ? mem : 0)];
-      return ok ? v : 0.0;
-    };
-    // The A operands of four matrix instructions are read from LDS while the four before them run, and the scheduler is
-    // held to that order: left alone it reads a trip's 8 KT operands ahead of its first instruction, which the 40 KT
-    // registers of the recurrence vectors and the staged block leave no room for above 80 members.
-    // T (or Gram) block of the trip: steps (tm, q) ascending through ONE accumulator; b[tm][q] = the B operands
-    auto chain = [&](const auto& b) -> d4t {
-      d4t acc = {0., 0., 0., 0.};
-      double an[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) an[q] = a_in(0, q);
-#pragma unroll
-      for (int tm = 0; tm < KT; ++tm) {
-        double ac[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) ac[q] = an[q];
-        if (tm + 1 < KT) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) an[q] = a_in(tm + 1, q);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc = MIA_MFMA64(ac[q], b[tm][q], acc);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      return acc;
-    };
-    // y += Yw^T (s o .) over the block of the trip: the second product's steps (tb, q), B = the scaled block; step
-    // e = KT q + tj, four steps per group
-    auto fold = [&](const double (&s)[4], d4t (&y)[KT]) {
-      double an[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) an[i] = a_out(i / KT, i % KT);
-#pragma unroll
-      for (int g = 0; g < KT; ++g) {
-        double ac[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ac[i] = an[i];
-        if (g + 1 < KT) {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) an[i] = a_out((4 * g + 4 + i) / KT, (4 * g + 4 + i) % KT);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) y[(4 * g + i) % KT] = MIA_MFMA64(ac[i], s[(4 * g + i) / KT], y[(4 * g + i) % KT]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    };
-    // the end of a trip: the staged block into the other half, which becomes the current one
-    auto turn = [&](double& fin) {
-      commit(cur ^ 1, fin);
-      __syncthreads();
-      cur ^= 1;
-    };
     // ---- union of the lists of points [lo, hi): slot = RANK of the observation index, found by repeated extraction of
     //      the smallest remaining key (one sweep over the keys in LDS and one DPP reduction per slot); shrink the range
     //      until the union fits
@@ -388,8 +296,8 @@ __global__ __launch_bounds__(64, 1) void lienks_stream64_kernel(LienksStream64Pa
       }
       // ---- block 0 into the ring
       double fin = 0.0;
-      stage(0);
-      commit(cur, fin);
+      ring.stage(0);
+      ring.commit(cur, fin);
       __syncthreads();
       // ---- rhs_g = Yw^T (rho_g o d), once per tile (d = column k of the records); this first pass over the union also
       //      looks at every record (blocks 1 .. UB - 1 and block 0 again pass through commit)
@@ -400,17 +308,17 @@ __global__ __launch_bounds__(64, 1) void lienks_stream64_kernel(LienksStream64Pa
         int tb = 0;
 #pragma clang loop unroll(disable)
         do {
-          stage(tb + 1 < UB ? tb + 1 : 0);
+          ring.stage(tb + 1 < UB ? tb + 1 : 0);
           __builtin_amdgcn_sched_barrier(0);
-          const d4t Tb = chain(wmean);            // T = Yw w_mean: slot 4 q + h of the block in register q, column = point
+          const d4t Tb = ring.chain(wmean);            // T = Yw w_mean: slot 4 q + h of the block in register q, column = point
           double s[4];
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             const double dv = Dcol[16 * tb + 4 * q];
             s[q] = (dv * dv) * (Ring[cur * 16 * KS + (4 * q + h) * KS + k] * P.dshift + Tb[q]);
           }
-          fold(s, rhs);
-          turn(fin);
+          ring.fold(s, rhs);
+          ring.turn(fin);
         } while (++tb < UB);
       }
       // A non-finite record would reach EVERY column of the tile through the shared products (NaN * 0 = NaN), also the
@@ -450,15 +358,15 @@ __global__ __launch_bounds__(64, 1) void lienks_stream64_kernel(LienksStream64Pa
         int tk = 0;
 #pragma clang loop unroll(disable)
         do {
-          stage(tk + 1 < UB ? tk + 1 : 0);
+          ring.stage(tk + 1 < UB ? tk + 1 : 0);
           __builtin_amdgcn_sched_barrier(0);
-          const d4t Gb = chain(at);
+          const d4t Gb = ring.chain(at);
           double dk[4];
 #pragma unroll
           for (int q = 0; q < 4; ++q) dk[q] = Dcol[16 * tk + 4 * q];
 #pragma unroll
           for (int q = 0; q < 4; ++q) R = MIA_MFMA64(fabs(Gb[q]), dk[q], R);
-          turn(nofin);
+          ring.turn(nofin);
         } while (++tk < UB);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -488,11 +396,7 @@ __global__ __launch_bounds__(64, 1) void lienks_stream64_kernel(LienksStream64Pa
     }
     // (a column without observations has its W_in back already: it is not active and asks for no step)
     const int degmax = (int)tile64_wave_max_u32((colact && !decl) ? (unsigned)deg : 0u);
-    const double2* ctab = P.tab_c + (size_t)tab_idx * kTab64Deg;
-    auto coef = [&](int j) -> double2 {                              // (zero beyond a point's own degree)
-      const double2 c = ctab[j < kTab64Deg ? j : kTab64Deg - 1];
-      return double2{c.x * P.cs_phi, c.y * P.cs_psi};
-    };
+    const Coef64 coef{P.tab_c + (size_t)tab_idx * kTab64Deg, P.cs_phi, P.cs_psi};
 
 #pragma clang loop unroll(disable)
     for (int c = 0; c < k; ++c) {
@@ -508,42 +412,12 @@ __global__ __launch_bounds__(64, 1) void lienks_stream64_kernel(LienksStream64Pa
       for (int tm = 0; tm < KT; ++tm)
 #pragma unroll
         for (int q = 0; q < 4; ++q) va[tm][q] = (colact && 16 * tm + 4 * q + hv == c) ? 1.0 : 0.0;
-      // acc += sc C u = Yw^T (sc rho o (Yw u)), one sixteen-slot block of the union per trip; sc = alpha or 2 alpha of the
-      // column.  The caller has put the recurrence's other terms into acc: the step needs no vector of its own for C u,
-      // which at 128 members is the 64 registers that decide between spilling and not
-      auto product = [&](const d4t (&u)[KT], d4t (&acc)[KT], const double sc) {
-        int tb = 0;
-#pragma clang loop unroll(disable)
-        do {
-          stage(tb + 1 < UB ? tb + 1 : 0);
-          __builtin_amdgcn_sched_barrier(0);
-          const d4t Tb = chain(u);
-          double s[4];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const double dv = Dcol[16 * tb + 4 * q];
-            s[q] = (sc * (dv * dv)) * Tb[q];
-          }
-          fold(s, acc);
-          turn(nofin);
-        } while (++tb < UB);
-      };
-      // vnew = 2 alpha C vcur - 2 vcur - vold, accumulated over vold; the two functions accumulate c_j vnew
-      auto advance = [&](d4t (&vold)[KT], const d4t (&vcur)[KT], const double2 cj) {
-#pragma unroll
-        for (int t = 0; t < KT; ++t) vold[t] = -2.0 * vcur[t] - vold[t];
-        product(vcur, vold, 2.0 * alpha);
-#pragma unroll
-        for (int t = 0; t < KT; ++t) {
-          aphi[t] = cj.x * vold[t] + aphi[t];
-          apsi[t] = cj.y * vold[t] + apsi[t];
-        }
-      };
+      const Recur64<KT> step{ring, Dcol, UB, nofin, alpha, aphi, apsi};     // product / advance of the recurrence
       {
         const double2 c0 = coef(0), c1 = coef(1);
 #pragma unroll
         for (int t = 0; t < KT; ++t) vb[t] = -va[t];
-        product(va, vb, alpha);                 // vb = v_1 = alpha C v_0 - v_0
+        step.product(va, vb, alpha);                 // vb = v_1 = alpha C v_0 - v_0
 #pragma unroll
         for (int t = 0; t < KT; ++t) {
           aphi[t] = c0.x * va[t] + c1.x * vb[t];
@@ -555,11 +429,11 @@ __global__ __launch_bounds__(64, 1) void lienks_stream64_kernel(LienksStream64Pa
 #pragma clang loop unroll(disable)
       for (; j + 1 <= degmax; j += 2) {
         const double2 nj = coef(j + 2), nj1 = coef(j + 3);       // requested one trip ahead
-        advance(va, vb, cj);          // va = v_j
-        advance(vb, va, cj1);         // vb = v_{j+1}
+        step.advance(va, vb, cj);          // va = v_j
+        step.advance(vb, va, cj1);         // vb = v_{j+1}
         cj = nj; cj1 = nj1;
       }
-      if (j <= degmax) advance(va, vb, cj);
+      if (j <= degmax) step.advance(va, vb, cj);
       // ---- wm_c = (psi(C) e_c) . rhs / reg: members in the lane's registers first, then the four lane groups
       double zs = 0.0;
 #pragma unroll
