@@ -889,6 +889,35 @@ int mia_lienks_update_stream_f64(const double* W_in, int64_t w_stride, int k, in
                                  const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
                                  double epsilon, double* W_out, int32_t* flags, int32_t* retry_count, void* stream);
 int mia_lienks_update_stream_f64_cover(int k, int p_max, int64_t n_points, int64_t P);
+/* mia_lienks_update_stream_f64 with the sixteen points of a tile taken from a MAP (csrc/lienks_patch64.hip): the same kernel
+ * body -- union by rank, the ring, the row means of W_in and the shift, rhs, streamed Gershgorin bound, primal table, degree,
+ * decline, bundle scaling, the prior test of the transform variant, one pass per member -- with mia_letkf_weights_patch_f64's
+ * changes to the frame.  tile_pts [n_tiles][16] int32: the point of slot s of tile t as an index into [0, g1 - g0), or -1 for
+ * an empty slot; every point of the range must occur exactly once (mia_letkf_tile_union_census checks it; this entry trusts
+ * the map except that an entry outside the range is treated as empty).  Through the map go a point's list row, count, flag,
+ * its k x k block of W_out and its block of W_in (row means, prior test, the bit-for-bit copy-back of a point without
+ * observations); with w_stride = 0 W_in is ONE matrix and is not mapped.  union_blocks: sixteen-slot blocks of the sqrt(rho)
+ * and slot tables in LDS, 1 .. 16 at every ensemble size; a tile whose union exceeds it runs in halves of its slots, a single
+ * list longer than 16 union_blocks, p_max or p_cap is MIA_FLAG_OVERFLOW and NaN weights for that point only.  Every lane
+ * writes its point's block through a 64-bit base of its own, so a tile's points may lie anywhere in W_out.  Lists, flags and
+ * W stay in natural point order: declined points are redone by mia_lienks_update_retry_f64 unchanged, with the data-dependent
+ * MIA_ERR_UNSUPPORTED of that kernel.  W_out and flags are mia_lienks_update_stream_f64's bit for bit under any map.
+ * Argument list: mia_lienks_update_stream_f64's with tile_pts, n_tiles, union_blocks in front of stream.  Validation before
+ * any launch, nothing dereferenced, in this order: sizes (g1 < g0, g0 < 0, k < 2, P < 0, p_cap < 1, p_max < 0, n_tiles < 0:
+ * MIA_ERR_SIZE), w_stride other than 0 or k*k (MIA_ERR_SIZE), empty shard (MIA_OK), NULL pointers with tile_pts among them
+ * (MIA_ERR_NULL), NULL records with P > 0 (MIA_ERR_NULL), n_tiles == 0 for a non-empty range (MIA_ERR_SIZE), p_max cut to
+ * p_cap; then MIA_ERR_UNSUPPORTED for the option "tile" = 0, p_max <= k, p_max > 256, k outside 2 .. 128, union_blocks outside
+ * 1 .. 16, more tiles than a launch grid (65 536 x 65 535) and a coefficient table that cannot be had (stream being captured).
+ * The kernel's name is reported through mia_last_analysis_kernel.
+ * mia_lienks_update_patch_f64_cover: mia_letkf_weights_patch_f64_cover's arithmetic (2 <= k <= 128, k < p_max <= 256,
+ * 0 <= n_points < 2^31 for the int32 map entries, k^2 8 < 2^31 for the 32-bit offset inside a point's weights, the LDS of
+ * the largest image, P >= 0), host only, no device work. */
+int mia_lienks_update_patch_f64(const double* W_in, int64_t w_stride, int k, int64_t g0, int64_t g1,
+                                const double* rec, int64_t P,
+                                const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                                double epsilon, double* W_out, int32_t* flags, int32_t* retry_count,
+                                const int32_t* tile_pts, int64_t n_tiles, int union_blocks, void* stream);
+int mia_lienks_update_patch_f64_cover(int k, int p_max, int64_t n_points, int64_t P);
 
 /* ------------------------------------------------------------------------------------
  * Observation-space preparation, the step immediately upstream of the analysis

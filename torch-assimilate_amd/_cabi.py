@@ -155,6 +155,8 @@ _PROTOS = {
     "mia_lienks_update_wide_f64_cover": _COVER4,
     "mia_lienks_update_stream_f64": _ienks_tile_entry(f64),
     "mia_lienks_update_stream_f64_cover": _COVER4,
+    "mia_lienks_update_patch_f64": (_ienks_tile_entry(f64)[0][:-1] + [vp, i64, i32, vp], i32),      # ..., tile_pts, n_tiles, union_blocks, stream
+    "mia_lienks_update_patch_f64_cover": _COVER4,
     "mia_obs_space_uncorr_f32": ([vp, i64, vp, vp, i32, i64, vp, i64, vp, vp, vp], i32),
     "mia_obs_space_uncorr_f64": ([vp, i64, vp, vp, i32, i64, vp, i64, vp, vp, vp], i32),
     "mia_obs_space_corr_workspace_bytes": ([i32, i64, i32, C.POINTER(sz)], i32),

@@ -399,17 +399,22 @@ static int apply_local_weights_impl(const T* X, int64_t ldx, int m, int k, int64
 
 // What an entry of an IEnKS tile route checks before its launch, in this order: sizes, the weight stride, empty shard, NULL
 // pointers, NULL records, clamp of p_max -- nothing is dereferenced.  kLaunch (no status: those are <= 0): the entry goes on
-// to its launch, with *p_max clamped to p_cap; anything else is what the entry returns.
+// to its launch, with *p_max clamped to p_cap; anything else is what the entry returns.  The route under a tile map
+// (mia_lienks_update_patch_f64) has n_tiles among the sizes (< 0), the map among the pointers, and n_tiles == 0 for a
+// non-empty range as a size error behind the pointers, as tile_entry_checks has them (letkf_entry.hip)
 constexpr int kLaunch = 1;
+static const char kNoTileMap = 0;
 template <typename T>
 static int ienks_tile_entry_checks(const T* W_in, int64_t w_stride, int k, int64_t g0, int64_t g1, const T* rec, int64_t P,
                                    const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int* p_max,
-                                   const T* W_out, const int32_t* flags, const int32_t* retry_count) {
-  if (g1 < g0 || g0 < 0 || k < 2 || P < 0 || p_cap < 1 || *p_max < 0) return MIA_ERR_SIZE;
+                                   const T* W_out, const int32_t* flags, const int32_t* retry_count,
+                                   const void* tile_pts = &kNoTileMap, int64_t n_tiles = 1) {
+  if (g1 < g0 || g0 < 0 || k < 2 || P < 0 || p_cap < 1 || *p_max < 0 || n_tiles < 0) return MIA_ERR_SIZE;
   if (w_stride != 0 && w_stride != (int64_t)k * k) return MIA_ERR_SIZE;
   if (g1 == g0) return MIA_OK;
-  if (!W_in || !W_out || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count) return MIA_ERR_NULL;
+  if (!W_in || !W_out || !nbr_cnt || !nbr_idx || !nbr_w || !flags || !retry_count || !tile_pts) return MIA_ERR_NULL;
   if (P > 0 && !rec) return MIA_ERR_NULL;
+  if (n_tiles == 0) return MIA_ERR_SIZE;
   if (*p_max > p_cap) *p_max = p_cap;
   return kLaunch;
 }
@@ -518,6 +523,25 @@ extern "C" int mia_lienks_update_stream_f64(const double* W_in, int64_t w_stride
 extern "C" int mia_lienks_update_stream_f64_cover(int k, int p_max, int64_t n_points, int64_t P) {
   if (P < 0) return 0;
   return lienks_stream64_route_covers(k, p_max, n_points) ? 1 : 0;
+}
+// lienks_stream64.hip's update with a tile map and caller-sized slot tables (lienks_patch64.hip): the same checks with the map's
+// arguments among the sizes and pointers, then the option, the cover, union_blocks and the grid (the launch's answers,
+// MIA_ERR_UNSUPPORTED), then the one kernel of the route
+extern "C" int mia_lienks_update_patch_f64(const double* W_in, int64_t w_stride, int k, int64_t g0, int64_t g1,
+                                           const double* rec, int64_t P, const int32_t* nbr_cnt, const int32_t* nbr_idx,
+                                           const double* nbr_w, int p_cap, int p_max, double epsilon, double* W_out,
+                                           int32_t* flags, int32_t* retry_count, const int32_t* tile_pts, int64_t n_tiles,
+                                           int union_blocks, void* stream) {
+  (void)hipGetLastError();
+  const int rc = ienks_tile_entry_checks(W_in, w_stride, k, g0, g1, rec, P, nbr_cnt, nbr_idx, nbr_w, p_cap, &p_max, W_out, flags,
+                                         retry_count, tile_pts, n_tiles);
+  if (rc != kLaunch) return rc;
+  return lienks_patch64_launch(W_in, w_stride, k, g1 - g0, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, epsilon, W_out, flags,
+                               retry_count, tile_pts, n_tiles, union_blocks, (hipStream_t)stream);
+}
+extern "C" int mia_lienks_update_patch_f64_cover(int k, int p_max, int64_t n_points, int64_t P) {
+  if (P < 0) return 0;
+  return lienks_patch64_route_covers(k, p_max, n_points) ? 1 : 0;
 }
 extern "C" int mia_apply_local_weights_f32(const float* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
                                            const float* W, float* Xa, int64_t ldo, int64_t o0, void* stream) {

@@ -1,49 +1,39 @@
-// The localised IEnKS weight update with tau = 1 in FLOAT64 for DENSE local networks (p_max > k) of ensembles up to 128
-// members, sixteen grid points per wavefront, every contraction on the matrix cores (v_mfma_f64_16x16x4_f64), without an
-// eigensolver: what IEnKSTransformModule / IEnKSBundleModule.forward (core/ienks.py:108-141, 167-173) return on the localised
-// block under LocalizedIEnKS*.inner_loop (interface/lienks.py:75-118), where a point sees more observations than there are
-// members.  With tau = 1, reg = k - 1, D = Yl (transform variant, while Wp = I) or D = Yl / eps (bundle
-// variant) and C = D D^T (k x k), core/ienks.py:108-126 in primal form is
+// lienks_stream64.hip's IEnKS weight UPDATE (tau = 1, FLOAT64, dense local networks p_max > k, ensembles up to 128 members,
+// sixteen grid points per wavefront, every contraction a v_mfma_f64_16x16x4_f64, the union's records streamed through a ring of
+// two sixteen-slot blocks) with letkf_patch64w.hip's three changes to the FRAME; mathematics, lane roles,
+// summation order, the ring and its stage / chain / fold / turn discipline and the run-time loops are the ring family's
+// (csrc/mia_ring64_dev.h, shared), the row means, the rhs pass with the shift D^T w_mean, the streamed bound, table, decline,
+// the bundle scaling and the prior test of the transform variant lienks_stream64.hip's (reference:
+// core/ienks.py:108-141, 167-173 under interface/lienks.py:75-118) and are not restated here.
 //
-//     Wp'     = phi(C),                    phi(t) = 1 / sqrt(1 + t / reg)
-//     w_mean' = psi(C) rhs / reg,          psi(t) = 1 / (1 + t / reg),      rhs = D (d_l + D^T w_mean)
-//     W'      = w_mean' 1^T + Wp',         w_mean_i = (sum_j W_in[i][j] - 1) / k
+// 1. TILE MAP.  The sixteen points of tile t are tile_pts[16 t + s], s = 0 .. 15: indices into the launch's range [0, ng),
+//    -1 = empty slot.  On a row-major 2-D mesh sixteen CONSECUTIVE points are a 16 x 1 strip whose lists have a union of 200
+//    observations at radius 3 against 176 of a 4 x 4 patch: the strip runs in parts, the patch in one pass.  Through the map
+//    go the list row, the count, the flag, the point's k x k block of W_out -- and the point's block of W_IN, which the
+//    weights twin does not have: the row means, the prior test of the transform variant and the copy-back of a point without
+//    observations (bit for bit, by the whole wavefront) read W_in + tile_pts[slot] w_stride; with w_stride = 0 there is ONE
+//    shared matrix and no map on it.  Live slots need not be a prefix: a dead slot is clamped to the tile's first live point
+//    for loads, takes no part (its bit of skipmask is set from the start) and every store is predicated.  The range loop
+//    runs over SLOTS, starts a range at a live slot and ends at the last live one.  A tile without a live slot returns
+//    before the union, as does a tile whose live points all lack observations, after their copy-back; an entry outside
+//    [0, ng) is an empty slot.  Lists and flags stay in natural point order, so the redo of declined points
+//    (mia_lienks_update_retry_f64) needs no map.
+// 2. IMAGE SIZED BY THE CALLER.  `ub` sixteen-slot blocks of the sqrt(rho) table and the slot table, 1 <= ub <= 16 at every
+//    ensemble size (the records are not resident); the caller has it from tile_union_census_kernel (letkf_patch64.hip).  A tile
+//    whose union exceeds it runs in halves of its SLOTS, quarters, ...; a single list longer than the image, p_max or p_cap is
+//    MIA_FLAG_OVERFLOW and NaN weights, never a truncated list.
+// 3. THE STORES.  lienks_stream64.hip addresses W_out as a wave-uniform base (the tile's first point, row c) + a 32-bit lane
+//    offset point k^2 8 + j 8, which needs a tile's points to be consecutive.  Under a map they lie anywhere in n k^2 8 bytes (more
+//    than 2^31 at 1e5 points): every lane owns one column = one point, so it forms a 64-bit base W_out + tile_pts[slot] k^2 (once
+//    per member pass, behind the recurrence: see there) and keeps the 32-bit part to c k 8 + j 8 < k^2 8 <= 2^17.  The per-point reads of W_in were wave-uniform per
+//    point already (a 64-bit scalar base + a 32-bit lane offset inside the matrix): they take the point from the map.
 //
-// i.e. the LETKF weights at inflation 1 with the innovations shifted by D^T w_mean.
+// A point's observations are summed in ascending index order with exact zeros in between whatever else is in the tile, and its
+// row means depend on its own matrix alone, so W and flags are lienks_stream64_kernel's bit for bit under any map
+// (tests/test_gpu_ienks_patch64.py).
 //
-// The frame is letkf_stream64w.hip's, block for block: per-point lists of any metric, union by rank
-// extraction, the union's records streamed through a ring of two sixteen-slot blocks in LDS with its stage / chain / fold /
-// turn discipline (csrc/mia_ring64_dev.h, shared), rhs in LDS, the streamed Gershgorin bound, the primal table with its
-// degree, decline and MIA_FLAG_RETRY count, halving of oversized tiles, the point-by-point pass after a non-finite record,
-// MIA_FLAG_OVERFLOW with NaN into the point's block, the XCD tile map, one pass of the recurrence per MEMBER c < k on e_c,
-// the stores (64-bit wave-uniform base plus 32-bit lane offset).  With
-// C_g = Yw^T diag(rho_g [/ eps^2]) Yw:
-//
-//     W'[g][c][j] = wm_c + (phi(C_g) e_c)_j,        wm_c = (psi(C_g) e_c) . rhs_g / reg
-//
-// Lane roles follow v_mfma_f64_16x16x4_f64 as in letkf_tile64.hip: lane (lr, h) = (lane & 15, lane >> 4) supplies A[lr][h]
-// and B[h][lr]; of a result block it holds column lr (= grid point lr), rows h + 4 r in register r.  A k-vector of the
-// sixteen points is KT result blocks (member 16 tm + h + 4 r in register r): register q of block tm IS the B operand of
-// step (tm, q) of the first product, the scaled block of T the B operand of steps (tb, q) of the second.  Summation order
-// is canonical: slot = RANK of the observation index inside the union, blocks and steps ascend, every sum over the union is
-// ONE chain of matrix instructions through its accumulator, so a point's bits depend on neither tile nor shard.  The ring
-// and the rules of the run-time loops (builtins only) are described in mia_ring64_dev.h.
-//
-// What differs is lienks_wide64.hip's, placed into this frame:
-//
-//     w_mean   per point (or once, for ONE shared matrix: w_stride = 0), in lienks64_row_means' order: lane lr adds columns
-//              lr, lr + 16, ..., then a butterfly over the sixteen lanes of a row -- an order that depends on (i, j) alone.
-//              It lands in the k-vector layout above (4 KT registers, live through the rhs pass only)
-//     rhs      one trip of the file's own product pair with the start vector w_mean: T = Yw w_mean is the first thin
-//              product on the staged block, s = rho [/ eps^2] (d dshift + T) per slot (dshift = 1, or eps for the bundle
-//              variant), then the fold.  T comes out in the layout s needs: slot 4 q + h in register q, column = point
-//     sqrt(rho) enters Dl as sqrt(rho) / eps (bundle): bound, table row and degree are those of the scaled C
-//
-// A point without observations gets its W_in back bit for bit, flag 0 (core/ienks.py:135), copied by the whole wavefront,
-// and takes no part in the tile; a tile without an active point returns before the union.  Transform variant: a point with
-// observations whose Wp is not the identity (kStreamPriorTol below) is declined whole like a point whose degree exceeds the
-// table's cap: MIA_FLAG_RETRY, counted once, W_out untouched; the general kernel redoes them (mia_lienks_update_retry_f64)
-// where it holds the shape.
+// The kernel keeps its own text for everything the map reaches (DESIGN 2.18 on letkf_patch64.hip: the map reaches every
+// address the frame forms); what it does not reach is mia_ring64_dev.h's and mia_lienks_stream64_dev.h's.
 #include "mia_cheb_table64.h"
 #include "mia_frames64.h"
 #include "mia_lienks_stream64_dev.h"
@@ -52,15 +42,14 @@
 
 namespace mia {
 
-// (the row means and the prior test of a point's incoming weights, with kStreamPriorTol: mia_lienks_stream64_dev.h, shared
-// with lienks_patch64.hip)
-struct LienksStream64Params {
+struct LienksPatch64Params {
   int k; int kp;
   int64_t ng;
   const double* Win; int64_t w_stride;     // [ng][k][k], or one [k][k] for all points when w_stride == 0
   const double* rec;
   const int32_t* cnt; const int32_t* idx; const double* w; int p_cap; int p_max;
-  int ub;                                                    // sixteen-slot blocks of the slot table of the launch
+  const int32_t* tile_pts; int64_t n_tiles;                  // [n_tiles][16] point of a slot, -1 = none
+  int ub;                                                    // sixteen-slot blocks of the slot table of the launch: the caller's
   int transform;                           // 1: transform variant (D = Yl while Wp = I), 0: bundle variant (D = Yl / eps)
   double dscale, dshift;                   // 1 / eps and eps (bundle), 1 and 1 (transform)
   double reg, inv_reg, cs_phi, cs_psi;
@@ -71,7 +60,7 @@ struct LienksStream64Params {
 
 // KT = ceil(k / 16).  One wavefront per workgroup; its LDS bounds how many share a compute unit.
 template <int KT>
-__global__ __launch_bounds__(64, 1) void lienks_stream64_kernel(LienksStream64Params P) {
+__global__ __launch_bounds__(64, 1) void lienks_patch64_kernel(LienksPatch64Params P) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int lane = threadIdx.x;
   const int k = P.k, kp = P.kp, pm = P.p_max;
@@ -84,54 +73,67 @@ __global__ __launch_bounds__(64, 1) void lienks_stream64_kernel(LienksStream64Pa
   unsigned* Kl = reinterpret_cast<unsigned*>(Dl);            // [16][nl]    index + 1 of the lists' entries while the union is formed
 
   const int64_t bid = (int64_t)blockIdx.y * gridDim.x + blockIdx.x;
-  const int64_t ntile = (P.ng + 15) >> 4;
+  const int64_t ntile = P.n_tiles;
   if (bid >= ntile) return;
   const int64_t tile = ring64_tile_of_block(bid, ntile);
-  const int64_t p0 = tile << 4;                              // first point of the tile (index into the launch's ng points)
-  const int npts = P.ng - p0 < 16 ? (int)(P.ng - p0) : 16;
   const int lr = lane & 15, h = lane >> 4, lp = lane >> 2, sub = lane & 3;
-  const unsigned kk8 = (unsigned)(k * k) * 8u;               // bytes of one point's weights
+  const int64_t kk = (int64_t)(k * k);                       // doubles of one point's weights
 
-  // ---- the tile's neighbour lists stay in memory: lane (lp, sub) walks entries sub, sub + 4, ... of point lp
+  // ---- the tile's points: slot lr is this lane's column, slot lp the list it walks.  An entry outside [0, ng) is an empty
+  //      slot (the census refuses such a map; nothing is ever indexed by one)
+  const int32_t* tp = P.tile_pts + tile * 16;
+  int ptc = tp[lr], ptl = tp[lp];
+  ptc = (ptc >= 0 && ptc < P.ng) ? ptc : -1;
+  ptl = (ptl >= 0 && ptl < P.ng) ? ptl : -1;
+  const unsigned livemask = (unsigned)(__ballot(ptc >= 0) & 0xffffull);       // (lanes 0 .. 15 are slots 0 .. 15)
+  if (livemask == 0u) return;
+  const int nslot = 32 - __builtin_clz(livemask);             // one past the last live slot
+  const int pfirst = tp[__builtin_ctz(livemask)];             // a point that exists: what dead slots load from
+  const bool live_c = ptc >= 0, live_l = ptl >= 0;
+  const int colpt = live_c ? ptc : pfirst;                    // (from here on the column's point: ptc is not used again)
+
+  // ---- the tile's neighbour lists stay in memory: lane (lp, sub) walks entries sub, sub + 4, ... of slot lp's point
   int nl = pm < P.p_cap ? pm : P.p_cap;
   nl = nl < UMAX ? nl : UMAX;
-  const int64_t lrow = p0 + (lp < npts ? lp : 0);            // (lists, flags and weights count from the shard's g0)
+  const int64_t lrow = live_l ? ptl : pfirst;                // (lists, flags and weights count from the shard's g0)
   const int32_t* ib = P.idx + lrow * P.p_cap;
   const double* wb = P.w + lrow * P.p_cap;
   int lcnt = P.cnt[lrow];
   const bool shared_w = P.w_stride == 0;
-  unsigned long long skipmask;       // bit 4 p: point p takes no part in the tile (overflow, no observation, declined here)
+  unsigned long long skipmask;       // bit 4 s: slot s takes no part in the tile (dead, overflow, no observation, declined here)
   {
-    const bool pbad = lp < npts && (lcnt > pm || lcnt > P.p_cap || lcnt > UMAX);   // loud failure, never truncate
+    const bool pbad = live_l && (lcnt > pm || lcnt > P.p_cap || lcnt > UMAX);   // loud failure, never truncate
     if (pbad) {
-      if (sub == 0) P.flags[p0 + lp] = MIA_FLAG_OVERFLOW;
+      if (sub == 0) P.flags[ptl] = MIA_FLAG_OVERFLOW;
       const double nanv = __builtin_nan("");
-      double* wp = P.W + (p0 + lp) * (int64_t)(k * k);
+      double* wp = P.W + (int64_t)ptl * kk;
       for (int it = sub; it < k * k; it += 4) wp[it] = nanv;
     }
-    if (lp >= npts || pbad) lcnt = 0;
+    if (!live_l || pbad) lcnt = 0;
     // ---- no local observation: the weights go back as they came (core/ienks.py:135), the whole wavefront copying a point
-    const unsigned long long emask = __ballot(lp < npts && !pbad && lcnt == 0);
-    skipmask = __ballot(pbad) | emask;
-    for (int pt = 0; pt < npts; ++pt) {
-      if (!((emask >> (4 * pt)) & 1ull)) continue;
-      const double* win = P.Win + (p0 + pt) * P.w_stride;
-      double* wout = P.W + (p0 + pt) * (int64_t)(k * k);
+    const unsigned long long emask = __ballot(live_l && !pbad && lcnt == 0);
+    skipmask = __ballot(pbad || !live_l) | emask;
+    for (int s = 0; s < nslot; ++s) {
+      if (!((emask >> (4 * s)) & 1ull)) continue;
+      const int64_t pt = tp[s];                              // (a live slot: wave-uniform, inside [0, ng))
+      const double* win = P.Win + pt * P.w_stride;
+      double* wout = P.W + pt * kk;
       for (int it = lane; it < k * k; it += 64) wout[it] = win[it];
-      if (lane == 0) P.flags[p0 + pt] = 0;
+      if (lane == 0) P.flags[pt] = 0;
     }
     // ---- transform variant: D = Wp^-1 Yl is Yl only at the prior; any other point with observations is the general kernel's
     if (P.transform) {
-      unsigned np = 0u;                                      // bit p: point p is not at the prior
-      const int nscan = shared_w ? 1 : npts;
-      for (int pt = 0; pt < nscan; ++pt) {
-        if (!shared_w && ((skipmask >> (4 * pt)) & 1ull)) continue;
-        const double dev = lienks_stream64_prior_dev<KT>(P.Win + (p0 + pt) * P.w_stride, k, lr, h);
-        if (__any(!(dev <= kStreamPriorTol))) np |= shared_w ? 0xffffu : (1u << pt);
+      unsigned np = 0u;                                      // bit s: slot s' point is not at the prior
+      const int nscan = shared_w ? 1 : nslot;
+      for (int s = 0; s < nscan; ++s) {
+        if (!shared_w && ((skipmask >> (4 * s)) & 1ull)) continue;
+        const int64_t pt = shared_w ? 0 : tp[s];             // (one shared matrix: no map on W_in)
+        const double dev = lienks_stream64_prior_dev<KT>(P.Win + pt * P.w_stride, k, lr, h);
+        if (__any(!(dev <= kStreamPriorTol))) np |= shared_w ? 0xffffu : (1u << s);
       }
-      const bool pnot = lp < npts && lcnt > 0 && ((np >> lp) & 1u);
+      const bool pnot = live_l && lcnt > 0 && ((np >> lp) & 1u);
       if (pnot && sub == 0) {
-        P.flags[p0 + lp] = MIA_FLAG_RETRY;
+        P.flags[ptl] = MIA_FLAG_RETRY;
         atomicAdd(P.retry_count, 1);
       }
       if (pnot) lcnt = 0;
@@ -149,17 +151,18 @@ __global__ __launch_bounds__(64, 1) void lienks_stream64_kernel(LienksStream64Pa
   int lo = 0;
   bool single = false;                                       // a non-finite record was met: the rest of the tile goes point by point
 #pragma clang loop unroll(disable)
-  while (lo < npts) {
-    const bool colok = lr < npts && !((skipmask >> (4 * lr)) & 1ull);
+  while (lo < nslot) {
+    if (!((livemask >> lo) & 1u)) { ++lo; continue; }        // a range starts at a live slot, so it is never empty
+    const bool colok = live_c && !((skipmask >> (4 * lr)) & 1ull);
     const double* Dcol = Dl + lr * DS + h;                    // + 16 t + 4 r: slot 16 t + h + 4 r of column lr
-    // ---- union of the lists of points [lo, hi): slot = RANK of the observation index, found by repeated extraction of
+    // ---- union of the lists of slots [lo, hi): slot of the union = RANK of the observation index, found by repeated extraction of
     //      the smallest remaining key (one sweep over the keys in LDS and one DPP reduction per slot); shrink the range
     //      until the union fits
     int n = single ? 1 : 16, hi, U;
     bool act;
     for (;;) {
-      hi = lo + n < npts ? lo + n : npts;
-      act = lp >= lo && lp < hi;
+      hi = lo + n < nslot ? lo + n : nslot;
+      act = lp >= lo && lp < hi && live_l;
       for (int pos = sub; pos < nl; pos += 4) {
         int e = -1;
         if (act && pos < lcnt) e = ib[pos];
@@ -211,12 +214,13 @@ __global__ __launch_bounds__(64, 1) void lienks_stream64_kernel(LienksStream64Pa
         d4t wm4 = {0., 0., 0., 0.};
         const int nscan = shared_w ? 1 : hi;
 #pragma clang loop unroll(disable)
-        for (int pt = shared_w ? 0 : lo; pt < nscan; ++pt) {
-          if (!shared_w && ((skipmask >> (4 * pt)) & 1ull)) continue;
+        for (int s = shared_w ? 0 : lo; s < nscan; ++s) {
+          if (!shared_w && ((skipmask >> (4 * s)) & 1ull)) continue;
           // (lo and hi come out of the union's wave reductions: the same in every lane, but only this tells the compiler so,
-          //  and with it that the matrix' address is a scalar)
-          const int ptu = __builtin_amdgcn_readfirstlane(pt);
-          lienks_stream64_row_means<KT>(P.Win + (p0 + ptu) * P.w_stride, k, tm, lr, h, shared_w || lr == pt, wm4);
+          //  and with it that the map's entry and the matrix' address are scalars)
+          const int su = __builtin_amdgcn_readfirstlane(s);
+          const int64_t pt = shared_w ? 0 : tp[su];
+          lienks_stream64_row_means<KT>(P.Win + pt * P.w_stride, k, tm, lr, h, shared_w || lr == s, wm4);
         }
         wmean[tm] = wm4;
       }
@@ -316,7 +320,7 @@ __global__ __launch_bounds__(64, 1) void lienks_stream64_kernel(LienksStream64Pa
       decl = colact && (deg > P.dmax || deg > kTab64Deg - 1);
       alpha = (deg > kTab64Deg - 1) ? 0.0 : hd.two_over_T * P.inv_reg;             // (a declined column carries bounded junk)
       if (decl && h == 0) {
-        P.flags[p0 + lr] = MIA_FLAG_RETRY;
+        P.flags[colpt] = MIA_FLAG_RETRY;                       // (colact: the slot is live, colpt is its point)
         atomicAdd(P.retry_count, 1);
       }
     }
@@ -329,8 +333,8 @@ __global__ __launch_bounds__(64, 1) void lienks_stream64_kernel(LienksStream64Pa
       // (lane roles through opaque copies, as in letkf_tile64.hip: what is invariant in this loop -- the member numbers of the
       // start vector, the 4 KT offsets of the output, their predicates -- would otherwise be hoisted and held in registers
       // across the recurrence, which has none to spare)
-      int hv = h, lrv = lr;
-      asm volatile("" : "+v"(hv), "+v"(lrv));
+      int hv = h, cpv = colpt;
+      asm volatile("" : "+v"(hv), "+v"(cpv));
       d4t va[KT], vb[KT], aphi[KT], apsi[KT];
       // ---- the recurrence on the 16 columns at once: v_0 = e_c on live columns (member c < k always exists), v_1 = alpha C v_0 - v_0,
       //      v_{j+1} = 2 (alpha C v_j - v_j) - v_{j-1}
@@ -367,9 +371,12 @@ __global__ __launch_bounds__(64, 1) void lienks_stream64_kernel(LienksStream64Pa
 #pragma unroll
         for (int r = 0; r < 4; ++r) zs = fma(apsi[tm][r], Rl[(4 * tm + r) * 64 + lane], zs);
       const double wm = tile64_add_h(zs);
-      // row c of the sixteen points' weights: wave-uniform 64-bit base (tile, row c) + 32-bit lane offset (point lr, column j)
-      char* obase = reinterpret_cast<char*>(P.W + (p0 * k + c) * (int64_t)k);
-      const unsigned olane = (unsigned)lrv * kk8 + (unsigned)hv * 8u;
+      // row c of the sixteen points' weights: the lane's 64-bit base (its point) + 32-bit offset (row c, column j) < k^2 8.
+      // This lane's column is one point (a dead slot: the tile's first live point, never stored to); the base of its k x k
+      // block is formed here, behind the recurrence, from the point's index: ONE register lives across the recurrence, not the
+      // base's two, which KT = 8 does not have (256 + 256 registers and four spills with the base formed once per range)
+      char* obase = reinterpret_cast<char*>(P.W + (int64_t)cpv * kk);
+      const unsigned olane = (unsigned)(c * k) * 8u + (unsigned)hv * 8u;
       const bool wr = colact && !decl;
 #pragma unroll
       for (int tj = 0; tj < KT; ++tj)
@@ -385,7 +392,7 @@ __global__ __launch_bounds__(64, 1) void lienks_stream64_kernel(LienksStream64Pa
       if (!(colact && !decl)) pflag = 0;          // (columns that are not written do not report)
       const unsigned long long fb = __ballot(pflag != 0);
       const bool anyf = ((fb >> lr) & 0x0001000100010001ull) != 0ull;
-      if (h == 0 && colact && !decl) P.flags[p0 + lr] = (anyf ? MIA_FLAG_NONFINITE : 0) | (deg << 8);
+      if (h == 0 && colact && !decl) P.flags[colpt] = (anyf ? MIA_FLAG_NONFINITE : 0) | (deg << 8);
     }
     lo = hi;
     __syncthreads();
@@ -393,42 +400,46 @@ __global__ __launch_bounds__(64, 1) void lienks_stream64_kernel(LienksStream64Pa
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------------
-constexpr int kLienksStream64MaxK = 128;
+constexpr int kLienksPatch64MaxBlocks = kRing64MaxBlocks;       // union_blocks of the caller: 256 slots, at every ensemble size of the route
+constexpr int kLienksPatch64MaxK = 128;
 
-// weights_stream64_route_covers' arithmetic
-bool lienks_stream64_route_covers(int k, int p_max, int64_t ng) {
-  if (k < 2 || k > kLienksStream64MaxK || p_max <= k || ng < 0) return false;           // p_max <= k: the dual routes
-  if (p_max > 16 * kRing64MaxBlocks) return false;
-  // a pass addresses W as wave-uniform base (tile, row) + 32-bit byte offset inside the tile's sixteen matrices
-  if ((int64_t)16 * k * k * 8 >= ((int64_t)1 << 31)) return false;
-  if (ring64_lds_bytes(ring64_blocks(p_max), k) > kMaxDynamicLds) return false;
-  return grid_covers((ng + 15) >> 4);
+// weights_patch64_route_covers' arithmetic
+bool lienks_patch64_route_covers(int k, int p_max, int64_t ng) {
+  if (k < 2 || k > kLienksPatch64MaxK || p_max <= k || ng < 0) return false;            // p_max <= k: the dual routes
+  if (p_max > 16 * kLienksPatch64MaxBlocks) return false;
+  // a lane addresses W_out as its point's 64-bit base + a 32-bit byte offset inside that point's k x k block; map entries are int32
+  if ((int64_t)k * k * 8 >= ((int64_t)1 << 31) || ng >= ((int64_t)1 << 31)) return false;
+  if (ring64_lds_bytes(kLienksPatch64MaxBlocks, k) > kMaxDynamicLds) return false;   // (the largest image; holds at every k: tests/test_ienks_patch64_cover.py)
+  return true;
 }
 
 // launches with the sizes of the ring frame (mia_frames64.h)
 template <int KT>
-static int lienks_stream64_launch_t(const LienksStream64Params& dp, hipStream_t stream) {
-  return launch_blocks(lienks_stream64_kernel<KT>, (dp.ng + 15) >> 4, 64, ring64_lds_bytes(dp.ub, dp.k), stream,
-                       [] { note_analysis_kernel("lienks_stream64_kernel<%d>", KT); }, dp);
+static int lienks_patch64_launch_t(const LienksPatch64Params& dp, hipStream_t stream) {
+  return launch_blocks(lienks_patch64_kernel<KT>, dp.n_tiles, 64, ring64_lds_bytes(dp.ub, dp.k), stream,
+                       [] { note_analysis_kernel("lienks_patch64_kernel<%d>", KT); }, dp);
 }
 
-int lienks_stream64_launch(const double* W_in, int64_t w_stride, int k, int64_t ng, const double* rec,
-                           const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
-                           double epsilon, double* W_out, int32_t* flags, int32_t* retry_count, hipStream_t stream) {
-  if (!option(MIA_OPT_TILE) || !W_in || !W_out || !flags || !retry_count) return MIA_ERR_UNSUPPORTED;
+int lienks_patch64_launch(const double* W_in, int64_t w_stride, int k, int64_t ng, const double* rec,
+                          const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                          double epsilon, double* W_out, int32_t* flags, int32_t* retry_count, const int32_t* tile_pts,
+                          int64_t n_tiles, int union_blocks, hipStream_t stream) {
+  if (!option(MIA_OPT_TILE) || !W_in || !W_out || !flags || !retry_count || !tile_pts) return MIA_ERR_UNSUPPORTED;
   if (w_stride != 0 && w_stride != (int64_t)k * k) return MIA_ERR_UNSUPPORTED;
-  if (!lienks_stream64_route_covers(k, p_max, ng)) return MIA_ERR_UNSUPPORTED;
+  if (!lienks_patch64_route_covers(k, p_max, ng)) return MIA_ERR_UNSUPPORTED;
+  if (union_blocks < 1 || union_blocks > kLienksPatch64MaxBlocks || n_tiles < 1 || !grid_covers(n_tiles)) return MIA_ERR_UNSUPPORTED;
   const CoefTable64* tab = cheb_coef_table64(stream, kTab64Primal);
   if (!tab) return MIA_ERR_UNSUPPORTED;
-  LienksStream64Params dp;
+  LienksPatch64Params dp;
   dp.k = k; dp.kp = (k + 1 + 3) & ~3;
   dp.ng = ng; dp.Win = W_in; dp.w_stride = w_stride; dp.rec = rec;
   dp.cnt = nbr_cnt; dp.idx = nbr_idx; dp.w = nbr_w; dp.p_cap = p_cap; dp.p_max = p_max;
-  dp.ub = ring64_blocks(p_max);
+  dp.tile_pts = tile_pts; dp.n_tiles = n_tiles;
+  dp.ub = union_blocks;
   dp.transform = epsilon > 0.0 ? 0 : 1;
   dp.dscale = epsilon > 0.0 ? 1.0 / epsilon : 1.0;
   dp.dshift = epsilon > 0.0 ? epsilon : 1.0;
-  // the constants of weights_stream64_launch at inf_factor = 1: reg = k - 1, f0 = 1
+  // the constants of lienks_stream64_launch: reg = k - 1, f0 = 1
   const double rg = (double)(k - 1), km = (double)(k - 1);
   dp.reg = rg;
   dp.inv_reg = 1.0 / rg;
@@ -437,7 +448,7 @@ int lienks_stream64_launch(const double* W_in, int64_t w_stride, int k, int64_t 
   dp.W = W_out; dp.flags = flags; dp.retry_count = retry_count;
   dp.dmax = kTab64Deg - 1;
   dp.tab_hdr = tab->hdr; dp.tab_c = tab->c;
-  return dispatch_upto<8>((k + 15) >> 4, [&](auto kt) { return lienks_stream64_launch_t<kt()>(dp, stream); });
+  return dispatch_upto<8>((k + 15) >> 4, [&](auto kt) { return lienks_patch64_launch_t<kt()>(dp, stream); });
 }
 
 }  // namespace mia

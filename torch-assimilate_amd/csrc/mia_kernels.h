@@ -193,6 +193,17 @@ int lienks_stream64_launch(const double* W_in, int64_t w_stride, int k, int64_t 
                            const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max, double epsilon, double* W_out,
                            int32_t* flags, int32_t* retry_count, hipStream_t stream);
 
+// lienks_patch64.hip: lienks_stream64.hip's update with a tile's sixteen points taken from a map (4 x 4 patches of a 2-D mesh;
+// W_in, W_out, lists and flags all go through it) and the slot tables sized by the caller, 1 <= union_blocks <= 16 at every
+// ensemble size.  lienks_patch64_route_covers: shape test (host only; weights_patch64_route_covers' arithmetic);
+// lienks_patch64_launch: MIA_ERR_UNSUPPORTED outside it, with union_blocks outside 1 .. 16, more tiles than a launch grid, the
+// option tile = 0, and when the float64 coefficient table cannot be had.
+bool lienks_patch64_route_covers(int k, int p_max, int64_t ng);
+int lienks_patch64_launch(const double* W_in, int64_t w_stride, int k, int64_t ng, const double* rec, const int32_t* nbr_cnt,
+                          const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max, double epsilon, double* W_out,
+                          int32_t* flags, int32_t* retry_count, const int32_t* tile_pts, int64_t n_tiles, int union_blocks,
+                          hipStream_t stream);
+
 // lketkf_tile64.hip: the float64 RBF-kernelised analysis on tiles (2 <= k <= 40, lists of at most 64 observations, any number
 // of state rows; no p_max <= k condition): one workgroup of four wavefronts per tile, the pair statistic on the matrix
 // cores, a point's k x k matrix in LDS.  rbf64_route_covers: shape test (host only, the LDS of the chosen instantiation

@@ -1303,6 +1303,47 @@ class LetkfEngine:
         return (k >= self.IENKS_STREAM64_AUTO_MIN_K
                 and self.IENKS_STREAM64_AUTO_DEN * p_max <= self.IENKS_STREAM64_AUTO_NUM * k)
 
+    # LocalizedIEnKS*(..., mesh_shape=...).inner_loop_arrays hands float64 updates with tau = 1 of DENSE networks to
+    # method="patch64" (csrc/lienks_patch64.hip) with the map of 4 x 4 patches, in two cases.  (a) Wherever
+    # _ienks_stream64_auto already says yes: those calls run lienks_stream64_kernel without the map, and the bits are equal
+    # under any map.  (b) Where the general kernel runs and is the default: IENKS_PATCH64_AUTO_MIN_K <= k <=
+    # IENKS_PATCH64_AUTO_MAX_K and IENKS_PATCH64_AUTO_DEN * p_max <= IENKS_PATCH64_AUTO_NUM * k -- the range in which every
+    # MEASURED case is at least 2x the general kernel in the variants it holds, beyond both spreads, counter read included
+    # (tools/time_ienks_patch64.py, profiles/ienks_patch64_time.json).
+    # Measured on MI355X, 316 x 316 meshes (224 x 224 at k = 128) with an observation at every point, radius 3 (3.5), p_max 101
+    # (145), 4 x 4 patches (largest union 176 / 232), census (0.7 - 0.9 ms, first call only) outside, five rounds, the methods
+    # alternating, counter read included, median ms; general kernel and method="stream64" on a build of the PARENT commit /
+    # method="stream64" on this build / this route; bundle (per-point weights) and transform (shared prior):
+    #   k  40 bundle:     97.9 /  823.3 /  822.5 /  216.5   0.45x the general kernel, LOSES     3.80x the route without a map
+    #   k  40 transform: 225.7 /  822.6 /  822.4 /  215.8   1.05x, misses the factor 2           3.81x
+    #   k  64 bundle:    490.3 / 1899.8 / 1901.2 /  388.4   1.26x, misses the factor 2           4.89x
+    #   k  64 transform:    -3 / 1899.6 / 1898.7 /  387.7   (the general kernel refuses)         4.90x
+    #   k  80 bundle / transform:  -3 / 2544.4, 2542.7 / 2542.4, 2543.4 /  751.3,  748.3         3.39x, 3.40x
+    #   k  96 bundle / transform:  -3 / 4928.7, 4927.1 / 4934.3, 4932.3 / 1004.8, 1002.9         4.91x, 4.91x
+    #   k 128 bundle / transform:  -3 / 5995.0, 5992.8 / 6000.4, 5994.9 / 2343.9, 2340.4         2.56x, 2.56x
+    # (spreads at most 0.6 % of a median; method="stream64" agrees between the two builds within its spreads in all ten; W and
+    # flags bit-identical to the route without a map in all ten; nothing declined).  (a) In every one of the ten cases the slowest
+    # round of this route is below the fastest round of the parent's method="stream64", so no shape of that range is excluded.
+    # (b) NO case with a baseline reaches 2x the general kernel (0.45x, 1.05x, 1.26x), so the constants admit NOTHING where the
+    # general kernel is the default: the classes take the map under (a) only.  NOT measured: other radii, observations at every
+    # second point, ensembles between the measured sizes, the range of IENKS_STREAM64_AUTO_* where the general kernel runs (k 65 -
+    # 79 with p_max <= 77 / 65 k: taken under (a) on the strength of the cases above).  method="patch64" itself stays available
+    # everywhere the kernel covers
+    IENKS_PATCH64_AUTO_MIN_K, IENKS_PATCH64_AUTO_MAX_K = 129, 0
+    IENKS_PATCH64_AUTO_NUM, IENKS_PATCH64_AUTO_DEN = 0, 1
+
+    def _ienks_patch64_auto(self, k: int, p_max: int, bundle: bool, shared: bool) -> bool:
+        """Whether the classes name method="patch64" on a ``mesh_shape`` for a float64 update with tau = 1 (checked by the
+        caller, like the entry's cover); arguments as :meth:`_ienks_stream64_auto`."""
+        if k < 2 or k > 128 or p_max <= k or p_max > 256:
+            return False
+        if not (bundle or shared):        # per-point transform weights have Wp != I: the launch would be declined whole
+            return False
+        if self._ienks_stream64_auto(k, p_max, bundle, shared):
+            return True
+        return (self.IENKS_PATCH64_AUTO_MIN_K <= k <= self.IENKS_PATCH64_AUTO_MAX_K
+                and self.IENKS_PATCH64_AUTO_DEN * p_max <= self.IENKS_PATCH64_AUTO_NUM * k)
+
     # the float64 tile kernels of ienks_update: method -> (C entry, its cover function, the cover in words, the ensemble size
     # from which "auto" takes it -- None: never at this level).  "auto" tries them in this order
     IENKS_TILE64_ROUTES = {
@@ -1311,14 +1352,20 @@ class LetkfEngine:
         "wide64": ("mia_lienks_update_wide_f64", "mia_lienks_update_wide_f64_cover", "2 <= k <= 128 and p_max <= k",
                    "IENKS_WIDE64_AUTO_MIN_K"),
         "stream64": ("mia_lienks_update_stream_f64", "mia_lienks_update_stream_f64_cover",
-                     "2 <= k <= 128 and k < p_max <= 256", None)}
+                     "2 <= k <= 128 and k < p_max <= 256", None),
+        "patch64": ("mia_lienks_update_patch_f64", "mia_lienks_update_patch_f64_cover",
+                    "2 <= k <= 128 and k < p_max <= 256", None)}
     IENKS_TILE64_METHODS = tuple(IENKS_TILE64_ROUTES)
     IENKS_METHODS = ("auto", "eig") + IENKS_TILE64_METHODS
+    # what the two messages below name: the methods that take no further argument ("patch64" needs tile_points and has a
+    # message of its own)
+    IENKS_PLAIN_TILE64_METHODS = tuple(m for m in IENKS_TILE64_METHODS if m != "patch64")
 
     def ienks_update(self, weights: torch.Tensor, Yb: Optional[torch.Tensor], d: Optional[torch.Tensor],
                      nbrs: NeighbourLists, tau: float = 1.0, epsilon: Optional[float] = None,
                      rec: Optional[torch.Tensor] = None, return_flags: bool = False, method: str = "auto",
-                     defer_retry: bool = False, out: Optional[torch.Tensor] = None):
+                     defer_retry: bool = False, out: Optional[torch.Tensor] = None,
+                     tile_points: Optional[torch.Tensor] = None, union_blocks: Optional[int] = None):
         """One IEnKS weight update per grid point of the shard ``nbrs`` (core/ienks.py:108-141 on the localised
         block, interface/lienks.py:75-118).  ``weights``: (k, k) shared by all points (e.g. the prior weights) or
         (n, k, k); ``epsilon`` None = transform variant, a positive value = bundle variant.  Returns (n, k, k).
@@ -1332,7 +1379,18 @@ class LetkfEngine:
         kernel answers MIA_ERR_UNSUPPORTED because its LDS cannot hold the shape.  "tile64" / "wide64": those kernels by name
         (ValueError outside float64, tau = 1 and the kernel's cover); "stream64": the tile kernel for DENSE local networks
         (csrc/lienks_stream64.hip, 2 <= k <= 128 and k < p_max <= 256; the same ValueErrors), which "auto" never takes at this
-        level -- the IEnKS classes name it where :meth:`_ienks_stream64_auto` says so; "eig": general kernel.  Points a tile kernel declines are
+        level -- the IEnKS classes name it where :meth:`_ienks_stream64_auto` says so; "patch64": that kernel with the sixteen
+        points of a tile taken from ``tile_points`` (csrc/lienks_patch64.hip, mia_lienks_update_patch_f64; the same cover and
+        ValueErrors): int32 (n_tiles, 16), a point's index relative to the shard's g0 or -1, every point exactly once --
+        :func:`mesh_tiles` builds the 4 x 4 patches of a 2-D mesh, whose unions fit one pass where sixteen consecutive points
+        run in parts.  W and flags are "stream64"'s bit for bit under any map.  ``union_blocks``: sixteen-slot blocks of the
+        slot tables, 1 .. 16; None sizes them for the largest union of a tile, which the census of the map counts (one 8-byte
+        read, kept on ``nbrs`` under the map's identity and shared with ``analysis(tile_points=...)`` and ``weights_patch64``);
+        a tile whose union exceeds them runs in halves of its slots.  ValueError for method="patch64" without ``tile_points``,
+        for ``tile_points`` / ``union_blocks`` with any other method, for a map that is not a partition of the shard's points,
+        a wrong dtype or shape of it and ``union_blocks`` outside 1 .. 16, before any launch; "auto" never takes the route at
+        this level -- the IEnKS classes name it on a ``mesh_shape`` where :meth:`_ienks_patch64_auto` says so; "eig": general
+        kernel.  Points a tile kernel declines are
         redone by the general kernel (mia_lienks_update_retry_f64) behind the 8-byte read of the decline counter; where the
         general kernel cannot hold a declined point's shape that redo raises MiaError AFTER every other point has been
         written -- data-dependent, as ``weights_wide64`` documents.  With ``defer_retry`` (the named tile methods only)
@@ -1340,9 +1398,19 @@ class LetkfEngine:
         redone).  ``out``: a contiguous (n, k, k) tensor of the weights' dtype to write into."""
         tile_methods = self.IENKS_TILE64_METHODS
         if method not in self.IENKS_METHODS:
-            raise ValueError("method must be " + _one_of(self.IENKS_METHODS))
+            raise ValueError("method must be " + _one_of(("auto", "eig") + self.IENKS_PLAIN_TILE64_METHODS))
         if defer_retry and method not in tile_methods:
-            raise ValueError("defer_retry needs method=" + _one_of(tile_methods))
+            raise ValueError("defer_retry needs method=" + _one_of(self.IENKS_PLAIN_TILE64_METHODS))
+        if method == "patch64":
+            if tile_points is None:
+                raise ValueError("the patch64 route needs tile_points (see mesh_tiles)")
+            if (not isinstance(tile_points, torch.Tensor) or tile_points.dtype != torch.int32 or tile_points.dim() != 2
+                    or tile_points.shape[1] != 16):
+                raise ValueError("tile_points must be an int32 tensor (n_tiles, 16)")
+            if union_blocks is not None and not 1 <= int(union_blocks) <= self.WEIGHTS_PATCH64_MAX_BLOCKS:
+                raise ValueError("union_blocks must lie in 1 .. %d" % self.WEIGHTS_PATCH64_MAX_BLOCKS)
+        elif tile_points is not None or union_blocks is not None:
+            raise ValueError("tile_points and union_blocks belong to method='patch64' (method='%s')" % method)
         weights = torch.as_tensor(weights)
         dtype = weights.dtype if weights.dtype in (torch.float32, torch.float64) else torch.float64
         weights = weights.to(device=self.device, dtype=dtype).contiguous()
@@ -1374,10 +1442,11 @@ class LetkfEngine:
         tail = (eps_c, _ptr(out), _ptr(flags))
         cover_args = (k, min(nbrs.p_max, nbrs.p_cap), n, rec.shape[0])
 
-        def tile_route(entry):
-            """The tile kernel behind ``entry`` and the redo of what it declines; None where the entry answers -3."""
+        def tile_route(entry, extra=()):
+            """The tile kernel behind ``entry`` and the redo of what it declines; None where the entry answers -3.  ``extra``: the
+            entry's further arguments in front of the stream (patch64's map, number of tiles and blocks)."""
             retry = torch.zeros(1, dtype=torch.int32, device=self.device)
-            rc = getattr(self.lib, entry)(*head, *tail, _ptr(retry), self._stream())
+            rc = getattr(self.lib, entry)(*head, *tail, _ptr(retry), *extra, self._stream())
             if rc == -3:
                 return None
             _cabi.check(rc, entry)
@@ -1388,7 +1457,7 @@ class LetkfEngine:
         f64_tau1 = dtype == torch.float64 and float(tau) == 1.0 and n > 0
         # (per-point weights of the transform variant have Wp != I everywhere: a tile launch would be declined whole)
         variant_ok = epsilon is not None or weights.dim() == 2
-        entry = None
+        entry, extra = None, ()
         if method in tile_methods:
             if dtype != torch.float64:
                 raise ValueError("method='%s' needs float64 weights (float32 has its own route under 'auto')" % method)
@@ -1397,6 +1466,12 @@ class LetkfEngine:
             entry, cover, text, _ = self.IENKS_TILE64_ROUTES[method]
             if not getattr(self.lib, cover)(*cover_args):
                 raise ValueError("method='%s' covers %s (k = %d, p_max = %d)" % (method, text, k, nbrs.p_max))
+            if method == "patch64":
+                # the map: validated (ValueError) and sized by the census, once per (lists, map), before any launch
+                extra = (None, 0, 1)
+                if n > 0:
+                    tp, ub, _ = self._patch64_map(nbrs, tile_points, union_blocks, k, self.WEIGHTS_PATCH64_MAX_BLOCKS)
+                    extra = (_ptr(tp), tp.shape[0], ub)
         elif dtype == torch.float32 and float(tau) == 1.0 and n > 0 and method != "eig":
             # tau = 1 through the eigensolver-free weights kernel; -3 = shape outside it (primal route, order > 32)
             res = tile_route("mia_lienks_update_matfun_f32")
@@ -1408,7 +1483,7 @@ class LetkfEngine:
                     entry = name
                     break
         if entry is not None:
-            res = tile_route(entry)
+            res = tile_route(entry, extra)
             if res is not None:
                 return res
             if method in tile_methods:

@@ -50,6 +50,21 @@ def _ienks_method(eng: LetkfEngine, dtype, k: int, nbrs, tau: float, epsilon: Op
     return "stream64" if tile.value else "auto"          # (option tile = 0 switches every tile route off: as before)
 
 
+def _ienks_patch64(eng: LetkfEngine, dtype, k: int, nbrs, tau: float, epsilon: Optional[float], shared: bool) -> bool:
+    """Whether the localised classes hand an update on a ``mesh_shape`` to method="patch64" (csrc/lienks_patch64.hip): float64,
+    tau = 1, ``LetkfEngine._ienks_patch64_auto`` and the kernel's cover say yes, and the tile routes are on."""
+    if dtype != torch.float64 or float(tau) != 1.0 or nbrs.g1 <= nbrs.g0:
+        return False
+    p_max = min(nbrs.p_max, nbrs.p_cap)
+    if not eng._ienks_patch64_auto(k, p_max, epsilon is not None, shared):
+        return False
+    if not eng.lib.mia_lienks_update_patch_f64_cover(k, p_max, nbrs.g1 - nbrs.g0, max(p_max, 1)):
+        return False
+    tile = C.c_int(1)
+    eng.lib.mia_get_option(b"tile", C.byref(tile))
+    return bool(tile.value)
+
+
 class IEnKSTransformModule(ETKFModule):
     """core/ienks.py:29-141.  In float64 with tau = 1 a block of more observations than members (up to 256, up to 128
     members) that the general kernel cannot hold goes through the dense tile kernel (csrc/lienks_stream64.hip), as one tile
@@ -114,16 +129,23 @@ class LocalizedIEnKSTransform(LETKF):
     more than members: from 69 members on) and inside ``LetkfEngine.IENKS_STREAM64_AUTO_*`` (from 65 members on with at most
     77 / 65 k local observations, the measured range in which the route is at least 2x the general kernel).
     Every later iteration has Wp != I and stays on the general kernel, which above 64 members holds only short observation
-    lists (e.g. not k = 80 with 63): there the second iteration raises MiaError."""
+    lists (e.g. not k = 80 with 63): there the second iteration raises MiaError.
+    ``mesh_shape=(ny, nx)``: the grid points are a row-major 2-D mesh.  Wherever ``LetkfEngine._ienks_patch64_auto`` says yes
+    -- everywhere the dense tile kernel is taken without it, and inside ``LetkfEngine.IENKS_PATCH64_AUTO_*`` -- that first
+    iteration runs the dense tile kernel under the map of 4 x 4 patches (csrc/lienks_patch64.hip, ``mesh_tiles``): a patch's
+    union fits one pass where sixteen consecutive points of a row run in parts; the weights are the same bit for bit.  A
+    ``mesh_shape`` that does not have the state's number of grid points is ignored with a RuntimeWarning; float32, tau < 1 and
+    the unlocalised driver never look at it."""
     _epsilon: Optional[float] = None
 
     def __init__(self, forward_model: Callable, localization=None, tau: float = 1.0, max_iter: int = 10,
                  smoother: bool = False, gpu: bool = True, pre_transform=None, post_transform=None,
                  chunksize: int = 10, weight_save_path=None, dtype: torch.dtype = torch.float32,
-                 engine: Optional[LetkfEngine] = None):
+                 engine: Optional[LetkfEngine] = None, mesh_shape=None):
         super().__init__(localization=localization, inf_factor=1.0, smoother=smoother, gpu=gpu,
                          pre_transform=pre_transform, post_transform=post_transform, chunksize=chunksize,
-                         weight_save_path=weight_save_path, forward_model=forward_model, dtype=dtype, engine=engine)
+                         weight_save_path=weight_save_path, forward_model=forward_model, dtype=dtype, engine=engine,
+                         mesh_shape=mesh_shape)
         self.max_iter = int(max_iter)
         self.tau = tau
 
@@ -172,7 +194,14 @@ class LocalizedIEnKSTransform(LETKF):
         nb = self._lists(grid_coords, obs_coords, 0, None, grid_info, obs_info)
         w = self._dev(weights)
         dtype = w.dtype if w.dtype in (torch.float32, torch.float64) else torch.float64
-        method = _ienks_method(self.engine, dtype, w.shape[-1], nb, self.tau, self._epsilon, w.dim() == 2)
+        k, shared = w.shape[-1], w.dim() == 2
+        if self.mesh_shape is not None and _ienks_patch64(self.engine, dtype, k, nb, self.tau, self._epsilon, shared):
+            # (float64 only: the map of the shard's 4 x 4 patches, or None with a warning for a mesh of another size)
+            tiles = self._mesh_map_of(dtype, len(grid_coords), nb)
+            if tiles is not None:
+                return self.engine.ienks_update(w, self._dev(yb), self._dev(d), nb, self.tau, self._epsilon, method="patch64",
+                                                tile_points=tiles)
+        method = _ienks_method(self.engine, dtype, k, nb, self.tau, self._epsilon, shared)
         return self.engine.ienks_update(w, self._dev(yb), self._dev(d), nb, self.tau, self._epsilon, method=method)
 
     def update_state_arrays(self, state, observe: Callable, grid_coords=None, obs_coords=None,
@@ -213,15 +242,20 @@ class LocalizedIEnKSBundle(LocalizedIEnKSTransform):
     80 members on, e.g. k = 96 with 107 or k = 128 with 203) and inside ``LetkfEngine.IENKS_STREAM64_AUTO_*`` (from 65 members
     on with at most 77 / 65 k local observations, the measured range in which the route is at least 2x the general kernel); the
     unlocalised ``IEnKSBundle`` takes the kernel with its one block only where the general kernel cannot hold it.  tau < 1, more than 256 local
-    observations and more than 128 members stay on the general kernel."""
+    observations and more than 128 members stay on the general kernel.
+    ``mesh_shape=(ny, nx)``: the grid points are a row-major 2-D mesh.  Wherever ``LetkfEngine._ienks_patch64_auto`` says yes
+    -- everywhere the dense tile kernel is taken without it, and inside ``LetkfEngine.IENKS_PATCH64_AUTO_*`` -- every
+    iteration runs the dense tile kernel under the map of 4 x 4 patches (csrc/lienks_patch64.hip, ``mesh_tiles``), with the
+    same weights bit for bit; a ``mesh_shape`` of another size is ignored with a RuntimeWarning, float32 and tau < 1 never
+    look at it."""
 
     def __init__(self, forward_model: Callable, localization=None, tau: float = 1.0, epsilon: float = 1e-4,
                  max_iter: int = 10, smoother: bool = False, gpu: bool = True, pre_transform=None,
                  post_transform=None, chunksize: int = 10, weight_save_path=None,
-                 dtype: torch.dtype = torch.float32, engine: Optional[LetkfEngine] = None):
+                 dtype: torch.dtype = torch.float32, engine: Optional[LetkfEngine] = None, mesh_shape=None):
         super().__init__(forward_model, localization=localization, tau=tau, max_iter=max_iter, smoother=smoother,
                          gpu=gpu, pre_transform=pre_transform, post_transform=post_transform, chunksize=chunksize,
-                         weight_save_path=weight_save_path, dtype=dtype, engine=engine)
+                         weight_save_path=weight_save_path, dtype=dtype, engine=engine, mesh_shape=mesh_shape)
         self.epsilon = epsilon
 
     @property

@@ -201,8 +201,9 @@ class LETKF(ETKF):
         # 4 x 4 patches (engine.mesh_tiles), which the dense route takes under LetkfEngine.PATCH64_AUTO_*; the result is the
         # same bit for bit; the float64 weights of dense networks (estimate_weights_arrays, weight_save_path) take the same map
         # to engine.weights_patch64 under LetkfEngine.WEIGHTS_PATCH64_AUTO_*, bit for bit as well.  Ignored (with a warning)
-        # when ny * nx is not the number of grid points; the other weights paths, the kernelised filter, IEnKS and float32 never
-        # look at it
+        # when ny * nx is not the number of grid points; the other weights paths, the kernelised filter and float32 never
+        # look at it.  The localised IEnKS classes (ienks.py) pass their own mesh_shape here and take the same map for the
+        # dense float64 update under LetkfEngine._ienks_patch64_auto
         self.mesh_shape = None if mesh_shape is None else (int(mesh_shape[0]), int(mesh_shape[1]))
         self._mesh_maps = {}
 
