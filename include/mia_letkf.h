@@ -514,6 +514,34 @@ int mia_letkf_analysis_stream_f64(const double* X, int64_t ldx, int m, int k, in
                                   void* stream);
 int mia_letkf_stream_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P);
 
+/* The analysis of mia_letkf_analysis_stream_f64 with the sixteen points of a tile taken from a MAP (csrc/letkf_patch64s.hip;
+ * what it replaces per point is unchanged: the gather and sqrt(rho) scaling of interface/wrapper.py:86-98, the decomposition
+ * and weights of core/etkf.py:57-103, the transform of interface/base.py:257-278): the same kernel -- mathematics, ring,
+ * streamed bound, coefficient table, flags, decline counter, the point-by-point mode after a non-finite record -- with
+ * mia_letkf_analysis_patch_f64's two changes to the frame.  On a row-major 2-D mesh sixteen consecutive points are a 16 x 1
+ * strip whose lists have a union of 200 observations at radius 3: it overflows the slot table the launch without a map
+ * takes and runs in parts; a 4 x 4 patch has 176 and runs in one pass.  tile_pts [n_tiles][16] int32: the point of slot s of
+ * tile t as an index into [0, g1 - g0), or -1 for an empty slot; every point of the range must occur exactly once
+ * (mia_letkf_tile_union_census checks it; this entry trusts the map except that an entry outside the range is treated as
+ * empty).  union_blocks: sixteen-slot blocks of the sqrt(rho) table and the slot table in LDS, 1 <= union_blocks <= 16 at
+ * every ensemble size (the records are not resident); a tile whose union exceeds them runs in halves of its slots, a single
+ * list longer than 16 union_blocks is MIA_FLAG_OVERFLOW and NaN output for that point.  Lists, flags and outputs stay in
+ * natural point order, so declined points are redone by mia_letkf_analysis_retry_f64 unchanged (with its data-dependent
+ * MIA_ERR_UNSUPPORTED from 97 members on, as for mia_letkf_analysis_stream_f64).  Xa and flags are those of
+ * mia_letkf_analysis_stream_f64 bit for bit under any map, any union_blocks, any shard and any m.  Argument list, validation
+ * order and return codes as mia_letkf_analysis_patch_f64: n_tiles < 0 and union_blocks < 1 among the sizes (MIA_ERR_SIZE),
+ * tile_pts among the pointers (MIA_ERR_NULL), n_tiles == 0 for a non-empty range MIA_ERR_SIZE, an empty shard 0; outside the
+ * cover, with gamma > 0, the option "tile" = 0 or a coefficient table that cannot be had MIA_ERR_UNSUPPORTED before any
+ * launch; union_blocks > 16 MIA_ERR_SIZE at every k.
+ * mia_letkf_patch_stream_f64_cover: mia_letkf_stream_f64_cover's answer (host only, no device work). */
+int mia_letkf_analysis_patch_stream_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
+                                        const double* rec, int64_t P,
+                                        const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w,
+                                        int p_cap, int p_max, double inf_factor, double gamma,
+                                        double* Xa, int64_t ldo, int64_t o0, int32_t* flags, int32_t* retry_count,
+                                        const int32_t* tile_pts, int64_t n_tiles, int union_blocks, void* stream);
+int mia_letkf_patch_stream_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P);
+
 /* The analysis of mia_letkf_analysis_matfun_f64 for ensembles ABOVE 64 members (csrc/letkf_wide64.hip): the same mathematics,
  * input, prologue, coefficient table (target exp(-26), margin 2, degree cap 127), flags and decline counter, with the
  * sixteen-slot row blocks of a tile's union split over the two (up to 96 slots) or four (up to 128) wavefronts of a

@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libmia_letkf.so")
 STAMP = os.path.join(LIB_DIR, "libmia_letkf.stamp")
-SOURCES = ["localize.hip", "letkf_entry.hip", "etkf_global.hip", "letkf_wave.hip", "letkf_sys.hip", "letkf_cheb.hip", "letkf_tile.hip", "letkf_tile_split.hip", "letkf_tile64.hip", "letkf_tile64w.hip", "letkf_dense64.hip", "letkf_patch64.hip", "letkf_stream64.hip", "letkf_stream64w.hip", "letkf_patch64w.hip", "letkf_wide64.hip", "letkf_wide64w.hip", "letkf_tile2.hip", "letkf_tile2w.hip", "letkf_tile2p.hip", "letkf_tile2f.hip", "lketkf_tile.hip", "lketkf_tile64.hip", "lketkf_kern64.hip", "tile_lists.hip", "sharded_step.hip", "step_comm.hip", "obs_space.hip", "ienks.hip", "lienks_tile64.hip", "lienks_wide64.hip", "lienks_stream64.hip", "lienks_patch64.hip", "apply_local.hip", "apply_local64.hip", "api.cc"]
+SOURCES = ["localize.hip", "letkf_entry.hip", "etkf_global.hip", "letkf_wave.hip", "letkf_sys.hip", "letkf_cheb.hip", "letkf_tile.hip", "letkf_tile_split.hip", "letkf_tile64.hip", "letkf_tile64w.hip", "letkf_dense64.hip", "letkf_patch64.hip", "letkf_stream64.hip", "letkf_stream64w.hip", "letkf_patch64w.hip", "letkf_patch64s.hip", "letkf_wide64.hip", "letkf_wide64w.hip", "letkf_tile2.hip", "letkf_tile2w.hip", "letkf_tile2p.hip", "letkf_tile2f.hip", "lketkf_tile.hip", "lketkf_tile64.hip", "lketkf_kern64.hip", "tile_lists.hip", "sharded_step.hip", "step_comm.hip", "obs_space.hip", "ienks.hip", "lienks_tile64.hip", "lienks_wide64.hip", "lienks_stream64.hip", "lienks_patch64.hip", "apply_local.hip", "apply_local64.hip", "api.cc"]
 HEADERS = ["mia_common.h", "mia_options.h", "mia_jacobi.h", "mia_jacobi_sym.h", "mia_kernel_prog.h", "mia_localize_dev.h", "mia_kernels.h", "mia_cheb_table64.h", "mia_pack_dev.h", "mia_step_comm.h", "mia_tiles.h", "mia_tile_launch.h", "mia_frames64.h", "mia_ring64_dev.h", "mia_lienks_stream64_dev.h", os.path.join(ROOT, "include", "mia_letkf.h")]
 INCLUDES = {"letkf_tile_split.hip": ["letkf_tile.hip"], "lketkf_kern64.hip": ["lketkf_tile64.hip"]}     # sources that include another source
 # per-source flags.  letkf_tile2.hip: no SLP vectoriser -- it packs the recurrence's scalar f32 multiply-adds into v_pk_fma_f32,

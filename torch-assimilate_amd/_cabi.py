@@ -85,6 +85,9 @@ _PROTOS = {
     "mia_letkf_tile_union_census": ([vp, i64, i64, vp, vp, i32, i32, i32, vp, vp, sz, vp], i32),
     "mia_letkf_analysis_stream_f64": _analysis_entry(f64),
     "mia_letkf_stream_f64_cover": _COVER7,
+    "mia_letkf_analysis_patch_stream_f64": ([vp, i64, i32, i32, i64, i64, vp, i64, vp, vp, vp, i32, i32, f64, f64,
+                                             vp, i64, i64, vp, vp, vp, i64, i32, vp], i32),
+    "mia_letkf_patch_stream_f64_cover": _COVER7,
     "mia_letkf_analysis_wide_f64": _analysis_entry(f64),
     "mia_letkf_wide_f64_cover": _COVER7,
     "mia_lketkf_rbf_analysis_matfun_f64": _analysis_entry(f64),

@@ -399,6 +399,25 @@ extern "C" int mia_letkf_stream_f64_cover(int m, int k, int p_max, int64_t ldx, 
   if (P < 0) return 0;
   return stream64_route_covers(m, k, p_max, ldx, ldo, n_points) ? 1 : 0;
 }
+// the streamed route with a tile map and caller-sized slot tables (letkf_patch64s.hip): mia_letkf_analysis_patch_f64's
+// validation, the map's arguments among the sizes and pointers, then the one kernel of the route
+extern "C" int mia_letkf_analysis_patch_stream_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
+                                                   const double* rec, int64_t P, const int32_t* nbr_cnt,
+                                                   const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                                                   double inf_factor, double gamma, double* Xa, int64_t ldo, int64_t o0,
+                                                   int32_t* flags, int32_t* retry_count, const int32_t* tile_pts,
+                                                   int64_t n_tiles, int union_blocks, void* stream) {
+  (void)hipGetLastError();
+  const int rc = tile_entry_checks(kGammaRefused, X, ldx, m, k, g0, g1, rec, P, nbr_cnt, nbr_idx, nbr_w, p_cap, &p_max, inf_factor,
+                                   gamma, Xa, ldo, o0, tile_pts, flags, retry_count, nullptr, 0, n_tiles, union_blocks);
+  if (rc != kLaunch) return rc;
+  return patch64s_analysis_launch(X, ldx, m, k, g0, g1 - g0, rec, nbr_cnt, nbr_idx, nbr_w, p_cap, p_max, inf_factor, Xa, ldo, o0,
+                                  flags, retry_count, tile_pts, n_tiles, union_blocks, (hipStream_t)stream);
+}
+extern "C" int mia_letkf_patch_stream_f64_cover(int m, int k, int p_max, int64_t ldx, int64_t ldo, int64_t n_points, int64_t P) {
+  if (P < 0) return 0;
+  return stream64_route_covers(m, k, p_max, ldx, ldo, n_points) ? 1 : 0;
+}
 // float64 on tiles for ensembles up to 128 members (letkf_wide64.hip): the same validation, then the one kernel of the route
 extern "C" int mia_letkf_analysis_wide_f64(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t g1,
                                            const double* rec, int64_t P, const int32_t* nbr_cnt,

@@ -48,7 +48,7 @@ static inline size_t wide64_lds_bytes(int ut, int kt, int nw) {
                   (size_t)(umax + nw) * sizeof(int), 16);
 }
 
-// ---- ring (letkf_stream64, letkf_stream64w, lienks_stream64, letkf_patch64w, lienks_patch64): the union's records streamed, k <= 128.
+// ---- ring (letkf_stream64, letkf_stream64w, lienks_stream64, letkf_patch64w, lienks_patch64, letkf_patch64s): the union's records streamed, k <= 128.
 // ring [2][16][kp | 1] + rhs [4 KT][64] + sqrt(rho) [16][16 ub + 1] doubles, slot table [16 ub] ints
 constexpr int kRing64MaxBlocks = 16;                            // 256 slots, at every ensemble size of the routes
 static inline size_t ring64_lds_bytes(int ub, int k) {

@@ -174,6 +174,16 @@ int weights_patch64_launch(int k, int64_t ng, const double* rec, const int32_t* 
                            const double* nbr_w, int p_cap, int p_max, double inf_factor, double* W, int32_t* flags,
                            int32_t* retry_count, const int32_t* tile_pts, int64_t n_tiles, int union_blocks, hipStream_t stream);
 
+// letkf_patch64s.hip: letkf_stream64.hip's analysis with a tile's sixteen points taken from a map (4 x 4 patches of a 2-D mesh)
+// and the slot tables sized by the caller; the cover is stream64_route_covers.  patch64s_analysis_launch: MIA_ERR_UNSUPPORTED
+// outside it, with ng >= 2^31 (the map's entries are int32), more tiles than a launch grid holds, the option tile = 0, and when
+// the coefficient table cannot be had; MIA_ERR_SIZE for union_blocks outside 1 .. 16, at every ensemble size.  The map is
+// validated by tile_union_census_launch (letkf_patch64.hip).
+int patch64s_analysis_launch(const double* X, int64_t ldx, int m, int k, int64_t g0, int64_t ng, const double* rec,
+                             const int32_t* nbr_cnt, const int32_t* nbr_idx, const double* nbr_w, int p_cap, int p_max,
+                             double inf_factor, double* Xa, int64_t ldo, int64_t o0, int32_t* flags, int32_t* retry_count,
+                             const int32_t* tile_pts, int64_t n_tiles, int union_blocks, hipStream_t stream);
+
 // lienks_wide64.hip: lienks_tile64.hip's float64 IEnKS weight update with tau = 1 for ensembles up to 128 members on
 // letkf_wide64w.hip's frame (2 <= k <= 128, p_max <= k): the weights at inflation 1 with the innovations shifted by
 // D^T w_mean, the row blocks of the union split over two or four wavefronts.  lienks_wide64_route_covers: shape test (host

@@ -1,6 +1,6 @@
 // The device frame of the streamed ("ring") float64 tile kernels for DENSE local networks (p_max > k) of ensembles up to 128
 // members: letkf_stream64.hip (analysis), letkf_stream64w.hip (weights, 2.19), lienks_stream64.hip (IEnKS update,
-// 2.20), letkf_patch64w.hip (weights under a tile map, 2.22) and lienks_patch64.hip (IEnKS update under a tile map, 2.23).  Each of them keeps its __global__ kernel, its head (lists,
+// 2.20), letkf_patch64w.hip (weights under a tile map, 2.22), lienks_patch64.hip (IEnKS update under a tile map, 2.23) and letkf_patch64s.hip (analysis under a tile map, 2.24).  Each of them keeps its __global__ kernel, its head (lists,
 // overflow, map, prior scan), the passes over the union written out in its body, the start vector of a pass and its stores;
 // what they share stands here once: the block -> tile map, the ring, the table's coefficient pair and the two
 // steps of the recurrence.

@@ -757,6 +757,49 @@ class LetkfEngine:
         return (m <= self.PATCH64_AUTO_MAX_ROWS and k >= self.PATCH64_AUTO_MIN_K
                 and self.PATCH64_AUTO_DEN * p_max <= self.PATCH64_AUTO_NUM * k)
 
+    # LETKF(..., mesh_shape=...).analyse_arrays hands a float64 analysis that method="auto" would run on letkf_stream64_kernel
+    # (_stream64_auto) to method="patch64s" (csrc/letkf_patch64s.hip: the same kernel under the map of 4 x 4 patches) where the
+    # census says every tile fits one pass (largest union <= 256) and PATCH64S_AUTO_MIN_K <= k <= PATCH64S_AUTO_MAX_K,
+    # PATCH64S_AUTO_DEN * p_max <= PATCH64S_AUTO_NUM * k and m <= PATCH64S_AUTO_MAX_ROWS -- the range in which every MEASURED
+    # case is faster than method="stream64" on a build of the PARENT commit beyond both spreads (slowest sample of this route
+    # against the fastest of the baseline; the criterion of _ienks_patch64_auto's case (a): the bits are equal under any map, so
+    # there is nothing else to weigh).  method="auto" itself never takes the route: the hand-over lives in the class, as for
+    # estimate_weights_arrays and the IEnKS classes.
+    # Measured on MI355X (tools/time_patch64s.py, profiles/patch64s_time.json), 316 x 316 meshes (224 x 224 at k = 128)
+    # with an observation at every point, radius 3 (3.5), p_max 101 (145), 4 x 4 patches (largest union 176 / 232), census (0.7 -
+    # 0.9 ms, first call only) outside, three rounds of four calls, the methods alternating, counter read included, median ms
+    # per call; Jacobi kernel and method="stream64" on a build of the parent commit / method="stream64" on this build / this route:
+    #   k  65 m 1:  288.2 /  57.18 /  57.14 / 10.60   5.39x the route without a map (worst round against best: 5.33x)   27.1x the Jacobi kernel
+    #   k  80 m 1:  868.4 /  56.05 /  56.01 / 14.60   3.84x (3.78x)                                                       59.5x
+    #   k  96 m 1: 1434.1 /  87.93 /  87.89 / 16.12   5.45x (5.45x)                                                       89.0x
+    #   k  80 m 8:  927.0 / 284.97 / 285.24 / 82.02   3.47x (3.47x)                                                       11.3x
+    #   k 128 m 1: MiaError / 80.46 / 80.47 / 29.50   2.73x (2.72x)                                       (no Jacobi kernel)
+    # (spreads at most 0.25 ms; method="stream64" agrees between the two builds within its spreads in all five -- its kernel is
+    # unchanged; Xa and flags bit-identical to the route without a map in all five; nothing declined; k 80 m 1 reproduces the
+    # 56.0 ms that STREAM64_AUTO_*'s table records for this mesh).  A further state row costs 9.6 ms here against 32.7 ms without
+    # the map (k 80).  Every measured case passes, so the rule is the range that was measured: 65 .. 128 members, p_max / k up to
+    # the largest measured (101 / 65 = 1.55), up to the 8 state rows that were measured (at k = 80 only).  NOT measured: other
+    # radii, observations at every second point or sparser, ensembles between the measured sizes, 2 - 7 state rows, 8 rows at any
+    # k but 80, p_max / k above 1.55; there the class stays on method="auto".  method="patch64s" itself stays available
+    # everywhere the kernel covers
+    PATCH64S_AUTO_MIN_K, PATCH64S_AUTO_MAX_K = 65, 128
+    PATCH64S_AUTO_NUM, PATCH64S_AUTO_DEN = 101, 65
+    PATCH64S_AUTO_MAX_ROWS = 8
+    PATCH64S_MAX_BLOCKS = 16               # kPatch64SMaxBlocks (csrc/letkf_patch64s.hip): 256 slots at every ensemble size
+
+    def _patch64s_auto(self, m: int, k: int, p_max: int) -> bool:
+        """Whether LETKF(mesh_shape=...) names method="patch64s" for a float64 analysis that "auto" would hand to
+        letkf_stream64_kernel (the class checks :meth:`_stream64_auto`, the cover and the census beside this)."""
+        if k < 2 or k > 128 or p_max <= k or p_max > 256:
+            return False
+        return (self.PATCH64S_AUTO_MIN_K <= k <= self.PATCH64S_AUTO_MAX_K and m <= self.PATCH64S_AUTO_MAX_ROWS
+                and self.PATCH64S_AUTO_DEN * p_max <= self.PATCH64S_AUTO_NUM * k)
+
+    def patch64s_fits(self, nbrs: NeighbourLists, tile_points: torch.Tensor, k: int) -> bool:
+        """Whether every tile of the map runs in ONE pass of analysis(method="patch64s") (largest union <= 256): the census,
+        once per map."""
+        return self._patch64_map(nbrs, tile_points, None, k, self.PATCH64S_MAX_BLOCKS)[2]
+
     @staticmethod
     def _dense64_capacity_blocks(k: int) -> int:
         """Restates dense64_capacity_blocks / patch64_capacity_blocks (csrc): sixteen-slot blocks of the record image that fit
@@ -830,6 +873,15 @@ class LetkfEngine:
                      ("wide64", "mia_letkf_analysis_wide_f64", _wide64_auto),
                      ("stream64", "mia_letkf_analysis_stream_f64", _stream64_auto))
     TILE64_METHODS = tuple(r[0] for r in TILE64_ROUTES)
+    # ... and the rows that only their own name takes ("auto" never does at this level: the class names the method under
+    # _patch64s_auto, as the IEnKS classes name ienks_update's "stream64" and "patch64"); the "method must be one of" message
+    # lists ANALYSIS_METHODS, the methods that need no further argument or had their place there first
+    TILE64_NAMED_ROUTES = (("patch64s", "mia_letkf_analysis_patch_stream_f64", None),)
+    TILE64_NAMED_METHODS = tuple(r[0] for r in TILE64_NAMED_ROUTES)
+    # the rows with steps of their own in front of the entry -- the caller's tile map, the cover, the census (once per map):
+    # method -> (cover function, the route's largest image in sixteen-slot blocks; None = the dense route's at this ensemble size)
+    TILE64_MAP_ROUTES = {"patch64": ("mia_letkf_patch_f64_cover", None),
+                         "patch64s": ("mia_letkf_patch_stream_f64_cover", PATCH64S_MAX_BLOCKS)}
 
     def analysis(self, X: torch.Tensor, Yb: Optional[torch.Tensor], d: Optional[torch.Tensor],
                  nbrs: NeighbourLists, inf_factor: float = 1.0, return_weights: bool = False,
@@ -858,7 +910,14 @@ class LetkfEngine:
         records streamed through a ring in LDS instead of a resident image (2 <= k <= 128, k < p_max <= 256, same conditions;
         what dense networks of 65 .. 128 members run -- "auto" takes it from STREAM64_AUTO_MIN_K members on wherever the Jacobi
         kernel cannot hold the shape, k >= 97, and elsewhere only inside STREAM64_AUTO_*; a point it declines is redone by the
-        Jacobi kernel, and at k >= 97 that redo raises MiaError AFTER the other points have been written, as below); "rbf64" = the RBF-kernelised core in float64 on
+        Jacobi kernel, and at k >= 97 that redo raises MiaError AFTER the other points have been written, as below);
+        "patch64s" = stream64's analysis with the sixteen points of a tile taken from ``tile_points`` as for "patch64"
+        (csrc/letkf_patch64s.hip, mia_letkf_analysis_patch_stream_f64; stream64's cover and conditions, stream64's bits under
+        any map; ``union_blocks`` 1 .. 16 at every ensemble size, None = sized for the largest union the census counts, which
+        is shared with "patch64", ``weights_patch64`` and ``ienks_update(method="patch64")``; a tile whose union exceeds the
+        blocks runs in halves of its slots; ValueError without ``tile_points``, for a wrong dtype or shape of the map, a map
+        that is no partition of the shard's points and ``union_blocks`` outside 1 .. 16, before any launch); "auto" never
+        takes it at this level -- LETKF(mesh_shape=...) names it where :meth:`_patch64s_auto` says so; "rbf64" = the RBF-kernelised core in float64 on
         tiles (``rbf_gamma`` given, 2 <= k <= 40, lists of at most 64 observations -- no p_max <= k condition --, no
         ``kernel_program``, no weights; csrc/lketkf_tile64.hip); "kern64" = the same kernel with K from a ``kernel_program``
         (float64, the cover of rbf64, ``kernel_psd=True``, no tanh / sin, no weights; csrc/lketkf_kern64.hip); "auto" picks
@@ -900,10 +959,10 @@ class LetkfEngine:
             self._keep_rec = rec      # (a record buffer packed during HIP-graph capture must outlive the capture)
         if rec.dtype != dtype or rec.shape[1] != (k + 1 + 3) // 4 * 4:
             raise ValueError("packed records do not match the state's dtype / ensemble size")
-        if method not in self.ANALYSIS_METHODS:
+        if method not in self.ANALYSIS_METHODS + self.TILE64_NAMED_METHODS:
             raise ValueError("method must be " + _one_of(self.ANALYSIS_METHODS))
-        if method == "patch64" and tile_points is None:
-            raise ValueError("the patch64 route needs tile_points (see mesh_tiles)")
+        if method in self.TILE64_MAP_ROUTES and tile_points is None:
+            raise ValueError("the %s route needs tile_points (see mesh_tiles)" % method)
         # float64 RBF-kernelised filter on tiles (csrc/lketkf_tile64.hip): 2 <= k <= 40, lists of at most 64 observations, no weights
         can_rbf64 = dtype == torch.float64 and not return_weights and rbf_gamma is not None and kernel_program is None
         if method == "rbf64" and not can_rbf64:
@@ -972,30 +1031,31 @@ class LetkfEngine:
         # under STREAM64_AUTO_*, the one with a map under PATCH64_AUTO_*) and falls back to the Jacobi kernel elsewhere; a
         # route's own name takes that row alone and raises there instead.
         can_matfun64 = dtype == torch.float64 and not return_weights and rbf_gamma is None
-        if method in self.TILE64_METHODS and not can_matfun64:
+        if method in self.TILE64_METHODS + self.TILE64_NAMED_METHODS and not can_matfun64:
             raise ValueError("the %s route needs float64, the plain ETKF core and cannot return the weights" % method)
         use_matfun = can_matfun and (method == "matfun" or (method == "auto" and m <= self.MATFUN_MAX_ROWS))
         # the eigensolver-free entry that is tried, its status, and whether -3 (shape outside the kernel, or tile = 0) hands
         # the shard to the Jacobi kernel below instead of raising
         name, rc, soft = None, -3, method == "auto"
-        if can_matfun64 and n > 0 and (method == "auto" or method in self.TILE64_METHODS):
+        if can_matfun64 and n > 0 and (method == "auto" or method in self.TILE64_METHODS + self.TILE64_NAMED_METHODS):
             if retry is None:
                 retry = torch.zeros(1, dtype=torch.int32, device=self.device)
             name = self.TILE64_ROUTES[0][1]
-            for meth, entry, auto in self.TILE64_ROUTES:
+            for meth, entry, auto in self.TILE64_ROUTES + self.TILE64_NAMED_ROUTES:
                 if rc != -3:
                     break
-                if method != meth and not (method == "auto" and auto(self, m, k, nbrs.p_max)):
+                if method != meth and not (method == "auto" and auto is not None and auto(self, m, k, nbrs.p_max)):
                     continue
                 more = ()
-                if meth == "patch64":      # the row with steps of its own: the caller's map, the cover, the census (once per map)
+                if meth in self.TILE64_MAP_ROUTES:      # the rows with steps of their own: the caller's map, the cover, the census (once per map)
                     if tile_points is None:
                         continue
                     name = entry
-                    if self.lib.mia_letkf_patch_f64_cover(m, k, nbrs.p_max, G, ldo, n, P) != 1:
+                    cover, cap = self.TILE64_MAP_ROUTES[meth]
+                    if getattr(self.lib, cover)(m, k, nbrs.p_max, G, ldo, n, P) != 1:
                         continue
-                    tp, ub, fits = self._patch64_map(nbrs, tile_points, union_blocks, k)
-                    if not fits and method != "patch64":      # ("auto": a map whose tiles would run in parts is left to the rows below)
+                    tp, ub, fits = self._patch64_map(nbrs, tile_points, union_blocks, k, cap)
+                    if not fits and method != meth:      # ("auto": a map whose tiles would run in parts is left to the rows below)
                         continue
                     more = (_ptr(tp), tp.shape[0], ub)
                 name = entry

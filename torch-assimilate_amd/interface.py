@@ -198,7 +198,8 @@ class LETKF(ETKF):
         self.localization = localization
         self.chunksize = chunksize          # dask chunking of the reference; the GPU path does not chunk
         # (ny, nx) of a row-major 2-D mesh the grid points form: the float64 analysis then hands the engine a tile map of
-        # 4 x 4 patches (engine.mesh_tiles), which the dense route takes under LetkfEngine.PATCH64_AUTO_*; the result is the
+        # 4 x 4 patches (engine.mesh_tiles), which the dense route takes under LetkfEngine.PATCH64_AUTO_* and, from 65 members
+        # on, the streamed dense route under LetkfEngine.PATCH64S_AUTO_* (method="patch64s"); the result is the
         # same bit for bit; the float64 weights of dense networks (estimate_weights_arrays, weight_save_path) take the same map
         # to engine.weights_patch64 under LetkfEngine.WEIGHTS_PATCH64_AUTO_*, bit for bit as well.  Ignored (with a warning)
         # when ny * nx is not the number of grid points; the other weights paths, the kernelised filter and float32 never
@@ -498,6 +499,21 @@ class LETKF(ETKF):
             eng.retry_points(x, yb, d, nb, self.inf_factor, xa, flags, rbf_gamma=gamma)
         return xa, flags
 
+    def _analysis_on_patch64s(self, x, yb, nb, tiles) -> bool:
+        """Whether the float64 analysis of a DENSE local network on a 2-D mesh names method="patch64s" (csrc/letkf_patch64s.hip)
+        with the map of 4 x 4 patches that ``mesh_shape`` gives (``tiles``; None: no mesh, another size, float32): where
+        ``engine.analysis(method="auto")`` would run letkf_stream64_kernel today (LetkfEngine._stream64_auto), inside the measured
+        LetkfEngine.PATCH64S_AUTO_* (_patch64s_auto), inside the kernel's cover and with a census that says every tile fits ONE
+        pass (a map that does not is left to "auto", as before).  The bits are that kernel's under any map."""
+        eng = self.engine
+        m, k, G = x.shape
+        n, p_max = nb.g1 - nb.g0, int(nb.p_max)
+        if tiles is None or n <= 0 or not (eng._stream64_auto(m, k, p_max) and eng._patch64s_auto(m, k, p_max)):
+            return False
+        if eng.lib.mia_letkf_patch_stream_f64_cover(m, k, p_max, G, n, n, int(yb.shape[1])) != 1:
+            return False
+        return bool(eng.patch64s_fits(nb, tiles, k))
+
     def analyse_arrays(self, state, yb, d, grid_coords=None, obs_coords=None, g0=0, g1=None,
                        grid_info=None, obs_info=None) -> torch.Tensor:
         """Fused path: the weights never leave the GPU's LDS -- unless a ``weight_save_path`` asks for them: then
@@ -527,6 +543,8 @@ class LETKF(ETKF):
             ka = self._kernel_args()
             if ka.get("rbf_gamma") is None and ka.get("kernel_program") is None:      # (the plain ETKF core: the kernelised
                 ka = dict(ka, tile_points=self._mesh_map(st3, nb))                    #  filter has no route that takes a map)
+                if self._analysis_on_patch64s(st3, ybd, nb, ka["tile_points"]):
+                    ka["method"] = "patch64s"
             xa, flags = self.engine.analysis(st3, ybd, dd, nb, self.inf_factor, return_flags=True, **ka)
         bad = int((flags & 0xff).max().item()) if flags.numel() else 0
         if bad & 1:
